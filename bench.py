@@ -12,6 +12,14 @@ over gloo by a coordinator child of each rank (the rank process loads one HIP
 runtime, libmpcekf's, and never imports torch).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--cells-per-gpu C | --total-cells T]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (with the
+per-kernel and roofline figures of the HIP events recorded inside those K steps).
+--full adds what takes a run of its own: the CPU baseline (the C oracle on the host
+cores and the single-core configs[0] charge).  --dump-outputs DIR writes the last timed
+step's outputs (u, v, soc, phise, nexec of every cell of the rank's shard) as
+DIR/<name>.npy in float64 (DIR/<name>_rank<r>.npy with more than one rank).
 
 --gpus N without torchrun starts N rank processes itself (one per GPU, before any
 GPU call); under torchrun the ranks come from RANK/WORLD_SIZE.  configs[3] is
@@ -314,7 +322,11 @@ def main():
     ap.add_argument("--cpu-cells", type=int, default=32768)
     ap.add_argument("--cpu-steps", type=int, default=0, help="default: warmup + steps (the GPU run's steps)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="default: the cores this process may use")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the CPU baseline (C oracle on the host cores, configs[0] on one core)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's outputs (u, v, soc, phise, nexec) as DIR/<name>.npy")
     ap.add_argument("--timing-every", type=int, default=8,
                     help="per-kernel HIP-event timing on every N-th step of the timed region (N divides "
                          "the flush period, 64)")
@@ -402,7 +414,19 @@ def main():
         status = ctx.get_state()["status"]
         nerr = int((status & 1).sum())
         u_last = outs[0].to_host(K)[K - 1] if K else np.zeros(0)
-        mean_nexec = float(nex.to_host(K).mean()) if K else 0.0
+        nex_host = nex.to_host(K) if K else None
+        mean_nexec = float(nex_host.mean()) if K else 0.0
+        if args.dump_outputs and K:
+            # the last timed step's row of each trajectory, as step_device's caller reads it
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            sfx = f"_rank{rank}" if world > 1 else ""
+            last = {"u": u_last, "nexec": nex_host[K - 1]}
+            for name, b in zip(("v", "soc", "phise"), outs[1:]):
+                last[name] = np.empty(ncell, dtype=np.float64)
+                M.check(ctx.L.mpcekf_dev_copy(last[name].ctypes.data, b.ptr + (K - 1) * b.row_bytes(),
+                                              last[name].nbytes, M._lib.COPY_D2H))
+            for name, a in last.items():
+                np.save(os.path.join(args.dump_outputs, f"{name}{sfx}.npy"), np.asarray(a, dtype=np.float64))
         build_id = ctx.L.mpcekf_build_id().decode()
         runtimes = M.hip_runtimes()
         for b in outs + [nex]:
@@ -503,7 +527,7 @@ def report(args, rom, tim, K, ncell, value, nerr, mean_nexec, u_last, build_id, 
         fp64 = {"achieved": tf, "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": tf / FP64_PEAK_TFLOPS,
                 "flops_per_launch": flops, "source": os.path.relpath(args.pmc, ROOT)}
     cpu = None
-    if world == 1 and not args.no_cpu:
+    if args.full and world == 1 and not args.no_cpu:
         cpu = cpu_baseline(rom, soc0_all, tc_all, min(args.cpu_cells, ncell), args.cpu_steps or (args.warmup + K),
                            args.cpu_threads or cpu_threads_default(), Np=args.np, Nc=args.nc)
     return {

@@ -71,3 +71,27 @@ def test_bench_ranks_map_one_runtime():
     line = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])
     assert line["config"]["timing_collectives"] == "gloo"
     _one_runtime(line["checks"]["hip_runtime"], "bench.py rank")
+
+
+def test_bench_dump_outputs_are_the_last_timed_step(tmp_path, P, M):
+    """bench.py --dump-outputs DIR: the last timed step's u, v, soc, phise, nexec of every
+    cell as float64 .npy files, equal to step warmup + steps of one runMPC call on the
+    same inputs; a plain run carries no CPU baseline."""
+    sys.path.insert(0, ROOT)
+    import bench
+    n, steps, warmup = 2048, 20, 2
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--cells-per-gpu", str(n),
+                        "--steps", str(steps), "--warmup", str(warmup), "--dump-outputs", str(tmp_path / "out")],
+                       capture_output=True, text=True, env=env, timeout=240)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])
+    assert line["steps"] == steps and line["ms_per_step"] > 0 and line["cpu_baseline"] is None
+    soc0, tc = bench.batch_inputs(n)
+    ref = M.runMPC(P.make_synth_rom(lookup="quintic"), soc0, tc, warmup + steps)
+    for k in ("u", "v", "soc", "phise", "nexec"):
+        a = np.load(tmp_path / "out" / f"{k}.npy")
+        assert a.dtype == np.float64 and a.shape == (n,)
+        np.testing.assert_array_equal(a, ref[k][-1].astype(np.float64), err_msg=k)

@@ -165,6 +165,15 @@ def test_count_gpus_from_kfd_topology(tmp_path):
     assert bench.count_gpus(str(tmp_path / "none"), str(dev), env={}) == 0
 
 
+def test_bench_full_and_dump_options_parse(tmp_path):
+    """--full and --dump-outputs are accepted (here with --dry-run, which computes no
+    outputs and so writes none); --steps sets the timed steps the line reports."""
+    line, err = _bench("--gpus", "1", "--dry-run", "--full", "--steps", "3", "--warmup", "1",
+                       "--dump-outputs", str(tmp_path / "out"))
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0
+    assert not (tmp_path / "out").exists()
+
+
 def test_bench_refuses_world_size_mismatch():
     import subprocess
     e = dict(os.environ, RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")

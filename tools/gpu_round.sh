@@ -48,7 +48,7 @@ do_trace() {
 do_pmc() {
   bash tools/profile.sh $TAG && \
   bash tools/cell_pmc.sh $TAG && \
-  timeout -k 10 300 python bench.py --pmc gpurun_out/prof_$TAG/pmc_traffic.json > $O/bench_pmc.json 2> $O/bench_pmc.err
+  timeout -k 10 300 python bench.py --full --pmc $(dirname $O)/prof_$TAG/pmc_traffic.json > $O/bench_pmc.json 2> $O/bench_pmc.err
 }
 do_dropin() {
   for rt in capi capi-async c c-async c-reuse c-async-reuse; do
