@@ -7,6 +7,7 @@
  * replaces one of them, batched over independent cells:
  *
  *   mpcekf_plant_step   <- [Vcell,obs,cellState] = OB_step(Iapp,Tc,cellState,ROM)  OB_step.m:1
+ *   mpcekf_plant_step_obs  the same with every field of obs (OB_step.m:226-228,289-356)
  *   mpcekf_ekf_step     <- [zk,boundzk,ekfData,Xind] = iterEKF(vk,ik,Tk,ekfData)    iterEKF.m:30
  *   mpcekf_linearize    <- [MPC,xhat] = EKFmatsHandler(ekfData,Xind,zk,Tk)         EKFmatsHandler.m:1
  *   mpcekf_predmat      <- [Phi,G,aug] = predMat(A,B,C,D,Np,Nc)                    predMat.m:1
@@ -41,7 +42,7 @@
 extern "C" {
 #endif
 
-#define MPCEKF_ABI_VERSION 4
+#define MPCEKF_ABI_VERSION 5
 
 /* return codes */
 #define MPCEKF_OK 0
@@ -63,6 +64,23 @@ enum {
   MPCEKF_TF_negThetass, MPCEKF_TF_posThetass, MPCEKF_TF_negPhie, MPCEKF_TF_sepPhie,
   MPCEKF_TF_posPhie, MPCEKF_TF_negThetae, MPCEKF_TF_sepThetae, MPCEKF_TF_posThetae,
   MPCEKF_TF_COUNT
+};
+
+/* The fields of OB_step's obs struct (OB_step.m:226-228, 289-356), in the order of one
+ * observable record (mpcekf_obs_layout).  A vector field is as long as tfData.names says
+ * (possibly 0), its entries in ROM row order (MATLAB's find); Phie has numel(ind.Phie) + 1
+ * entries, -negPhise0 first (OB_step.m:320-322). */
+enum {
+  MPCEKF_OBS_negSOC = 0, MPCEKF_OBS_posSOC, MPCEKF_OBS_cellSOC,
+  MPCEKF_OBS_negIfdl, MPCEKF_OBS_posIfdl, MPCEKF_OBS_negIfdl0, MPCEKF_OBS_posIfdl3,
+  MPCEKF_OBS_negIf, MPCEKF_OBS_posIf, MPCEKF_OBS_negIf0, MPCEKF_OBS_posIf3,
+  MPCEKF_OBS_negIdl, MPCEKF_OBS_posIdl,
+  MPCEKF_OBS_negThetass, MPCEKF_OBS_posThetass, MPCEKF_OBS_negThetass0, MPCEKF_OBS_posThetass3,
+  MPCEKF_OBS_negPhise, MPCEKF_OBS_posPhise, MPCEKF_OBS_negPhise0,
+  MPCEKF_OBS_Phie, MPCEKF_OBS_Thetae,
+  MPCEKF_OBS_negPhis, MPCEKF_OBS_posPhis,
+  MPCEKF_OBS_Vcell,
+  MPCEKF_OBS_COUNT
 };
 
 /* One electrode's cellData.function.{neg,pos} handles in tabulated form.
@@ -244,6 +262,20 @@ int mpcekf_cl_eig(int32_t n, const double *a, double *re, double *im, double *sv
 /* OB_step: applies iapp[c] to the plant state at tc_degC[c], returns vcell[c] (may be NULL:
  * Vcell also stays on the device for the next mpcekf_ekf_step with vk = NULL). */
 int mpcekf_plant_step(mpcekf_ctx *ctx, const double *iapp, const double *tc_degC, double *vcell);
+/* Slot offsets of the observable record: field f (MPCEKF_OBS_*) occupies slots off[f] ..
+ * off[f + 1] - 1, off[MPCEKF_OBS_COUNT] = nobs, the record length. */
+int mpcekf_obs_layout(const mpcekf_ctx *ctx, int32_t off[MPCEKF_OBS_COUNT + 1]);
+/* OB_step with its obs output: mpcekf_plant_step's contract (the same Vcell and plant state,
+ * bit for bit) plus the observable record of this step, obs [nobs][ncells] (slot-major: each
+ * slot one contiguous per-cell vector).  obs may be NULL: the record stays on the device for
+ * mpcekf_plant_obs_slots.  A cell with MPCEKF_ST_ERROR has NaN in every slot.  The record's
+ * device memory is allocated by the first call. */
+int mpcekf_plant_step_obs(mpcekf_ctx *ctx, const double *iapp, const double *tc_degC, double *vcell, double *obs);
+/* Selected slots of the device-resident record of the last mpcekf_plant_step_obs: out
+ * [nslots][ncells] (8 bytes per cell and slot cross PCIe, not 8 nobs).  MPCEKF_E_STATE when
+ * there is no record since init / the last fused step / set_state; MPCEKF_E_ARG for a slot
+ * outside 0 .. nobs - 1. */
+int mpcekf_plant_obs_slots(mpcekf_ctx *ctx, const int32_t *slots, int32_t nslots, double *out);
 /* iterEKF: zk/boundzk [ncells][nz+2], xind_model [ncells][4] (model index t*nZ+z of
  * Xind.theT/theZ), xind_gamma [ncells][4].  Every output may be NULL: zk and Xind also stay
  * on the device for the next mpcekf_linearize (runMPC.m:91 -> :94 without a host round trip).
@@ -279,6 +311,9 @@ int mpcekf_mpc_step_ex(mpcekf_ctx *ctx, const double *lin, const double *soc_k1,
 int mpcekf_mpc_diag(mpcekf_ctx *ctx, const double *lin, const double *uk_1, double *poles, double *sv);
 /* the _async twins (see above) */
 int mpcekf_plant_step_async(mpcekf_ctx *ctx, const double *iapp, const double *tc_degC, double *vcell);
+int mpcekf_plant_step_obs_async(mpcekf_ctx *ctx, const double *iapp, const double *tc_degC, double *vcell,
+                                double *obs);
+int mpcekf_plant_obs_slots_async(mpcekf_ctx *ctx, const int32_t *slots, int32_t nslots, double *out);
 int mpcekf_ekf_step_async(mpcekf_ctx *ctx, const double *vk, const double *ik, const double *tk_degC, double *zk,
                           double *boundzk, int32_t *xind_model, double *xind_gamma);
 int mpcekf_linearize_async(mpcekf_ctx *ctx, const double *zk, const int32_t *xind_model, const double *xind_gamma,

@@ -14,6 +14,15 @@
  *   [u,v,soc,phise,nexec] = mpcekf_mex('step', h, nsteps, tc)          mpcekf_step
  *                       tc: [] or ncells x nsteps (degC); outputs ncells x nsteps
  *   v                 = mpcekf_mex('plant', h, iapp, tc)               mpcekf_plant_step   (OB_step.m:1)
+ *   [v,obs]           = mpcekf_mex('plantobs', h, iapp, tc)            mpcekf_plant_step_obs (OB_step.m:1)
+ *                       obs: struct with the fields of OB_step's obs (OB_step.m:226-228,289-356),
+ *                       each len x ncells (a field without rows in tfData.names is 0 x ncells);
+ *                       with one output the record only stays on the device for 'obsslots'
+ *   out               = mpcekf_mex('obsslots', h, idx)                 mpcekf_plant_obs_slots
+ *                       rows idx (1-based slots of the record, mpcekf_obs_layout) of the last
+ *                       'plantobs' record on the device, numel(idx) x ncells
+ *   off               = mpcekf_mex('obslayout', h)                     mpcekf_obs_layout
+ *                       1 x 26: field f of obs is slots off(f)+1 .. off(f+1); off(end) = nobs
  *   [zk,zbk,xm,xg]    = mpcekf_mex('ekf', h, vk, ik, tk)               mpcekf_ekf_step     (iterEKF.m:30)
  *   lin               = mpcekf_mex('linearize', h, zk, xm, xg, tk)     mpcekf_linearize    (EKFmatsHandler.m:1)
  *   [uk,nexec,J_uncon,J_final,norm_DU,viol] = mpcekf_mex('mpc', h, lin, soc_k1)
@@ -331,11 +340,25 @@ static void gateway(mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
     return;
   }
   static const char *const with_handle[] = {"destroy", "init", "step", "plant", "ekf", "linearize", "mpc",
-                                            "graph", "mpcdiag", "get_state", "set_state", "scalars", "linfields"};
+                                            "graph", "mpcdiag", "get_state", "set_state", "scalars", "linfields",
+                                            "plantobs", "obsslots", "obslayout"};
   int known = 0;
   for (size_t i = 0; i < sizeof with_handle / sizeof *with_handle; ++i) known = known || !strcmp(cmd, with_handle[i]);
   if (!known) mexErrMsgIdAndTxt("mpcekf:arg", "unknown command %s", cmd);
   if (nrhs < 2) mexErrMsgIdAndTxt("mpcekf:arg", "%s: missing handle", cmd);
+  /* the obs commands refuse what no context can make valid before they look at the handle,
+     and before any device work: the output count, and slot indices that are no 1-based integers */
+  if (!strcmp(cmd, "plantobs") && g_nlhs > 2) mexErrMsgIdAndTxt("mpcekf:arg", "plantobs: at most 2 outputs [Vcell, obs]");
+  if (!strcmp(cmd, "obsslots")) {
+    if (g_nlhs > 1) mexErrMsgIdAndTxt("mpcekf:arg", "obsslots: at most 1 output");
+    need(nrhs, 3, "'obsslots', h, idx");
+    const size_t k = mxGetNumberOfElements(prhs[2]);
+    if (k < 1) mexErrMsgIdAndTxt("mpcekf:arg", "obsslots: idx: expected at least 1 slot index");
+    const double *idx = dvec(prhs[2], k, "idx");
+    for (size_t j = 0; j < k; ++j)
+      if (!(idx[j] >= 1 && idx[j] <= 2147483647.0) || idx[j] != (double)(int32_t)idx[j])
+        mexErrMsgIdAndTxt("mpcekf:arg", "obsslots: idx(%zu) = %g is not a slot 1..nobs", j + 1, idx[j]);
+  }
   mpcekf_ctx *h = handle(prhs[1]);
   int64_t n = 0;
   int32_t NM = 0, nz = 0, ncon = 0;
@@ -363,6 +386,60 @@ static void gateway(mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
     plhs[0] = dmat(1, nc);
     chk(mpcekf_plant_step(h, dvec(prhs[2], nc, "iapp"), nrhs > 3 ? opt_vec(prhs[3], nc, "tc") : NULL,
                           mxGetDoubles(plhs[0])));
+  } else if (!strcmp(cmd, "plantobs")) {
+    need(nrhs, 3, "'plantobs', h, iapp[, tc]");
+    static const char *const obs_names[MPCEKF_OBS_COUNT] = {
+        "negSOC", "posSOC", "cellSOC", "negIfdl", "posIfdl", "negIfdl0", "posIfdl3", "negIf", "posIf",
+        "negIf0", "posIf3", "negIdl", "posIdl", "negThetass", "posThetass", "negThetass0", "posThetass3",
+        "negPhise", "posPhise", "negPhise0", "Phie", "Thetae", "negPhis", "posPhis", "Vcell"};
+    int32_t off[MPCEKF_OBS_COUNT + 1];
+    chk(mpcekf_obs_layout(h, off));
+    const double *iapp = dvec(prhs[2], nc, "iapp"), *tc = nrhs > 3 ? opt_vec(prhs[3], nc, "tc") : NULL;
+    const size_t nobs = (size_t)off[MPCEKF_OBS_COUNT];
+    plhs[0] = dmat(1, nc);
+    if (g_nlhs < 2) { /* v = plantobs(..): the record stays on the device for 'obsslots' */
+      chk(mpcekf_plant_step_obs(h, iapp, tc, mxGetDoubles(plhs[0]), NULL));
+      return;
+    }
+    /* the record is slot-major [nobs][ncells]; a field is len x ncells column-major */
+    double *rec = (double *)mxMalloc(nobs * nc * sizeof(double) + 8);
+    chk(mpcekf_plant_step_obs(h, iapp, tc, mxGetDoubles(plhs[0]), rec));
+    plhs[1] = mxCreateStructMatrix(1, 1, MPCEKF_OBS_COUNT, (const char **)obs_names);
+    for (int f = 0; f < MPCEKF_OBS_COUNT; ++f) {
+      const size_t len = (size_t)(off[f + 1] - off[f]);
+      mxArray *a = dmat(len, nc);
+      double *d = mxGetDoubles(a);
+      for (size_t i = 0; i < len; ++i)
+        for (size_t c = 0; c < nc; ++c) d[i + len * c] = rec[((size_t)off[f] + i) * nc + c];
+      mxSetField(plhs[1], 0, obs_names[f], a);
+    }
+    mxFree(rec);
+  } else if (!strcmp(cmd, "obslayout")) {
+    /* off = mpcekf_mex('obslayout', h): 1 x 26 doubles, field f (the order of 'plantobs') is
+       slots off(f)+1 .. off(f+1) of the record, off(end) = nobs */
+    int32_t off[MPCEKF_OBS_COUNT + 1];
+    chk(mpcekf_obs_layout(h, off));
+    plhs[0] = dmat(1, MPCEKF_OBS_COUNT + 1);
+    for (int f = 0; f <= MPCEKF_OBS_COUNT; ++f) mxGetDoubles(plhs[0])[f] = (double)off[f];
+  } else if (!strcmp(cmd, "obsslots")) {
+    int32_t off[MPCEKF_OBS_COUNT + 1];
+    chk(mpcekf_obs_layout(h, off));
+    const size_t k = mxGetNumberOfElements(prhs[2]);
+    const double *idx = mxGetDoubles(prhs[2]); /* class, count and >= 1 checked above */
+    int32_t *slots = (int32_t *)mxMalloc(k * sizeof(int32_t));
+    for (size_t j = 0; j < k; ++j) {
+      if (idx[j] > (double)off[MPCEKF_OBS_COUNT])
+        mexErrMsgIdAndTxt("mpcekf:arg", "obsslots: idx(%zu) = %g is not a slot 1..%d", j + 1, idx[j],
+                          (int)off[MPCEKF_OBS_COUNT]);
+      slots[j] = (int32_t)idx[j] - 1;
+    }
+    double *rows = (double *)mxMalloc(k * nc * sizeof(double) + 8); /* [k][ncells] */
+    chk(mpcekf_plant_obs_slots(h, slots, (int32_t)k, rows));
+    plhs[0] = dmat(k, nc);
+    for (size_t j = 0; j < k; ++j)
+      for (size_t c = 0; c < nc; ++c) mxGetDoubles(plhs[0])[j + k * c] = rows[j * nc + c];
+    mxFree(rows);
+    mxFree(slots);
   } else if (!strcmp(cmd, "ekf")) {
     need(nrhs, 4, "'ekf', h, vk, ik[, tk]");
     /* [zk, zbk, xm, xg]: Xind crosses back only when asked for (nargout > 2); it stays on

@@ -22,6 +22,7 @@ NSCAL = 8
 MB_SIZE = 42
 METHOD_OB, METHOD_MB = 0, 1
 S_SOCNAVG, S_SOCPAVG, S_X0, S_SIGMAX0, S_PRIORI, S_UK_1, S_UK, S_VK = range(8)
+OBS_COUNT = 25   # MPCEKF_OBS_COUNT: the fields of OB_step's obs (rom.py OBS_FIELDS)
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
@@ -81,13 +82,15 @@ EXPORTS = [
     "mpcekf_build_id", "mpcekf_cl_eig", "mpcekf_mpc_diag", "mpcekf_set_graph",
     "mpcekf_dev_alloc", "mpcekf_dev_free", "mpcekf_dev_copy", "mpcekf_dev_copy2d", "mpcekf_sync",
     "mpcekf_get_scalars", "mpcekf_lin_fields",
+    "mpcekf_obs_layout", "mpcekf_plant_step_obs", "mpcekf_plant_obs_slots",
     # the _async stage twins (include/mpcekf.h)
     "mpcekf_plant_step_async", "mpcekf_ekf_step_async", "mpcekf_linearize_async", "mpcekf_lin_fields_async",
     "mpcekf_mpc_step_async", "mpcekf_mpc_step_ex_async", "mpcekf_mpc_diag_async", "mpcekf_get_scalars_async",
+    "mpcekf_plant_step_obs_async", "mpcekf_plant_obs_slots_async",
 ]
 
 COPY_H2D, COPY_D2H, COPY_D2D = 0, 1, 2
-ABI_VERSION = 4   # include/mpcekf.h MPCEKF_ABI_VERSION
+ABI_VERSION = 5   # include/mpcekf.h MPCEKF_ABI_VERSION
 
 _lib = None
 
@@ -142,8 +145,11 @@ def load():
     L.mpcekf_sync.argtypes = [vp]
     L.mpcekf_get_scalars.argtypes = [vp, _ip, C.c_int32, _dp, _ip, _ip]
     L.mpcekf_lin_fields.argtypes = [vp, _ip, C.c_int32, _dp, _dp]
+    L.mpcekf_obs_layout.argtypes = [vp, _ip]
+    L.mpcekf_plant_step_obs.argtypes = [vp, _dp, _dp, _dp, _dp]
+    L.mpcekf_plant_obs_slots.argtypes = [vp, _ip, C.c_int32, _dp]
     for nm in ("plant_step", "ekf_step", "linearize", "lin_fields", "mpc_step", "mpc_step_ex", "mpc_diag",
-               "get_scalars"):   # the _async twins take the synchronous call's arguments
+               "get_scalars", "plant_step_obs", "plant_obs_slots"):   # the _async twins take the synchronous call's arguments
         getattr(L, f"mpcekf_{nm}_async").argtypes = getattr(L, f"mpcekf_{nm}").argtypes
     for nm in EXPORTS:
         if nm not in ("mpcekf_abi_version", "mpcekf_last_error", "mpcekf_config_defaults", "mpcekf_build_id"):

@@ -308,6 +308,24 @@ struct mpcekf_ctx {
   double *d_szk = nullptr, *d_sxg = nullptr, *d_slin = nullptr, *d_sv = nullptr;
   int *d_sxm = nullptr, *d_zslot = nullptr;  // d_zslot: zk(end)'s slot, nz + 1 (mpc_step's NULL soc_k1)
   bool stage_zk = false, stage_lin = false, stage_v = false;
+  // mpcekf_plant_step_obs (OB_step's obs output): the layout and the obs blob are made by
+  // build_rom on the host; the blob's device copy and the record [nobs][n] are allocated by
+  // the first obs call (a context that never asks for obs holds neither)
+  int32_t obs_off[MPCEKF_OBS_COUNT + 1] = {};
+  std::vector<double> h_obs_blob;
+  KObs ko{};
+  double *d_obs_blob = nullptr, *d_obs = nullptr;
+  bool stage_obs = false;  // d_obs holds the record of an obs call since init / fused step / set_state
+  int obs_bufs() {
+    if (!d_obs_blob) {
+      HIPCHK(hipMalloc((void **)&d_obs_blob, h_obs_blob.size() * sizeof(double)));
+      HIPCHK(hipMemcpy(d_obs_blob, h_obs_blob.data(), h_obs_blob.size() * sizeof(double), hipMemcpyHostToDevice));
+      ko.blob = d_obs_blob;
+    }
+    if (!d_obs) HIPCHK(hipMalloc((void **)&d_obs, (size_t)ko.nobs * (size_t)n * sizeof(double)));
+    ko.rec = d_obs;
+    return MPCEKF_OK;
+  }
   int stage_bufs() {
     const size_t nzz = (size_t)nz + 2;
     if (!d_sv) HIPCHK(hipMalloc((void **)&d_sv, (size_t)n * sizeof(double)));
@@ -768,6 +786,69 @@ static int build_rom(mpcekf_ctx *X, const mpcekf_rom *R) {
   if (lds_need() > 160 * 1024) r.rom_global = 1;
   if (lds_need() > 160 * 1024)
     return fail(MPCEKF_E_UNSUPPORTED, "rom: %d bytes of electrode tables exceed the 160 KiB LDS", lds_need());
+  // --- OB_step's obs output (mpcekf_plant_step_obs): record layout, row descriptors and a
+  // blob of its own with every row's C, res0 and D (the plant and cell blobs stay as they
+  // are); host memory only, uploaded by the first obs call ---
+  {
+    int32_t *off = X->obs_off;
+    static const int vec_field[MPCEKF_TF_COUNT] = {
+        MPCEKF_OBS_negIfdl, MPCEKF_OBS_posIfdl, MPCEKF_OBS_negIf, MPCEKF_OBS_posIf, MPCEKF_OBS_negIdl,
+        MPCEKF_OBS_posIdl, MPCEKF_OBS_negPhis, MPCEKF_OBS_posPhis, MPCEKF_OBS_negPhise, MPCEKF_OBS_posPhise,
+        MPCEKF_OBS_negThetass, MPCEKF_OBS_posThetass, MPCEKF_OBS_Phie, MPCEKF_OBS_Phie, MPCEKF_OBS_Phie,
+        MPCEKF_OBS_Thetae, MPCEKF_OBS_Thetae, MPCEKF_OBS_Thetae};
+    static const int row_kind[MPCEKF_TF_COUNT] = {
+        OBS_PLAIN, OBS_PLAIN, OBS_PLAIN, OBS_PLAIN, OBS_PLAIN, OBS_PLAIN, OBS_PLAIN, OBS_PPHIS, OBS_NPHISE,
+        OBS_PPHISE, OBS_NTHSS, OBS_PTHSS, OBS_PHIE, OBS_PHIE, OBS_PHIE, OBS_THETAE, OBS_THETAE, OBS_THETAE};
+    int len[MPCEKF_OBS_COUNT];
+    for (int f = 0; f < MPCEKF_OBS_COUNT; ++f) len[f] = 1;  // the scalars; the vector fields follow
+    for (int code = 0; code <= MPCEKF_TF_posThetass; ++code) len[vec_field[code]] = (int)rows_of(code).size();
+    len[MPCEKF_OBS_Phie] = (int)Phie.size() + 1;  // OB_step.m:320
+    len[MPCEKF_OBS_Thetae] = (int)Thetae.size();
+    off[0] = 0;
+    for (int f = 0; f < MPCEKF_OBS_COUNT; ++f) off[f + 1] = off[f] + len[f];
+    KObs &ko = X->ko;
+    ko = KObs{};
+    ko.nobs = off[MPCEKF_OBS_COUNT];
+    ko.slot_phie0 = off[MPCEKF_OBS_Phie];
+    std::vector<int> slot1(nz, -1), slot2(nz, -1);
+    for (int code = 0; code <= MPCEKF_TF_posThetass; ++code) {
+      const std::vector<int> v = rows_of(code);
+      for (size_t i = 0; i < v.size(); ++i) slot1[v[i]] = off[vec_field[code]] + (int)i;
+    }
+    for (size_t i = 0; i < Phie.size(); ++i) slot1[Phie[i]] = off[MPCEKF_OBS_Phie] + 1 + (int)i;
+    for (size_t i = 0; i < Thetae.size(); ++i) slot1[Thetae[i]] = off[MPCEKF_OBS_Thetae] + (int)i;
+    slot2[role[R_IFDL0]] = off[MPCEKF_OBS_negIfdl0];
+    slot2[role[R_IFDL3]] = off[MPCEKF_OBS_posIfdl3];
+    slot2[role[R_IF0]] = off[MPCEKF_OBS_negIf0];
+    slot2[role[R_IF3]] = off[MPCEKF_OBS_posIf3];
+    slot2[role[R_TH0]] = off[MPCEKF_OBS_negThetass0];
+    slot2[role[R_TH3]] = off[MPCEKF_OBS_posThetass3];
+    slot2[role[R_PHISE0]] = off[MPCEKF_OBS_negPhise0];
+    if (nz > OBS_MAXROWS || ko.nobs > 1023) return fail(MPCEKF_E_UNSUPPORTED, "rom: nz = %d rows exceed the obs record", nz);
+    for (int p = 0; p < nz; ++p) {
+      const int q = perm[p];
+      ko.desc[p] = (unsigned)row_kind[R->tf_code[q]] | (unsigned)(slot1[q] + 1) << 4 | (unsigned)(slot2[q] + 1) << 14;
+    }
+    ko.stride = nz * OBS_ROW;
+    std::vector<double> &ob = X->h_obs_blob;
+    ob.assign((size_t)NM * ko.stride, 0.0);
+    for (int m = 0; m < NM; ++m)
+      for (int p = 0; p < nz; ++p) {
+        double *b = ob.data() + (size_t)m * ko.stride + (size_t)p * OBS_ROW;
+        const int q = perm[p], code = R->tf_code[q];
+        for (int k = 0; k < NX; ++k) b[k] = Cval(m, q, k);
+        // OB_step.m:178-181: res0 removed from the Phise rows
+        b[NX] = (code == MPCEKF_TF_negPhise || code == MPCEKF_TF_posPhise) ? 0.0 : Cval(m, q, NX);
+        b[NX + 1] = Dval(m, q);
+      }
+    ko.tab = (int)ob.size();  // NM * nz * 8: even
+    ko.tablen = (int)tabs.size();
+    ob.insert(ob.end(), tabs.begin(), tabs.end());
+    ob.insert(ob.end(), pts.begin(), pts.end());
+    ko.len = (int)ob.size();
+    ko.global = r.rom_global;
+    if (obs_lds_bytes(ko) > 160 * 1024) ko.global = 1;  // the tables alone fit: lds_need above
+  }
   int rc;
   if (poly) {
     if ((rc = dalloc(&X->d_poly, ptab.size()))) return rc;
@@ -962,7 +1043,8 @@ int mpcekf_ctx_destroy(mpcekf_ctx *X) {
   void *ptrs[] = {X->d_prob, X->d_cell_blob, X->d_plant_blob, X->d_bulk, X->d_const, X->d_scal, X->d_int, X->d_zk,
                   X->d_zbk,       X->d_tmp,        X->s.bigx, X->s.ekf,   X->s.lam,   X->d_ts, X->d_hist, X->d_stamps, X->d_bnd, X->d_xm, X->d_xg,
                   X->w.prob, X->w.X, X->w.R, X->w.K, X->w.hii, X->w.it, X->w.smin, X->d_lin, X->d_zsoc, X->d_mb, X->d_uk1p,
-                  X->w.q, X->w.list, X->w.hist, X->d_poly, X->d_szk, X->d_sxg, X->d_sxm, X->d_slin, X->d_sv, X->d_zslot};
+                  X->w.q, X->w.list, X->w.hist, X->d_poly, X->d_szk, X->d_sxg, X->d_sxm, X->d_slin, X->d_sv, X->d_zslot,
+                  X->d_obs_blob, X->d_obs};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   for (auto &g : X->graphs) (void)hipGraphExecDestroy(g.exec);
@@ -1015,7 +1097,7 @@ static int set_tc(mpcekf_ctx *X, const double *tc, struct Xfer *xf = nullptr);
 
 // initKF.m:30-136, initMPC.m:29-74 and OB_step.m:39-72 for every cell.
 int mpcekf_init_cells(mpcekf_ctx *X, const double *soc0_pct, const double *tc_degC) {
-  if (X) X->stage_zk = X->stage_lin = X->stage_v = false;  // the stage route's device hand-offs are stale
+  if (X) X->stage_zk = X->stage_lin = X->stage_v = X->stage_obs = false;  // the stage route's device hand-offs are stale
   if (!X || ((!soc0_pct || !tc_degC) && X->n)) return fail(MPCEKF_E_ARG, "init_cells: null argument");
   HIPCHK(hipSetDevice(X->device));
   const size_t n = (size_t)X->n;
@@ -1069,7 +1151,7 @@ static int lerr(int rc, const char *what) {
 // update) -> iterEKF measurement update -> EKFmatsHandler -> iterMPC.
 int mpcekf_step_ex(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const mpcekf_traj *tr,
                    int32_t outputs_on_device) {
-  if (X) X->stage_zk = X->stage_lin = X->stage_v = false;  // the stage route's device hand-offs are stale
+  if (X) X->stage_zk = X->stage_lin = X->stage_v = X->stage_obs = false;  // the stage route's device hand-offs are stale
   int rc = need_init(X);
   if (rc) return rc;
   if (nsteps < 0) return fail(MPCEKF_E_ARG, "nsteps < 0");
@@ -1536,6 +1618,68 @@ int mpcekf_plant_step_async(mpcekf_ctx *X, const double *iapp, const double *tc_
   return plant_step_impl(X, iapp, tc_degC, vcell, true);
 }
 
+int mpcekf_obs_layout(const mpcekf_ctx *X, int32_t off[MPCEKF_OBS_COUNT + 1]) {
+  if (!X || !off) return fail(MPCEKF_E_ARG, "obs_layout: null argument");
+  std::memcpy(off, X->obs_off, sizeof X->obs_off);
+  return MPCEKF_OK;
+}
+
+// mpcekf_plant_step with k_plant_obs in front: it reads the state of step t-1 that k_plant4
+// is about to overwrite (SOCn / SOCp) and k_bulk to advance (bigx), on the same stream
+static int plant_step_obs_impl(mpcekf_ctx *X, const double *iapp, const double *tc_degC, double *vcell, double *obs,
+                               bool async) {
+  int rc = need_init(X);
+  if (rc) return rc;
+  if (!iapp) return fail(MPCEKF_E_ARG, "plant_step_obs: null argument");
+  const size_t n = (size_t)X->n, ob = (size_t)X->ko.nobs * n * 8;
+  Xfer xf{X};
+  if ((rc = xf.reserve({n * 8, n * 8, n * 8, obs ? ob : 0}))) return rc;
+  if ((rc = set_tc(X, tc_degC, &xf))) return rc;
+  if ((rc = X->tmp(2 * n * 8 + 512)) || (rc = X->stage_bufs()) || (rc = X->obs_bufs())) return rc;
+  Slab sl{(char *)X->d_tmp};
+  double *di = sl.take<double>(n), *dv = X->d_sv;
+  X->stage_v = X->stage_obs = false;
+  HIPCHK(xf.in(di, iapp, n * 8));
+  if ((rc = lerr(launch_plant_obs(X->r, X->s, X->ko, di, X->stream), "plant_obs"))) return rc;
+  if ((rc = lerr(launch_plant(X->r, X->s, di, dv, 0, nullptr, X->stream), "plant"))) return rc;
+  if ((rc = lerr(launch_bulk(X->r, X->k, X->s, di, 1, 0, X->stream), "bulk"))) return rc;
+  if (vcell) HIPCHK(xf.out(vcell, dv, n * 8));
+  if (obs) HIPCHK(xf.out(obs, X->d_obs, ob));
+  if ((rc = xf.end(async))) return rc;
+  X->stage_v = X->stage_obs = true;
+  return MPCEKF_OK;
+}
+int mpcekf_plant_step_obs(mpcekf_ctx *X, const double *iapp, const double *tc_degC, double *vcell, double *obs) {
+  return plant_step_obs_impl(X, iapp, tc_degC, vcell, obs, false);
+}
+int mpcekf_plant_step_obs_async(mpcekf_ctx *X, const double *iapp, const double *tc_degC, double *vcell,
+                                double *obs) {
+  return plant_step_obs_impl(X, iapp, tc_degC, vcell, obs, true);
+}
+
+// the record is slot-major, so a slot is one contiguous [ncells] vector: a copy each, no kernel
+static int plant_obs_slots_impl(mpcekf_ctx *X, const int32_t *slots, int32_t nslots, double *out, bool async) {
+  int rc = need_init(X);
+  if (rc) return rc;
+  if (!X->stage_obs) return fail(MPCEKF_E_STATE, "plant_obs_slots: no mpcekf_plant_step_obs record on the device");
+  if (nslots < 0 || (nslots && (!slots || !out))) return fail(MPCEKF_E_ARG, "plant_obs_slots: null argument");
+  for (int i = 0; i < nslots; ++i)
+    if (slots[i] < 0 || slots[i] >= X->ko.nobs)
+      return fail(MPCEKF_E_ARG, "plant_obs_slots: slot %d outside 0..%d", slots[i], X->ko.nobs - 1);
+  if (!nslots) return MPCEKF_OK;
+  const size_t n = (size_t)X->n;
+  Xfer xf{X};
+  if ((rc = xf.reserve(std::vector<size_t>((size_t)nslots, n * 8)))) return rc;
+  for (int i = 0; i < nslots; ++i) HIPCHK(xf.out(out + (size_t)i * n, X->d_obs + (size_t)slots[i] * n, n * 8));
+  return xf.end(async);
+}
+int mpcekf_plant_obs_slots(mpcekf_ctx *X, const int32_t *slots, int32_t nslots, double *out) {
+  return plant_obs_slots_impl(X, slots, nslots, out, false);
+}
+int mpcekf_plant_obs_slots_async(mpcekf_ctx *X, const int32_t *slots, int32_t nslots, double *out) {
+  return plant_obs_slots_impl(X, slots, nslots, out, true);
+}
+
 static int ekf_step_impl(mpcekf_ctx *X, const double *vk, const double *ik, const double *tk_degC, double *zk,
                     double *boundzk, int32_t *xind_model, double *xind_gamma, bool async) {
   int rc = need_init(X);
@@ -1997,7 +2141,7 @@ int mpcekf_get_scalars_async(mpcekf_ctx *X, const int32_t *slots, int32_t nslots
 }
 
 int mpcekf_set_state(mpcekf_ctx *X, const mpcekf_state *st) {
-  if (X) X->stage_zk = X->stage_lin = X->stage_v = false;  // the stage route's device hand-offs are stale
+  if (X) X->stage_zk = X->stage_lin = X->stage_v = X->stage_obs = false;  // the stage route's device hand-offs are stale
   int rc = need_init(X);
   if (rc) return rc;
   if (!st) return fail(MPCEKF_E_ARG, "set_state: null");

@@ -1888,6 +1888,136 @@ __global__ void __launch_bounds__(PLANT4_BLOCK) k_plant4(const KRom r, const KSt
 }
 
 // ---------------------------------------------------------------------------
+// k_plant_obs: every observable of OB_step.m:226-228,289-356 for the stage route
+// (mpcekf_plant_step_obs), a lane quad per cell as k_plant4.  It is launched BEFORE the
+// call's k_plant4 / k_bulk and only reads the plant state (SOCn/SOCp, bigx at step t-1), so
+// Vcell and the state the call leaves are k_plant4's own; this kernel recomputes Vcell with
+// k_plant4's expressions (the same bits) for posPhis and the record's Vcell slot.
+// The obs blob (host build_rom) holds, per model, all nz rows in the permuted order as
+// [C 5][res0][D][0] -- res0 zeroed on the Phise rows, OB_step.m:178-181 -- then the plant
+// blob's tables.  Pass 1 forms role rows 0..R_PHISE0 (unrolled, registers) for Vcell and
+// negPhise0; pass 2 walks every row once more: blend, the row's correction (OBS_* kind) and
+// its one or two record slots, all from the row's uniform descriptor word.  The record is
+// slot-major [nobs][n]; lane j of the quad stores the slots = j (mod 4).
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ double obs_row(const double *B, const double xs[6], double Iapp) {
+  const double2 *p = reinterpret_cast<const double2 *>(B);
+  const double2 c01 = p[0], c23 = p[1], c4r = p[2], d = p[3];
+  double acc = 0.0;
+  acc = acc + c01.x * xs[0];
+  acc = acc + c01.y * xs[1];
+  acc = acc + c23.x * xs[2];
+  acc = acc + c23.y * xs[3];
+  acc = acc + c4r.x * xs[4];
+  acc = acc + c4r.y * xs[5];
+  return acc + d.x * Iapp;
+}
+__device__ __forceinline__ double quad_blend(double y, double aZ, double aT) {  // OB_step.m:285
+  const double y0 = qbc<0>(y), y1 = qbc<1>(y), y2 = qbc<2>(y), y3 = qbc<3>(y);
+  return (1 - aT) * ((1 - aZ) * y0 + aZ * y1) + aT * ((1 - aZ) * y2 + aZ * y3);
+}
+constexpr int OBS_BLOCK = 512;  // 256 VGPRs a lane: no scratch (at 1024 / 128 the quintic lookups spilled)
+template <bool GR, bool PL>
+__global__ void __launch_bounds__(OBS_BLOCK) k_plant_obs(const KRom r, const KState s, const KObs o,
+                                                            const double *iapp) {
+  extern __shared__ double lds[];
+  const int64_t gt = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int j = (int)(gt & 3);
+  const int64_t c = gt >> 2;  // a quad is one cell: every exit below is quad-uniform
+  const int lo = GR ? o.tab : 0;
+  stage_lds(lds, o.blob + lo, o.len - lo);
+  __syncthreads();
+  const double *tb = lds - lo;
+  const double *L = GR ? o.blob : lds;
+  const double *Tp = tb + o.tab + o.tablen;
+  const double *Zp = Tp + MAXT;
+  if (c >= s.n) return;
+  const size_t n = (size_t)s.n;
+  double *rec = o.rec + c;
+  auto put = [&](int slot, double v) {
+    if ((slot & 3) == j) rec[(size_t)slot * n] = v;
+  };
+  if (s.status[c] & ST_ERROR) {
+    for (int k = j; k < o.nobs; k += 4) rec[(size_t)k * n] = __builtin_nan("");
+    return;
+  }
+  const double Iapp = iapp[c];
+  const double T = s.Tc[c] + 273.15;  // OB_step.m:75
+  const double negSOC = s.SOCn[c], posSOC = s.SOCp[c];  // OB_step.m:226-227
+  const double SOC0n = s.SOC0n[c], SOC0p = s.SOC0p[c];
+  const ETab et = etab<PL>(r, tb + o.tab, T);
+  const double cellSOC = (negSOC - r.th0n) / (r.th100n - r.th0n);  // OB_step.m:228
+  int iZu = 0, iZl = 0, iTu = 0, iTl = 0;
+  if (r.nZ > 1) {
+    int a, b;
+    two_nearest(Zp, r.nZ, cellSOC, a, b);
+    iZu = a > b ? a : b; iZl = a < b ? a : b;
+  }
+  if (r.nT > 1) {
+    int a, b;
+    two_nearest(Tp, r.nT, T, a, b);
+    iTu = a > b ? a : b; iTl = a < b ? a : b;
+  }
+  const int mj = ((j & 2) ? iTu : iTl) * r.nZ + ((j & 1) ? iZu : iZl);
+  double xs[6];
+  {
+    const double2 *p = reinterpret_cast<const double2 *>(s.bigx + ((size_t)c * r.NM + mj) * 6);
+    const double2 q0 = p[0], q1 = p[1], q2 = p[2];
+    xs[0] = q0.x; xs[1] = q0.y; xs[2] = q1.x; xs[3] = q1.y; xs[4] = q2.x; xs[5] = q2.y;
+  }
+  const double Zu = Zp[iZu], Zl = Zp[iZl], Tu = Tp[iTu], Tl = Tp[iTl];
+  double aZ = 0.0, aT = 0.0;
+  if (Zu != Zl) aZ = (cellSOC - Zl) / (Zu - Zl);
+  if (Tu != Tl) aT = (T - Tl) / (Tu - Tl);
+  const double *B = L + (size_t)mj * o.stride;
+  double yk[R_PHISE0 + 1];
+#pragma unroll
+  for (int q = 0; q <= R_PHISE0; ++q) {
+    yk[q] = quad_blend(obs_row(B + q * OBS_ROW, xs, Iapp), aZ, aT);
+    __builtin_amdgcn_sched_barrier(0);  // one row's operands at a time (k_plant4)
+  }
+  const double th0 = fmin(fmax(yk[R_TH0] + SOC0n, 1e-6), 1 - 1e-6);
+  const double th3 = fmin(fmax(yk[R_TH3] + SOC0p, 1e-6), 1 - 1e-6);
+  const double te1 = fmax(yk[R_TE1] + 1, 1e-6);
+  const double teE = fmax(yk[R_TEE] + 1, 1e-6);
+  double i0n = et.f(0, EF_K0, negSOC) * sqrt(te1 * (1 - th0) * th0);  // OB_step.m:329-332
+  double i0p = et.f(1, EF_K0, posSOC) * sqrt(teE * (1 - th3) * th3);
+  double negEta0 = 2 * r.R * T / r.F * dasinh(yk[R_IF0] / (2 * i0n));
+  double posEta3 = 2 * r.R * T / r.F * dasinh(yk[R_IF3] / (2 * i0p));
+  double Uocpn0 = et.f(0, EF_U, th0), Uocpp3 = et.f(1, EF_U, th3);
+  const double Rfn = et.f(0, EF_RF, negSOC), Rfp = et.f(1, EF_RF, posSOC);  // OB_step.m:339-340
+  double V = posEta3 - negEta0 + yk[R_PHIE] + Uocpp3 - Uocpn0 + (Rfp * yk[R_IFDL3] - Rfn * yk[R_IFDL0]);
+  V = V - r.Rc * Iapp;
+  __builtin_amdgcn_sched_barrier(0);  // Vcell's lookups done before the two of the averages start
+  const double UocpnAvg = et.f(0, EF_U, negSOC), UocppAvg = et.f(1, EF_U, posSOC);  // OB_step.m:313-314
+  const double negPhise0 = yk[R_PHISE0] + UocpnAvg;                                 // OB_step.m:317
+  __builtin_amdgcn_sched_barrier(0);
+  put(OBS_S_NEGSOC, negSOC);
+  put(OBS_S_POSSOC, posSOC);
+  put(OBS_S_CELLSOC, cellSOC);
+  put(o.slot_phie0, -negPhise0);  // OB_step.m:321
+  put(o.nobs - 1, V);             // OB_step.m:356
+  for (int q = 0; q < r.nz; ++q) {
+    const unsigned d = o.desc[q];
+    const int kind = (int)(d & 15u), s1 = (int)(d >> 4 & 1023u) - 1, s2 = (int)(d >> 14 & 1023u) - 1;
+    if (s1 < 0 && s2 < 0) continue;  // a Phie row at x = 0 (OB_step.m:151-155): in no field
+    double v = quad_blend(obs_row(B + q * OBS_ROW, xs, Iapp), aZ, aT);
+    switch (kind) {
+      case OBS_NTHSS: v = fmin(fmax(v + SOC0n, 1e-6), 1 - 1e-6); break;  // OB_step.m:302-310
+      case OBS_PTHSS: v = fmin(fmax(v + SOC0p, 1e-6), 1 - 1e-6); break;
+      case OBS_NPHISE: v = v + UocpnAvg; break;                          // OB_step.m:315-317
+      case OBS_PPHISE: v = v + UocppAvg; break;
+      case OBS_PHIE: v = v - negPhise0; break;                           // OB_step.m:322
+      case OBS_THETAE: v = fmax(v + 1, 1e-6); break;                     // OB_step.m:325-326
+      case OBS_PPHIS: v = v + V; break;                                  // OB_step.m:348
+      default: break;
+    }
+    if (s1 >= 0) put(s1, v);
+    if (s2 >= 0) put(s2, v);
+  }
+}
+
+// ---------------------------------------------------------------------------
 // k_bulk: all-model plant advance and EKF time update (HBM streaming)
 // ---------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_bulk(const KRom r, const KCfg cf, const KState s, const double *iapp,
@@ -4251,6 +4381,28 @@ int launch_plant(const KRom &r, const KState &s, const double *iapp, double *vou
   } else {
     if (r.rom_global) hipLaunchKernelGGL((k_plant<true, false>), g, b, lds, st, r, s, iapp, vout, lazy_t, tc_in);
     else hipLaunchKernelGGL((k_plant<false, false>), g, b, lds, st, r, s, iapp, vout, lazy_t, tc_in);
+  }
+  return (int)hipGetLastError();
+}
+
+int obs_lds_bytes(const KObs &o) { return (int)((o.len - (o.global ? o.tab : 0) + 1) * sizeof(double)); }
+
+int launch_plant_obs(const KRom &r, const KState &s, const KObs &o, const double *iapp, void *stream) {
+  if (s.n == 0) return 0;
+  const hipStream_t st = (hipStream_t)stream;
+  const int lds = obs_lds_bytes(o);
+  const int block = spread_block(s.n, 4, OBS_BLOCK);
+  const dim3 g(grid_for(4 * s.n, block)), b(block);
+  auto go = [&](auto kern) {  // all nz rows of every model: above the 64 KiB default from ~40 models
+    (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    hipLaunchKernelGGL(kern, g, b, lds, st, r, s, o, iapp);
+  };
+  if (r.npoly) {
+    if (o.global) go(k_plant_obs<true, true>);
+    else go(k_plant_obs<false, true>);
+  } else {
+    if (o.global) go(k_plant_obs<true, false>);
+    else go(k_plant_obs<false, false>);
   }
   return (int)hipGetLastError();
 }

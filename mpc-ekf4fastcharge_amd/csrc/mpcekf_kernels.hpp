@@ -107,6 +107,26 @@ struct KState {
   long long *stamps;         // [NSTAMPS][n] section clocks (-DMPCEKF_STAMPS builds only, else null)
 };
 
+// mpcekf_plant_step_obs: the obs blob, the record and where each permuted row goes.
+// Blob: per model nz rows of OBS_ROW doubles [C 5][res0][D][0] in the permuted row order
+// (res0 = 0 on the negPhise / posPhise rows, OB_step.m:178-181), then -- at `tab`, even --
+// the plant blob's electrode tables (tablen doubles) and Tpts [MAXT], Zpts [MAXZ].
+constexpr int OBS_ROW = 8;
+constexpr int OBS_MAXROWS = 32;  // nz <= nzp <= 32 (build_rom)
+// the correction a row's blended value takes before it is stored (OB_step.m:289-348)
+enum { OBS_PLAIN = 0, OBS_NTHSS, OBS_PTHSS, OBS_NPHISE, OBS_PPHISE, OBS_PHIE, OBS_THETAE, OBS_PPHIS };
+enum { OBS_S_NEGSOC = 0, OBS_S_POSSOC, OBS_S_CELLSOC };  // the record's first slots; Vcell is the last
+struct KObs {
+  const double *blob;
+  int stride, tab, tablen, len;  // doubles: per model, tables' offset / length, blob length
+  int global;                    // 1: only the tables staged in LDS, model rows read from the blob (L2)
+  int nobs, slot_phie0;          // record length; slot of Phie(1) = -negPhise0 (OB_step.m:321)
+  // per permuted row: kind | (slot + 1) << 4 of its vector field | (slot + 1) << 14 of its
+  // collector scalar (negIfdl0 .. negPhise0), 0 = none
+  unsigned desc[OBS_MAXROWS];
+  double *rec;                   // [nobs][n] slot-major
+};
+
 // Inputs/outputs of one cell-kernel launch.  Any pointer may be null.
 struct KIO {
   int mode;               // MODE_* bits
@@ -168,6 +188,10 @@ struct KWide {
 // tc_in (device, [n] degC, may be null): the step's temperature, stored into s.Tc first
 int launch_plant(const KRom &r, const KState &s, const double *iapp, double *vout, int lazy_t, const double *tc_in,
                  void *stream);
+// every OB_step observable of the pre-step state into o.rec (reads the plant state only: launch
+// it before the call's launch_plant / launch_bulk); the temperature is s.Tc
+int launch_plant_obs(const KRom &r, const KState &s, const KObs &o, const double *iapp, void *stream);
+int obs_lds_bytes(const KObs &o);
 // brings every model of every cell from its ts to step t, then sets ts = new_ts
 // every model of cells [c_lo, c_hi) (c_hi < 0: to the end) brought to step t, timestamps new_ts
 int launch_flush(const KRom &r, const KCfg &c, const KState &s, int t, int new_ts, void *stream, int64_t c_lo = 0,

@@ -23,7 +23,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import LIN_SIZE, MpcekfError, check, dptr, iptr
-from .rom import EL_TABLES, ROM, TF_CODE
+from .rom import EL_TABLES, OBS_FIELDS, ROM, TF_CODE
 
 __all__ = ["Context", "DeviceBuffer", "hip_runtimes", "tc_grid", "make_config", "predMat", "constraintsMPC", "hildreth", "runMPC", "MpcekfError",
            "LIN_SIZE"]
@@ -355,14 +355,67 @@ class Context:
     def _tvec(self, T):
         return None if T is None else self._vec(T)
 
-    def OB_step(self, Iapp, Tc=None):
-        """[Vcell, ~, cellState] = OB_step(Iapp, Tc, cellState, ROM)  (OB_step.m:1).
-        Tc (degC, scalar or [n]) becomes the cell temperature; None keeps the current one."""
+    def obs_layout(self):
+        """{field: slice} of the observable record as the library lays it out
+        (mpcekf_obs_layout); equals ROM.obs_layout()."""
+        off = np.zeros(_lib.OBS_COUNT + 1, dtype=np.int32)
+        check(self.L.mpcekf_obs_layout(self.h, iptr(off)))
+        return {k: slice(int(off[f]), int(off[f + 1])) for f, k in enumerate(OBS_FIELDS)}
+
+    _OBS_SCALARS = frozenset(("negSOC", "posSOC", "cellSOC", "negIfdl0", "posIfdl3", "negIf0", "posIf3",
+                              "negThetass0", "posThetass3", "negPhise0", "Vcell"))
+
+    def _obs_dict(self, rec, fields, slices):
+        # views of the slot-major record: scalar fields [n], vector fields [n, len]
+        return {k: rec[sl.start] if k in self._OBS_SCALARS else rec[sl].T for k, sl in zip(fields, slices)}
+
+    def OB_step(self, Iapp, Tc=None, obs=False):
+        """[Vcell, obs, cellState] = OB_step(Iapp, Tc, cellState, ROM)  (OB_step.m:1).
+        Tc (degC, scalar or [n]) becomes the cell temperature; None keeps the current one.
+
+        obs=False: Vcell [n].  obs=True: (Vcell, dict) with every field of the reference's obs
+        struct (OB_step.m:226-228, 289-356; rom.OBS_FIELDS): scalar fields [n], vector fields
+        [n, len] (len may be 0).  obs=("negPhise0", "Thetae"): only those fields cross PCIe
+        (the record stays on the device, mpcekf_plant_obs_slots).  Vcell and the plant state
+        are the same bits whichever way it is called."""
         i = self._vec(Iapp)
         t = self._tvec(Tc)
         v = np.empty(self.n)
-        self._stage("plant_step", dptr(i), dptr(t), dptr(v), keep=(v,))
-        return v
+        if obs is False or obs is None:
+            self._stage("plant_step", dptr(i), dptr(t), dptr(v), keep=(v,))
+            return v
+        lay = self.rom.obs_layout()
+        if obs is True:
+            rec = np.empty((lay["Vcell"].stop, self.n))
+            # the inputs stay alive until the synchronisation too (an input the library
+            # cannot bounce is read in place)
+            self._stage("plant_step_obs", dptr(i), dptr(t), dptr(v), dptr(rec), keep=(v, rec, i, t))
+            return v, self._obs_dict(rec, OBS_FIELDS, [lay[k] for k in OBS_FIELDS])
+        fields = (obs,) if isinstance(obs, str) else tuple(obs)
+        for k in fields:
+            if k not in lay:
+                raise KeyError(f"OB_step: unknown obs field {k!r} (one of {OBS_FIELDS})")
+        slots = np.ascontiguousarray(np.concatenate([np.arange(lay[k].start, lay[k].stop) for k in fields] or [[]]),
+                                     dtype=np.int32)
+        rec = np.empty((slots.size, self.n))
+        self._stage("plant_step_obs", dptr(i), dptr(t), dptr(v), None, keep=(v, i, t))
+        if slots.size:
+            self._stage("plant_obs_slots", iptr(slots), int(slots.size), dptr(rec), keep=(rec, slots))
+        pos, sl = 0, []
+        for k in fields:
+            m = lay[k].stop - lay[k].start
+            sl.append(slice(pos, pos + m))
+            pos += m
+        return v, self._obs_dict(rec, fields, sl)
+
+    def plant_obs_slots(self, slots):
+        """Slots of the device-resident record of the last OB_step(obs=...) call, [len(slots), n]
+        (mpcekf_plant_obs_slots); MpcekfError when there is no record since init_cells, the
+        last fused step or set_state."""
+        sl = np.ascontiguousarray(slots, dtype=np.int32)
+        out = np.empty((sl.size, self.n))
+        self._stage("plant_obs_slots", iptr(sl), int(sl.size), dptr(out), keep=(out, sl))
+        return out
 
     def iterEKF(self, vk, ik, Tk=None, bounds=True, xind=True):
         """[zk, boundzk, ekfData, Xind] = iterEKF(vk, ik, Tk, ekfData)  (iterEKF.m:30).

@@ -39,6 +39,11 @@ TF_NAMES = [
 ]
 TF_CODE = {n: i for i, n in enumerate(TF_NAMES)}
 
+# the fields of OB_step's obs struct in record order (include/mpcekf.h: MPCEKF_OBS_*)
+OBS_FIELDS = ("negSOC", "posSOC", "cellSOC", "negIfdl", "posIfdl", "negIfdl0", "posIfdl3", "negIf", "posIf",
+              "negIf0", "posIf3", "negIdl", "posIdl", "negThetass", "posThetass", "negThetass0", "posThetass3",
+              "negPhise", "posPhise", "negPhise0", "Phie", "Thetae", "negPhis", "posPhis", "Vcell")
+
 # Role slots: the 11 rows the hot path addresses individually.  The device
 # layout puts them first, in this order (see DESIGN.md "row permutation").
 ROLE_NAMES = ["Ifdl0", "Ifdl3", "If0", "If3", "Thetass0", "Thetass3",
@@ -517,6 +522,34 @@ class ROM:
         return dict(perm=np.array(perm, dtype=np.int32),
                     flags=flags[perm].astype(np.int32),
                     c0kind=c0[perm].astype(np.int32))
+
+    # ---- OB_step's obs record (include/mpcekf.h MPCEKF_OBS_*) -------------
+    def obs_rows(self):
+        """{field: ROM rows} of OB_step's obs (OB_step.m:226-228, 289-356) in the record's
+        field order; a scalar field (negSOC, negIfdl0, Vcell, ..) maps to None or its one row.
+        Phie's rows are ind.Phie (after the x = 0 drop): the field is one longer, -negPhise0
+        first (OB_step.m:320-322)."""
+        info = self.resolve_indices()
+        ind, ro = info["ind"], info["roles"]
+        rows = {k: None for k in OBS_FIELDS}
+        for k in ("negIfdl", "posIfdl", "negIf", "posIf", "negIdl", "posIdl", "negThetass", "posThetass",
+                  "negPhise", "posPhise", "negPhis", "posPhis"):
+            rows[k] = list(ind[k])
+        rows["Phie"], rows["Thetae"] = list(info["Phie"]), list(info["Thetae"])
+        for k, r in (("negIfdl0", "Ifdl0"), ("posIfdl3", "Ifdl3"), ("negIf0", "If0"), ("posIf3", "If3"),
+                     ("negThetass0", "Thetass0"), ("posThetass3", "Thetass3"), ("negPhise0", "Phise0")):
+            rows[k] = ro[r]
+        return rows
+
+    def obs_layout(self):
+        """{field: slice} of the observable record of mpcekf_plant_step_obs, in the order of
+        the MPCEKF_OBS_* enum; the last slice's stop is nobs (mpcekf_obs_layout's offsets)."""
+        out, o = {}, 0
+        for k, r in self.obs_rows().items():
+            n = len(r) + (k == "Phie") if isinstance(r, list) else 1
+            out[k] = slice(o, o + n)
+            o += n
+        return out
 
     # ---- persistence ----------------------------------------------------
     def to_npz_dict(self):
