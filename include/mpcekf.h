@@ -18,6 +18,7 @@
  *   mpcekf_step         <- the fused loop body runMPC.m:84-111, nsteps times
  *   mpcekf_step_ex      <- the same, with every runMPC.m store (zkEst, zkBound, x_store,
  *                          mpcData.cost) per step
+ *   mpcekf_step_ex_obs  <- the same, plus selected fields of OB_step's obs per step
  *
  * Conventions
  *  - Plain C types only; no exceptions cross the ABI.  Every function returns an
@@ -235,6 +236,17 @@ typedef struct {
 } mpcekf_traj;
 int mpcekf_step_ex(mpcekf_ctx *ctx, int32_t nsteps, const double *tc_degC, const mpcekf_traj *traj,
                    int32_t outputs_on_device);
+
+/* mpcekf_step_ex plus the plant's observables of every step: obs [nsteps][nslots][ncells]
+ * (host, or device when outputs_on_device != 0), slot s of the record of mpcekf_obs_layout at
+ * position p = its index in slots[]; duplicates allowed.  Row k is OB_step's obs of step k:
+ * the plant's own values (obs.negPhise0 is the plant's side-reaction overpotential, where
+ * traj.phise is the EKF's estimate), bit for bit what mpcekf_plant_step_obs gives for the same
+ * state, current and temperature.  A cell with MPCEKF_ST_ERROR at the start of a step has NaN
+ * in that step's row.  nslots == 0 (slots, obs NULL) is mpcekf_step_ex.  MPCEKF_E_ARG: a slot
+ * outside 0..nobs-1, nslots < 0, a NULL among slots/obs with nslots > 0. */
+int mpcekf_step_ex_obs(mpcekf_ctx *ctx, int32_t nsteps, const double *tc_degC, const mpcekf_traj *traj,
+                       const int32_t *slots, int32_t nslots, double *obs, int32_t outputs_on_device);
 
 /* Optional per-step EKF output of the LAST mpcekf_step call: zk and boundzk
  * ([ncells][nz+2], boundzk only with MPCEKF_CF_BOUNDS). */

@@ -1,9 +1,15 @@
-function S = mpcekf_session(op, name, value)
+function [S, out] = mpcekf_session(op, name, value)
 % MPCEKF_SESSION  State the drop-in wrappers share within one MATLAB session: the
 % library context handle (one context for the batch, like the reference's one
 % persistent iterEKF state per session, iterEKF.m:31) and the initKF / initMPC settings
 % the context is created from on the first OB_step call.
 %   S = mpcekf_session('get');  mpcekf_session('set', name, value);  mpcekf_session('reset')
+%   [S, out] = mpcekf_session('step', nsteps, obsFields)
+%     nsteps fused closed-loop steps (runMPC.m:84-111) on the session's context: out.u, v,
+%     soc, phise, nexec are ncells x nsteps.  The optional obsFields -- 'all' or a cellstr
+%     such as {'negPhise0', 'Thetae'}, the names of initCfg.obsFields -- adds out.obs, the
+%     plant's own observables at every step: each field len x ncells x nsteps (len = 1 for
+%     the scalar fields).  out.phise is the EKF's estimate; out.obs.negPhise0 the plant's.
   persistent P
   % zk_last / ekf_tick: the zk the last iterEKF returned and a counter of iterEKF calls, so
   % EKFmatsHandler knows when the library's device copies of zk and Xind are the caller's
@@ -11,6 +17,7 @@ function S = mpcekf_session(op, name, value)
   % the xk an iterMPC call wrote over it)
   if isempty(P), P = struct('h', [], 'kf', [], 'mpc', [], 'device', 0, 'zk_last', [], 'ekf_tick', 0, ...
                             'xhat_dev', []); end
+  out = [];
   switch op
     case 'set'
       P.(name) = value;
@@ -18,6 +25,40 @@ function S = mpcekf_session(op, name, value)
       if ~isempty(P.h), mpcekf_mex('destroy', P.h); end
       P.h = [];
     case 'get'
+    case 'step'
+      if isempty(P.h), error('mpcekf_session: step before the first OB_step call created the context'); end
+      nsteps = name;
+      if nargin < 3 || isempty(value)
+        [u, v, soc, phise, nexec] = mpcekf_mex('step', P.h, nsteps);
+        out = struct('u', u, 'v', v, 'soc', soc, 'phise', phise, 'nexec', nexec);
+      else
+        names = {'negSOC', 'posSOC', 'cellSOC', 'negIfdl', 'posIfdl', 'negIfdl0', 'posIfdl3', 'negIf', 'posIf', ...
+                 'negIf0', 'posIf3', 'negIdl', 'posIdl', 'negThetass', 'posThetass', 'negThetass0', 'posThetass3', ...
+                 'negPhise', 'posPhise', 'negPhise0', 'Phie', 'Thetae', 'negPhis', 'posPhis', 'Vcell'};
+        if ischar(value)
+          if ~strcmpi(value, 'all'), error('obsFields: ''all'' or a cellstr of obs field names'); end
+          value = names;
+        end
+        [known, f] = ismember(value, names);
+        if ~all(known), error('obsFields: unknown obs field %s', value{find(~known, 1)}); end
+        off = mpcekf_mex('obslayout', P.h);
+        slots = arrayfun(@(k) off(k) + 1 : off(k + 1), f, 'UniformOutput', false);
+        keep = ~cellfun(@isempty, slots);                        % a field without rows in tfData.names
+        out = struct('obs', struct());
+        if any(keep)
+          [u, v, soc, phise, nexec, rows] = mpcekf_mex('stepobs', P.h, nsteps, [slots{:}]);
+        else
+          [u, v, soc, phise, nexec] = mpcekf_mex('step', P.h, nsteps);
+          rows = zeros(size(u, 1), 0, nsteps);
+        end
+        out.u = u; out.v = v; out.soc = soc; out.phise = phise; out.nexec = nexec;
+        at = 0;
+        for k = 1:numel(value)                                   % rows: ncells x nslots x nsteps
+          m = numel(slots{k});
+          out.obs.(value{k}) = permute(rows(:, at + 1 : at + m, :), [2 1 3]);
+          at = at + m;
+        end
+      end
     otherwise
       error('mpcekf_session: unknown op %s', op);
   end

@@ -21,6 +21,9 @@
  *   out               = mpcekf_mex('obsslots', h, idx)                 mpcekf_plant_obs_slots
  *                       rows idx (1-based slots of the record, mpcekf_obs_layout) of the last
  *                       'plantobs' record on the device, numel(idx) x ncells
+ *   [u,v,soc,phise,nexec,obs] = mpcekf_mex('stepobs', h, nsteps, idx, tc)  mpcekf_step_ex_obs
+ *                       'step' plus rows idx (1-based slots of the record) of the plant's
+ *                       observables at every step: obs ncells x numel(idx) x nsteps
  *   off               = mpcekf_mex('obslayout', h)                     mpcekf_obs_layout
  *                       1 x 26: field f of obs is slots off(f)+1 .. off(f+1); off(end) = nobs
  *   [zk,zbk,xm,xg]    = mpcekf_mex('ekf', h, vk, ik, tk)               mpcekf_ekf_step     (iterEKF.m:30)
@@ -272,6 +275,18 @@ static void cfg_from_struct(const mxArray *s, mpcekf_config *c) {
   }
 }
 
+/* a real double N-D array ('stepobs': ncells x nslots x nsteps).  The MEX API test shim this
+ * gateway is also built against (tests/mex, not MATLAB) declares no N-D constructor; the entry
+ * point its driver makes arrays with serves there, trailing singletons dropped as MATLAB does. */
+#ifdef MPCEKF_TEST_MATRIX_H
+mxArray *shim_numeric(int cls, int nd, const size_t *dims, const void *data, int cplx);
+static mxArray *dnd(mwSize nd, const mwSize *dims) {
+  while (nd > 2 && dims[nd - 1] == 1) --nd;
+  return shim_numeric((int)mxDOUBLE_CLASS, (int)nd, dims, NULL, 0);
+}
+#else
+static mxArray *dnd(mwSize nd, const mwSize *dims) { return mxCreateNumericArray(nd, dims, mxDOUBLE_CLASS, mxREAL); }
+#endif
 static mxArray *dmat(size_t r, size_t c) { return mxCreateDoubleMatrix((mwSize)r, (mwSize)c, mxREAL); }
 static mxArray *imat(size_t r, size_t c) { return mxCreateNumericMatrix((mwSize)r, (mwSize)c, mxINT32_CLASS, mxREAL); }
 
@@ -341,7 +356,7 @@ static void gateway(mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
   }
   static const char *const with_handle[] = {"destroy", "init", "step", "plant", "ekf", "linearize", "mpc",
                                             "graph", "mpcdiag", "get_state", "set_state", "scalars", "linfields",
-                                            "plantobs", "obsslots", "obslayout"};
+                                            "plantobs", "obsslots", "obslayout", "stepobs"};
   int known = 0;
   for (size_t i = 0; i < sizeof with_handle / sizeof *with_handle; ++i) known = known || !strcmp(cmd, with_handle[i]);
   if (!known) mexErrMsgIdAndTxt("mpcekf:arg", "unknown command %s", cmd);
@@ -349,15 +364,19 @@ static void gateway(mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
   /* the obs commands refuse what no context can make valid before they look at the handle,
      and before any device work: the output count, and slot indices that are no 1-based integers */
   if (!strcmp(cmd, "plantobs") && g_nlhs > 2) mexErrMsgIdAndTxt("mpcekf:arg", "plantobs: at most 2 outputs [Vcell, obs]");
-  if (!strcmp(cmd, "obsslots")) {
-    if (g_nlhs > 1) mexErrMsgIdAndTxt("mpcekf:arg", "obsslots: at most 1 output");
-    need(nrhs, 3, "'obsslots', h, idx");
-    const size_t k = mxGetNumberOfElements(prhs[2]);
-    if (k < 1) mexErrMsgIdAndTxt("mpcekf:arg", "obsslots: idx: expected at least 1 slot index");
-    const double *idx = dvec(prhs[2], k, "idx");
+  const int stepobs = !strcmp(cmd, "stepobs");
+  if (!strcmp(cmd, "obsslots") || stepobs) {
+    if (!stepobs && g_nlhs > 1) mexErrMsgIdAndTxt("mpcekf:arg", "obsslots: at most 1 output");
+    if (stepobs && g_nlhs > 6) mexErrMsgIdAndTxt("mpcekf:arg", "stepobs: at most 6 outputs [u, v, soc, phise, nexec, obs]");
+    if (stepobs) need(nrhs, 4, "'stepobs', h, nsteps, idx[, tc]");
+    else need(nrhs, 3, "'obsslots', h, idx");
+    const mxArray *ia = prhs[stepobs ? 3 : 2];
+    const size_t k = mxGetNumberOfElements(ia);
+    if (k < 1) mexErrMsgIdAndTxt("mpcekf:arg", "%s: idx: expected at least 1 slot index", cmd);
+    const double *idx = dvec(ia, k, "idx");
     for (size_t j = 0; j < k; ++j)
       if (!(idx[j] >= 1 && idx[j] <= 2147483647.0) || idx[j] != (double)(int32_t)idx[j])
-        mexErrMsgIdAndTxt("mpcekf:arg", "obsslots: idx(%zu) = %g is not a slot 1..nobs", j + 1, idx[j]);
+        mexErrMsgIdAndTxt("mpcekf:arg", "%s: idx(%zu) = %g is not a slot 1..nobs", cmd, j + 1, idx[j]);
   }
   mpcekf_ctx *h = handle(prhs[1]);
   int64_t n = 0;
@@ -381,6 +400,36 @@ static void gateway(mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
     plhs[4] = imat(nc, (size_t)ns);
     chk(mpcekf_step(h, ns, tc, mxGetDoubles(plhs[0]), mxGetDoubles(plhs[1]), mxGetDoubles(plhs[2]),
                     mxGetDoubles(plhs[3]), (int32_t *)mxGetData(plhs[4]), 0));
+  } else if (stepobs) {
+    /* 'step' plus rows idx of the plant's observable record at every step (the state each
+       step's OB_step starts from): ncells x numel(idx) x nsteps, the library's
+       [nsteps][nslots][ncells] as it stands */
+    const double nsd = scalar(prhs[2], "nsteps");
+    if (!(nsd >= 0 && nsd <= 2147483647.0) || nsd != (double)(int32_t)nsd)
+      mexErrMsgIdAndTxt("mpcekf:arg", "nsteps: expected a non-negative integer");
+    const int32_t ns = (int32_t)nsd;
+    int32_t off[MPCEKF_OBS_COUNT + 1];
+    chk(mpcekf_obs_layout(h, off));
+    const size_t k = mxGetNumberOfElements(prhs[3]);
+    const double *idx = mxGetDoubles(prhs[3]); /* class, count and >= 1 checked above */
+    int32_t *slots = (int32_t *)mxMalloc(k * sizeof(int32_t));
+    for (size_t j = 0; j < k; ++j) {
+      if (idx[j] > (double)off[MPCEKF_OBS_COUNT])
+        mexErrMsgIdAndTxt("mpcekf:arg", "stepobs: idx(%zu) = %g is not a slot 1..%d", j + 1, idx[j],
+                          (int)off[MPCEKF_OBS_COUNT]);
+      slots[j] = (int32_t)idx[j] - 1;
+    }
+    const double *tc = nrhs > 4 ? opt_vec(prhs[4], nc * (size_t)ns, "tc (ncells x nsteps)") : NULL;
+    for (int i = 0; i < 4; ++i) plhs[i] = dmat(nc, (size_t)ns);
+    plhs[4] = imat(nc, (size_t)ns);
+    const mwSize od[3] = {(mwSize)nc, (mwSize)k, (mwSize)ns};
+    plhs[5] = dnd(3, od);
+    mpcekf_traj tr;
+    memset(&tr, 0, sizeof tr);
+    tr.u = mxGetDoubles(plhs[0]); tr.v = mxGetDoubles(plhs[1]); tr.soc = mxGetDoubles(plhs[2]);
+    tr.phise = mxGetDoubles(plhs[3]); tr.nexec = (int32_t *)mxGetData(plhs[4]);
+    chk(mpcekf_step_ex_obs(h, ns, tc, &tr, slots, (int32_t)k, mxGetDoubles(plhs[5]), 0));
+    mxFree(slots);
   } else if (!strcmp(cmd, "plant")) {
     need(nrhs, 3, "'plant', h, iapp[, tc]");
     plhs[0] = dmat(1, nc);

@@ -82,7 +82,7 @@ EXPORTS = [
     "mpcekf_build_id", "mpcekf_cl_eig", "mpcekf_mpc_diag", "mpcekf_set_graph",
     "mpcekf_dev_alloc", "mpcekf_dev_free", "mpcekf_dev_copy", "mpcekf_dev_copy2d", "mpcekf_sync",
     "mpcekf_get_scalars", "mpcekf_lin_fields",
-    "mpcekf_obs_layout", "mpcekf_plant_step_obs", "mpcekf_plant_obs_slots",
+    "mpcekf_obs_layout", "mpcekf_plant_step_obs", "mpcekf_plant_obs_slots", "mpcekf_step_ex_obs",
     # the _async stage twins (include/mpcekf.h)
     "mpcekf_plant_step_async", "mpcekf_ekf_step_async", "mpcekf_linearize_async", "mpcekf_lin_fields_async",
     "mpcekf_mpc_step_async", "mpcekf_mpc_step_ex_async", "mpcekf_mpc_diag_async", "mpcekf_get_scalars_async",
@@ -116,6 +116,7 @@ def load():
     L.mpcekf_init_cells.argtypes = [vp, _dp, _dp]
     L.mpcekf_step.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp, vp, C.c_int32]
     L.mpcekf_step_ex.argtypes = [vp, C.c_int32, vp, C.POINTER(Traj), C.c_int32]
+    L.mpcekf_step_ex_obs.argtypes = [vp, C.c_int32, vp, C.POINTER(Traj), _ip, C.c_int32, vp, C.c_int32]
     L.mpcekf_get_zk.argtypes = [vp, _dp, _dp]
     L.mpcekf_plant_step.argtypes = [vp, _dp, _dp, _dp]
     L.mpcekf_ekf_step.argtypes = [vp, _dp, _dp, _dp, _dp, _dp, _ip, _dp]

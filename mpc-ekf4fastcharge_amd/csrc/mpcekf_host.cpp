@@ -316,12 +316,22 @@ struct mpcekf_ctx {
   KObs ko{};
   double *d_obs_blob = nullptr, *d_obs = nullptr;
   bool stage_obs = false;  // d_obs holds the record of an obs call since init / fused step / set_state
-  int obs_bufs() {
+  // mpcekf_step_ex_obs: the call's slot plan for k_obs_traj (KObsSel::plan), its host copy
+  // (alive until the call's synchronisation) and the permuted row behind each record slot
+  int *d_obs_plan = nullptr;
+  size_t obs_plan_cap = 0;
+  std::vector<int> h_obs_plan, obs_slot_src;
+  int obs_blob_buf() {
     if (!d_obs_blob) {
       HIPCHK(hipMalloc((void **)&d_obs_blob, h_obs_blob.size() * sizeof(double)));
       HIPCHK(hipMemcpy(d_obs_blob, h_obs_blob.data(), h_obs_blob.size() * sizeof(double), hipMemcpyHostToDevice));
       ko.blob = d_obs_blob;
     }
+    return MPCEKF_OK;
+  }
+  int obs_bufs() {
+    int rc = obs_blob_buf();
+    if (rc) return rc;
     if (!d_obs) HIPCHK(hipMalloc((void **)&d_obs, (size_t)ko.nobs * (size_t)n * sizeof(double)));
     ko.rec = d_obs;
     return MPCEKF_OK;
@@ -829,6 +839,16 @@ static int build_rom(mpcekf_ctx *X, const mpcekf_rom *R) {
       const int q = perm[p];
       ko.desc[p] = (unsigned)row_kind[R->tf_code[q]] | (unsigned)(slot1[q] + 1) << 4 | (unsigned)(slot2[q] + 1) << 14;
     }
+    // mpcekf_step_ex_obs: where each record slot comes from (a permuted row or OBS_SRC_*)
+    X->obs_slot_src.assign((size_t)ko.nobs, OBS_SRC_VCELL);
+    for (int p = 0; p < nz; ++p) {
+      if (slot1[perm[p]] >= 0) X->obs_slot_src[slot1[perm[p]]] = p;
+      if (slot2[perm[p]] >= 0) X->obs_slot_src[slot2[perm[p]]] = p;
+    }
+    X->obs_slot_src[OBS_S_NEGSOC] = OBS_SRC_NEGSOC;
+    X->obs_slot_src[OBS_S_POSSOC] = OBS_SRC_POSSOC;
+    X->obs_slot_src[OBS_S_CELLSOC] = OBS_SRC_CELLSOC;
+    X->obs_slot_src[ko.slot_phie0] = OBS_SRC_PHIE0;
     ko.stride = nz * OBS_ROW;
     std::vector<double> &ob = X->h_obs_blob;
     ob.assign((size_t)NM * ko.stride, 0.0);
@@ -1044,7 +1064,7 @@ int mpcekf_ctx_destroy(mpcekf_ctx *X) {
                   X->d_zbk,       X->d_tmp,        X->s.bigx, X->s.ekf,   X->s.lam,   X->d_ts, X->d_hist, X->d_stamps, X->d_bnd, X->d_xm, X->d_xg,
                   X->w.prob, X->w.X, X->w.R, X->w.K, X->w.hii, X->w.it, X->w.smin, X->d_lin, X->d_zsoc, X->d_mb, X->d_uk1p,
                   X->w.q, X->w.list, X->w.hist, X->d_poly, X->d_szk, X->d_sxg, X->d_sxm, X->d_slin, X->d_sv, X->d_zslot,
-                  X->d_obs_blob, X->d_obs};
+                  X->d_obs_blob, X->d_obs, X->d_obs_plan};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   for (auto &g : X->graphs) (void)hipGraphExecDestroy(g.exec);
@@ -1149,12 +1169,18 @@ static int lerr(int rc, const char *what) {
 
 // runMPC.m:84-111, nsteps times: OB_step -> (all-model advance + EKF time
 // update) -> iterEKF measurement update -> EKFmatsHandler -> iterMPC.
-int mpcekf_step_ex(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const mpcekf_traj *tr,
-                   int32_t outputs_on_device) {
+// nslots > 0 (mpcekf_step_ex_obs): k_obs_traj first in every step, its rows one more output
+// field; nslots == 0 is mpcekf_step_ex: the same launches, allocations and copies as ever.
+static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const mpcekf_traj *tr,
+                     const int32_t *slots, int32_t nslots, double *obs, int32_t outputs_on_device) {
   if (X) X->stage_zk = X->stage_lin = X->stage_v = X->stage_obs = false;  // the stage route's device hand-offs are stale
   int rc = need_init(X);
   if (rc) return rc;
   if (nsteps < 0) return fail(MPCEKF_E_ARG, "nsteps < 0");
+  if (nslots < 0 || (nslots && (!slots || !obs))) return fail(MPCEKF_E_ARG, "step_ex_obs: nslots < 0 or a null slots / obs");
+  for (int i = 0; i < nslots; ++i)
+    if (slots[i] < 0 || slots[i] >= X->ko.nobs)
+      return fail(MPCEKF_E_ARG, "step_ex_obs: slot %d outside 0..%d", slots[i], X->ko.nobs - 1);
   if (tc_degC && !outputs_on_device && (rc = check_tc(tc_degC, (size_t)X->n * (size_t)nsteps))) return rc;
   mpcekf_traj none{};
   if (!tr) tr = &none;
@@ -1177,7 +1203,8 @@ int mpcekf_step_ex(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const m
            {tr->phise, 8, 1, nullptr},   {tr->nexec, 4, 1, nullptr},  {tr->x, 8, 6, nullptr},
            {tr->zk, 8, nzz, nullptr},    {tr->zbk, 8, nzz, nullptr},  {tr->J_unc, 8, 1, nullptr},
            {tr->J_fin, 8, 1, nullptr},   {tr->norm_du, 8, 1, nullptr}, {tr->nviol, 4, 1, nullptr},
-           {tr->poles, 8, 2 * NA, nullptr}, {tr->sv, 8, NA, nullptr}};
+           {tr->poles, 8, 2 * NA, nullptr}, {tr->sv, 8, NA, nullptr},
+           {nslots ? obs : nullptr, 8, (size_t)nslots, nullptr}};  // [nsteps][nslots][ncells]
   constexpr int NF = sizeof(f) / sizeof(f[0]);
   const double *dtc = tc_degC;  // [nsteps][n] device copy of the per-step temperatures
   if (outputs_on_device) {
@@ -1201,6 +1228,32 @@ int mpcekf_step_ex(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const m
   // and the uk_1 the step's iterMPC used
   const bool diag = f[12].dev || f[13].dev;
   if (diag && (rc = X->diag_bufs())) return rc;
+  // the obs selection: each position's source and the shared values some position reads,
+  // uploaded on the step's stream before the loop (and before a graph replay)
+  KObsSel osel{};
+  if (nslots) {
+    if ((rc = X->obs_blob_buf())) return rc;
+    if (X->obs_plan_cap < (size_t)nslots) {
+      if (X->d_obs_plan) (void)hipFree(X->d_obs_plan);
+      X->d_obs_plan = nullptr;
+      X->obs_plan_cap = 0;
+      const size_t cap = std::max((size_t)nslots, (size_t)X->ko.nobs);  // duplicates may exceed nobs
+      HIPCHK(hipMalloc((void **)&X->d_obs_plan, cap * sizeof(int)));
+      X->obs_plan_cap = cap;
+    }
+    std::vector<int> &plan = X->h_obs_plan;
+    plan.resize((size_t)nslots);
+    for (int i = 0; i < nslots; ++i) {
+      const int src = plan[i] = X->obs_slot_src[slots[i]];
+      const int kind = src >= 0 ? (int)(X->ko.desc[src] & 15u) : -1;
+      if (src == OBS_SRC_VCELL || kind == OBS_PPHIS) osel.need |= OBS_NEED_V;
+      if (src == OBS_SRC_PHIE0 || kind == OBS_NPHISE || kind == OBS_PHIE) osel.need |= OBS_NEED_UN;
+      if (kind == OBS_PPHISE) osel.need |= OBS_NEED_UP;
+    }
+    HIPCHK(hipMemcpyAsync(X->d_obs_plan, plan.data(), (size_t)nslots * sizeof(int), hipMemcpyHostToDevice, X->stream));
+    osel.plan = X->d_obs_plan;
+    osel.nsel = nslots;
+  }
   constexpr int NEV = 8;  // events per step: plant | cell | bounds | hild (+ diag) |, then | flush |, hild start (side)
   if (X->timing && X->ev.size() < (size_t)nsteps * NEV) {
     size_t old = X->ev.size();
@@ -1238,6 +1291,13 @@ int mpcekf_step_ex(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const m
       hipEvent_t *E = sample ? &X->ev[(size_t)k * NEV] : nullptr;
       if (E) HIPCHK(hipEventRecord(E[0], X->stream));
       if (diag) HIPCHK(hipMemcpyAsync(X->d_uk1p, X->s.uk_1, n * 8, hipMemcpyDeviceToDevice, X->stream));
+      if (nslots) {  // the plant's observables of step t, before anything advances the plant
+        KObsSel ok = osel;
+        ok.out = (double *)row(14, k);
+        if ((rc = lerr(launch_obs_traj(X->r, X->s, X->ko, ok, t, dtc ? dtc + (size_t)k * n : nullptr, X->stream),
+                       "obs_traj")))
+          return rc;
+      }
       if (!plant_in_cell &&
           (rc = lerr(launch_plant(X->r, X->s, X->s.uk, X->s.vk, t, dtc ? dtc + (size_t)k * n : nullptr, X->stream),
                      "plant")))
@@ -1364,6 +1424,9 @@ int mpcekf_step_ex(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const m
     // replays one instantiated graph instead of 5-7 launches per step
     std::vector<uintptr_t> key = {(uintptr_t)nsteps, (uintptr_t)dtc, (uintptr_t)diag, (uintptr_t)bounds};
     for (const F &e : f) key.push_back((uintptr_t)e.dev);
+    key.push_back((uintptr_t)osel.plan);  // a regrown plan buffer retires the graphs that named the old one
+    key.push_back((uintptr_t)nslots);
+    for (int i = 0; i < nslots; ++i) key.push_back((uintptr_t)slots[i]);
     if ((rc = X->graph_launch(key, run_steps))) return rc;
   } else if ((rc = run_steps())) {
     return rc;
@@ -1385,7 +1448,7 @@ int mpcekf_step_ex(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const m
     for (int k = 0; k < nsteps; ++k)
       for (int j = 0; j < 5; ++j) {
         if ((k + 1) % X->timing_every != 0 && k != nsteps - 1) continue;
-        if ((j == 4 && !flushed[k]) || (j == 2 && !bnd_kernel) || (j == 0 && plant_in_cell) ||
+        if ((j == 4 && !flushed[k]) || (j == 2 && !bnd_kernel) || (j == 0 && plant_in_cell && !nslots) ||
             (j == 3 && hild_in_cell && !diag))
           continue;
         float ms = 0;
@@ -1396,6 +1459,16 @@ int mpcekf_step_ex(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const m
       }
   }
   return MPCEKF_OK;
+}
+
+int mpcekf_step_ex(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const mpcekf_traj *tr,
+                   int32_t outputs_on_device) {
+  return step_impl(X, nsteps, tc_degC, tr, nullptr, 0, nullptr, outputs_on_device);
+}
+
+int mpcekf_step_ex_obs(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const mpcekf_traj *tr,
+                       const int32_t *slots, int32_t nslots, double *obs, int32_t outputs_on_device) {
+  return step_impl(X, nsteps, tc_degC, tr, slots, nslots, obs, outputs_on_device);
 }
 
 int mpcekf_cl_eig(int32_t n, const double *a, double *re, double *im, double *sv) {

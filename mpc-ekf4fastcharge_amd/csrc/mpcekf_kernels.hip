@@ -2018,6 +2018,145 @@ __global__ void __launch_bounds__(OBS_BLOCK) k_plant_obs(const KRom r, const KSt
 }
 
 // ---------------------------------------------------------------------------
+// k_obs_traj: selected observables of OB_step.m:226-228,289-356 along the fused loop
+// (mpcekf_step_ex_obs), k_plant_obs's lane quad on k_plant_obs's blob.  Launched at the top
+// of fused step t, before whichever kernel runs the plant (k_plant4, k_cell's cell_plant,
+// k_ekf4's quad_plant); it only reads the state and stores nothing but its output rows.
+//  - The fused loop defers the all-model time update: lane j's corner record is current
+//    through step ts_plant[c][mj] of the running call, so the lane replays it through steps
+//    ts + 1 .. t - 1 from the hist_u ring in registers, with the plant's own expression
+//    (k_plant4) and diag(A) of the plant blob: the plant's bits, and no store to bigx.
+//  - The step's inputs: Iapp = s.uk (the command the step applies) and the temperature of
+//    tc_in, which no kernel has written to s.Tc yet.
+//  - Only the call's selected slots: q.plan[p] is the source of output position p (a
+//    permuted row, or SRC_* below), so a row no position reads is never formed, and q.need
+//    (wave-uniform) skips the Vcell chain and the two average-Uocp lookups nobody asked for.
+// Output position p of this step at q.out[p * n + c], stored by lane p & 3 of the quad.
+// Every value: k_plant_obs's expressions, hence its bits.
+// ---------------------------------------------------------------------------
+template <bool GR, bool PL>
+__global__ void __launch_bounds__(OBS_BLOCK) k_obs_traj(const KRom r, const KState s, const KObs o, const KObsSel q,
+                                                           const int lazy_t, const double *tc_in) {
+  extern __shared__ double lds[];
+  const int64_t gt = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int j = (int)(gt & 3);
+  const int64_t c = gt >> 2;  // a quad is one cell: every exit below is quad-uniform
+  const int lo = GR ? o.tab : 0;
+  stage_lds(lds, o.blob + lo, o.len - lo);
+  __syncthreads();
+  const double *tb = lds - lo;
+  const double *L = GR ? o.blob : lds;
+  const double *Tp = tb + o.tab + o.tablen;
+  const double *Zp = Tp + MAXT;
+  if (c >= s.n) return;
+  const size_t n = (size_t)s.n;
+  double *out = q.out + c;
+  if (s.status[c] & ST_ERROR) {
+    for (int p = j; p < q.nsel; p += 4) out[(size_t)p * n] = __builtin_nan("");
+    return;
+  }
+  const double Iapp = s.uk[c];
+  const double T = (tc_in ? tc_in[c] : s.Tc[c]) + 273.15;  // OB_step.m:75
+  const double negSOC = s.SOCn[c], posSOC = s.SOCp[c];      // OB_step.m:226-227
+  const double SOC0n = s.SOC0n[c], SOC0p = s.SOC0p[c];
+  const ETab et = etab<PL>(r, tb + o.tab, T);
+  const double cellSOC = (negSOC - r.th0n) / (r.th100n - r.th0n);  // OB_step.m:228
+  int iZu = 0, iZl = 0, iTu = 0, iTl = 0;
+  if (r.nZ > 1) {
+    int a, b;
+    two_nearest(Zp, r.nZ, cellSOC, a, b);
+    iZu = a > b ? a : b; iZl = a < b ? a : b;
+  }
+  if (r.nT > 1) {
+    int a, b;
+    two_nearest(Tp, r.nT, T, a, b);
+    iTu = a > b ? a : b; iTl = a < b ? a : b;
+  }
+  const int mj = ((j & 2) ? iTu : iTl) * r.nZ + ((j & 1) ? iZu : iZl);
+  double xs[6];
+  {
+    const double2 *p = reinterpret_cast<const double2 *>(s.bigx + ((size_t)c * r.NM + mj) * 6);
+    const double2 q0 = p[0], q1 = p[1], q2 = p[2];
+    xs[0] = q0.x; xs[1] = q0.y; xs[2] = q1.x; xs[3] = q1.y; xs[4] = q2.x; xs[5] = q2.y;
+  }
+  const int tsj = s.ts_plant[c * r.NM + mj];
+  const double Zu = Zp[iZu], Zl = Zp[iZl], Tu = Tp[iTu], Tl = Tp[iTl];
+  double aZ = 0.0, aT = 0.0;
+  if (Zu != Zl) aZ = (cellSOC - Zl) / (Zu - Zl);
+  if (Tu != Tl) aT = (T - Tl) / (Tu - Tl);
+  if (tsj + 1 < lazy_t) {  // OB_step.m:198-200 for the skipped steps, RCH ring inputs per round trip
+    double a[6];
+    {
+      const double *ap = r.plant_blob + (size_t)mj * PREC + NPLANT * NX + 2 * NPLANT;  // diag(A), a[5] = 1
+#pragma unroll
+      for (int e = 0; e < 6; ++e) a[e] = ap[e];
+    }
+    for (int k0 = tsj + 1; k0 < lazy_t; k0 += RCH) {
+      double u[RCH];
+      ring_chunk(s.hist_u, s, c, k0, lazy_t - 1, u);
+#pragma unroll
+      for (int i = 0; i < RCH; ++i)
+        if (k0 + i < lazy_t)
+#pragma unroll
+          for (int e = 0; e < 6; ++e) xs[e] = __builtin_fma(a[e], xs[e], u[i]);
+    }
+  }
+  const double *B = L + (size_t)mj * o.stride;
+  double V = 0.0, UocpnAvg = 0.0, UocppAvg = 0.0, negPhise0 = 0.0;
+  if (q.need & OBS_NEED_V) {  // the Vcell chain of k_plant4 / k_plant_obs
+    double yk[R_PHIE + 1];
+#pragma unroll
+    for (int i = 0; i <= R_PHIE; ++i) {
+      yk[i] = quad_blend(obs_row(B + i * OBS_ROW, xs, Iapp), aZ, aT);
+      __builtin_amdgcn_sched_barrier(0);  // one row's operands at a time (k_plant4)
+    }
+    const double th0 = fmin(fmax(yk[R_TH0] + SOC0n, 1e-6), 1 - 1e-6);
+    const double th3 = fmin(fmax(yk[R_TH3] + SOC0p, 1e-6), 1 - 1e-6);
+    const double te1 = fmax(yk[R_TE1] + 1, 1e-6);
+    const double teE = fmax(yk[R_TEE] + 1, 1e-6);
+    double i0n = et.f(0, EF_K0, negSOC) * sqrt(te1 * (1 - th0) * th0);  // OB_step.m:329-332
+    double i0p = et.f(1, EF_K0, posSOC) * sqrt(teE * (1 - th3) * th3);
+    double negEta0 = 2 * r.R * T / r.F * dasinh(yk[R_IF0] / (2 * i0n));
+    double posEta3 = 2 * r.R * T / r.F * dasinh(yk[R_IF3] / (2 * i0p));
+    double Uocpn0 = et.f(0, EF_U, th0), Uocpp3 = et.f(1, EF_U, th3);
+    const double Rfn = et.f(0, EF_RF, negSOC), Rfp = et.f(1, EF_RF, posSOC);  // OB_step.m:339-340
+    V = posEta3 - negEta0 + yk[R_PHIE] + Uocpp3 - Uocpn0 + (Rfp * yk[R_IFDL3] - Rfn * yk[R_IFDL0]);
+    V = V - r.Rc * Iapp;
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  if (q.need & OBS_NEED_UN) {  // OB_step.m:313,317
+    UocpnAvg = et.f(0, EF_U, negSOC);
+    negPhise0 = quad_blend(obs_row(B + R_PHISE0 * OBS_ROW, xs, Iapp), aZ, aT) + UocpnAvg;
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  if (q.need & OBS_NEED_UP) {  // OB_step.m:314
+    UocppAvg = et.f(1, EF_U, posSOC);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  for (int p = 0; p < q.nsel; ++p) {
+    const int src = q.plan[p];  // wave-uniform
+    double v;
+    if (src >= 0) {
+      v = quad_blend(obs_row(B + src * OBS_ROW, xs, Iapp), aZ, aT);
+      switch ((int)(o.desc[src] & 15u)) {
+        case OBS_NTHSS: v = fmin(fmax(v + SOC0n, 1e-6), 1 - 1e-6); break;  // OB_step.m:302-310
+        case OBS_PTHSS: v = fmin(fmax(v + SOC0p, 1e-6), 1 - 1e-6); break;
+        case OBS_NPHISE: v = v + UocpnAvg; break;                          // OB_step.m:315-317
+        case OBS_PPHISE: v = v + UocppAvg; break;
+        case OBS_PHIE: v = v - negPhise0; break;                           // OB_step.m:322
+        case OBS_THETAE: v = fmax(v + 1, 1e-6); break;                     // OB_step.m:325-326
+        case OBS_PPHIS: v = v + V; break;                                  // OB_step.m:348
+        default: break;
+      }
+    } else {
+      v = src == OBS_SRC_NEGSOC ? negSOC : src == OBS_SRC_POSSOC ? posSOC : src == OBS_SRC_CELLSOC ? cellSOC
+          : src == OBS_SRC_PHIE0 ? -negPhise0 : V;  // OB_step.m:226-228, 321, 356
+    }
+    if ((p & 3) == j) out[(size_t)p * n] = v;
+  }
+}
+
+// ---------------------------------------------------------------------------
 // k_bulk: all-model plant advance and EKF time update (HBM streaming)
 // ---------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_bulk(const KRom r, const KCfg cf, const KState s, const double *iapp,
@@ -4403,6 +4542,27 @@ int launch_plant_obs(const KRom &r, const KState &s, const KObs &o, const double
   } else {
     if (o.global) go(k_plant_obs<true, false>);
     else go(k_plant_obs<false, false>);
+  }
+  return (int)hipGetLastError();
+}
+
+int launch_obs_traj(const KRom &r, const KState &s, const KObs &o, const KObsSel &q, int lazy_t, const double *tc_in,
+                    void *stream) {
+  if (s.n == 0 || q.nsel == 0) return 0;
+  const hipStream_t st = (hipStream_t)stream;
+  const int lds = obs_lds_bytes(o);
+  const int block = spread_block(s.n, 4, OBS_BLOCK);
+  const dim3 g(grid_for(4 * s.n, block)), b(block);
+  auto go = [&](auto kern) {  // k_plant_obs's blob: above the 64 KiB default from ~40 models
+    (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    hipLaunchKernelGGL(kern, g, b, lds, st, r, s, o, q, lazy_t, tc_in);
+  };
+  if (r.npoly) {
+    if (o.global) go(k_obs_traj<true, true>);
+    else go(k_obs_traj<false, true>);
+  } else {
+    if (o.global) go(k_obs_traj<true, false>);
+    else go(k_obs_traj<false, false>);
   }
   return (int)hipGetLastError();
 }

@@ -127,6 +127,19 @@ struct KObs {
   double *rec;                   // [nobs][n] slot-major
 };
 
+// mpcekf_step_ex_obs: the call's slot selection for k_obs_traj.  plan[p] is the source of
+// output position p: a permuted row of the obs blob (>= 0, corrected by its desc kind) or one
+// of OBS_SRC_*; need says which shared values some position reads.
+enum { OBS_SRC_NEGSOC = -1, OBS_SRC_POSSOC = -2, OBS_SRC_CELLSOC = -3, OBS_SRC_PHIE0 = -4, OBS_SRC_VCELL = -5 };
+enum { OBS_NEED_V = 1,    // Vcell (rows 0..R_PHIE, i0, asinh, Uocp(thetass), Rf): Vcell, posPhis rows
+       OBS_NEED_UN = 2,   // Uocp(negSOC) and negPhise0 (row R_PHISE0): negPhise rows, negPhise0, Phie
+       OBS_NEED_UP = 4 }; // Uocp(posSOC): posPhise rows
+struct KObsSel {
+  const int *plan;  // [nsel] device
+  int nsel, need;
+  double *out;      // this step's [nsel][n] block
+};
+
 // Inputs/outputs of one cell-kernel launch.  Any pointer may be null.
 struct KIO {
   int mode;               // MODE_* bits
@@ -192,6 +205,11 @@ int launch_plant(const KRom &r, const KState &s, const double *iapp, double *vou
 // it before the call's launch_plant / launch_bulk); the temperature is s.Tc
 int launch_plant_obs(const KRom &r, const KState &s, const KObs &o, const double *iapp, void *stream);
 int obs_lds_bytes(const KObs &o);
+// the selected observables of fused step lazy_t (>= 1) into q.out, from the state before the
+// step's plant runs: launch it first in the step.  Reads s.uk and tc_in (null: s.Tc), replays
+// stale corners from the hist_u ring in registers; stores only q.out
+int launch_obs_traj(const KRom &r, const KState &s, const KObs &o, const KObsSel &q, int lazy_t, const double *tc_in,
+                    void *stream);
 // brings every model of every cell from its ts to step t, then sets ts = new_ts
 // every model of cells [c_lo, c_hi) (c_hi < 0: to the end) brought to step t, timestamps new_ts
 int launch_flush(const KRom &r, const KCfg &c, const KState &s, int t, int new_ts, void *stream, int64_t c_lo = 0,

@@ -275,15 +275,21 @@ class Context:
                        norm_du=(np.float64, ()), nviol=(np.int32, ()), poles=(np.float64, (7, 2)),
                        sv=(np.float64, (7,)))
 
-    def step(self, nsteps, outputs=("u", "v", "soc", "phise", "nexec"), tc=None):
+    def step(self, nsteps, outputs=("u", "v", "soc", "phise", "nexec"), tc=None, obs=None):
         """nsteps fused closed-loop steps (runMPC.m:83-112).  ``outputs`` names the per-step
         stores to return as [nsteps, ncells(, k)] arrays: u, v, soc, phise, nexec, and the
         diagnostics x (x_store), zk / zbk (zkEst / zkBound), J_unc, J_fin, norm_du, nviol
         (mpcData.cost), poles ([.., 7, 2] re/im of eig(CL)) and sv (svd(CL)), the stability
         diagnostics of iterMPC.m:53-60 (returned as complex [nsteps, ncells, 7] for poles).
         ``tc``: the TC of each step in degC (runMPC.m:85-92), see :func:`tc_grid`; None keeps
-        every cell's current temperature."""
+        every cell's current temperature.
+        ``obs``: the plant's own observables of every step (OB_step's obs struct on the state
+        each step starts from; ``phise`` above is the EKF's estimate): True for every field,
+        or a field name / tuple of names as OB_step(obs=...) takes them.  Adds out["obs"], a
+        dict field -> [nsteps, ncells] (scalar fields) or [nsteps, ncells, len] (vector
+        fields); only the selected slots are computed and copied.  None: the call as it was."""
         n = self.n
+        fields, slots = self._obs_select(obs, "step")   # KeyError before any library call
         tcs = None if tc is None else tc_grid(tc, nsteps, n)
         out = {}
         tr = _lib.Traj()
@@ -294,17 +300,55 @@ class Context:
             tail = (self.nz + 2,) if tail is None else tail
             out[k] = np.empty((nsteps, n) + tail, dtype=dt)
             setattr(tr, k, out[k].ctypes.data_as(C.c_void_p).value)
-        check(self.L.mpcekf_step_ex(self.h, int(nsteps), tcs.ctypes.data_as(C.c_void_p) if tcs is not None else None,
-                                    C.byref(tr), 0))
+        tcp = tcs.ctypes.data_as(C.c_void_p) if tcs is not None else None
+        if fields is None:
+            check(self.L.mpcekf_step_ex(self.h, int(nsteps), tcp, C.byref(tr), 0))
+        else:
+            rec = np.empty((nsteps, slots.size, n))
+            if slots.size:
+                check(self.L.mpcekf_step_ex_obs(self.h, int(nsteps), tcp, C.byref(tr), iptr(slots), int(slots.size),
+                                                rec.ctypes.data_as(C.c_void_p), 0))
+            else:
+                check(self.L.mpcekf_step_ex(self.h, int(nsteps), tcp, C.byref(tr), 0))
+            lay, pos, out["obs"] = self.rom.obs_layout(), 0, {}
+            for k in fields:   # slot-major rows per step -> [nsteps, n] / [nsteps, n, len]
+                m = lay[k].stop - lay[k].start
+                out["obs"][k] = rec[:, pos] if k in self._OBS_SCALARS else rec[:, pos:pos + m].transpose(0, 2, 1)
+                pos += m
         if "poles" in out:
             out["poles"] = _complex(out["poles"])
         return out
 
-    def step_device(self, nsteps, u=0, v=0, soc=0, phise=0, nexec=0):
+    def _obs_select(self, obs, who):
+        """obs=None / True / name / names -> (fields, int32 slots of the record), (None, None)
+        for None; an unknown field raises KeyError (the spelling rules of OB_step(obs=...))."""
+        if obs is None or obs is False:
+            return None, None
+        lay = self.rom.obs_layout()
+        fields = OBS_FIELDS if obs is True else (obs,) if isinstance(obs, str) else tuple(obs)
+        for k in fields:
+            if k not in lay:
+                raise KeyError(f"{who}: unknown obs field {k!r} (one of {OBS_FIELDS})")
+        slots = np.ascontiguousarray(np.concatenate([np.arange(lay[k].start, lay[k].stop) for k in fields] or [[]]),
+                                     dtype=np.int32)
+        return tuple(fields), slots
+
+    def step_device(self, nsteps, u=0, v=0, soc=0, phise=0, nexec=0, obs=0, obs_slots=()):
         """Fused steps writing [nsteps][ncells] outputs to device pointers (ints or
-        DeviceBuffer; allocate them with DeviceBuffer / mpcekf_dev_alloc)."""
+        DeviceBuffer; allocate them with DeviceBuffer / mpcekf_dev_alloc).  ``obs``: a device
+        buffer [nsteps][len(obs_slots)][ncells] for the slots ``obs_slots`` of the plant's
+        observable record at every step (mpcekf_step_ex_obs)."""
         p = [C.c_void_p(x.ptr if isinstance(x, DeviceBuffer) else x) if x else None for x in (u, v, soc, phise, nexec)]
-        check(self.L.mpcekf_step(self.h, int(nsteps), None, *p, 1))
+        sl = np.ascontiguousarray(obs_slots, dtype=np.int32).ravel()
+        if not obs and not sl.size:
+            check(self.L.mpcekf_step(self.h, int(nsteps), None, *p, 1))
+            return
+        tr = _lib.Traj()
+        for k, x in zip(("u", "v", "soc", "phise", "nexec"), p):
+            setattr(tr, k, x.value if x is not None else None)
+        op = C.c_void_p(obs.ptr if isinstance(obs, DeviceBuffer) else obs) if obs else None
+        check(self.L.mpcekf_step_ex_obs(self.h, int(nsteps), None, C.byref(tr), iptr(sl) if sl.size else None,
+                                        int(sl.size), op, 1))
 
     def sync(self):
         """Wait for every launch on the context's device and complete the asynchronous stage
@@ -640,14 +684,15 @@ def structured_M(Hv, He, Hs):
     return M
 
 
-def runMPC(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=None):
+def runMPC(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=None, obs=None):
     """runMPC.m:72-112 for a batch of cells; returns trajectories [nsteps, ncells].
-    tc_traj [nsteps, ncells] (degC): a temperature profile (TC is the initial one)."""
+    tc_traj [nsteps, ncells] (degC): a temperature profile (TC is the initial one).
+    obs: the plant's observables of every step as out["obs"] (Context.step's obs=)."""
     SOC0 = np.atleast_1d(np.asarray(SOC0, dtype=np.float64))
     n = ncells or SOC0.shape[0]
     with Context(rom, n, cfg, device) as ctx:
         ctx.init_cells(SOC0, TC)
-        out = ctx.step(nsteps, tc=tc_traj)
+        out = ctx.step(nsteps, tc=tc_traj, obs=obs)
         out["status"] = ctx.get_state()["status"]
         return out
 
