@@ -1,7 +1,7 @@
 // mpcekf_kernels.hip -- gfx950 kernels of the batched MPC+EKF control step.
 //
 // Work mapping (DESIGN.md "Kernels"):
-//   k_plant  lane-per-cell   OB_step.m:188-357 minus the all-model advance
+//   k_plant4 quad-per-cell   OB_step.m:188-357 minus the all-model advance
 //   k_bulk   block-streaming OB_step.m:278 (bigX = bigA.*bigX + Iapp) and the
 //                            all-model EKF time update iterEKF.m:73-84, over the
 //                            whole cell batch: the HBM-bound part
@@ -17,6 +17,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstdint>
+#include <type_traits>
 
 #include "mpcekf_kernels.hpp"
 #include "mpcekf_mpc.hpp"
@@ -1596,50 +1597,17 @@ __device__ __forceinline__ void ring_chunk(const double *ring, const KState &s, 
   for (int i = 0; i < RCH; ++i) v[i] = ring[(size_t)(min(k0 + i, kmax) % LAZY_H) * s.n + c];
 }
 // ---------------------------------------------------------------------------
-// k_plant: OB_step simStep outputs for every cell (lane per cell)
+// OB_step's simStep (OB_step.m:188-357), written once for every kernel that runs it:
+// k_plant4, k_plant_obs, k_obs_traj, cell_plant (k_cell) and quad_plant (k_ekf4).  The routes
+// agree bit for bit because they evaluate these expressions, in this order; where a call
+// sits in a kernel's instruction stream, and its sched_barriers, are the kernel's own.
 // ---------------------------------------------------------------------------
-template <bool GR, bool PL>
-__global__ void __launch_bounds__(256) k_plant(const KRom r, const KState s, const double *iapp, double *vout,
-                                               const int lazy_t, const double *tc_in) {
-  extern __shared__ double lds[];
-  // GR: tables only in LDS (tb + plant_tab is lds), model rows from the global blob
-  const int lo = GR ? r.plant_tab : 0;
-  stage_lds(lds, r.plant_blob + lo, r.plant_len - lo);
-  __syncthreads();
-  const double *tb = lds - lo;
-  const double *L = GR ? r.plant_blob : lds;
-  const double *Tp = tb + r.plant_tab + r.plant_tablen;
-  const double *Zp = Tp + MAXT;
-  int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (c == 0 && lazy_t) *s.hslow = 0;  // k_hild_slow of the previous step has finished
-  if (c >= s.n) return;
-  if (tc_in) s.Tc[c] = tc_in[c];  // this step's TC (runMPC.m:85-92), read by every later kernel
-  if (lazy_t) {  // this step's inputs, for the deferred updates of every model (k_cell, k_flush)
-    const size_t slot = (size_t)(lazy_t % LAZY_H) * s.n + c;
-    s.hist_u[slot] = iapp[c];
-    s.hist_p[slot] = s.priorI[c];
-  }
-  if (s.status[c] & ST_ERROR) {
-    vout[c] = __builtin_nan("");
-    return;
-  }
-  double Iapp = iapp[c];
-  double T = (tc_in ? tc_in[c] : s.Tc[c]) + 273.15;  // OB_step.m:75
-  const ETab et = etab<PL>(r, tb + r.plant_tab, T);
-  double SOCnAvg = s.SOCn[c], SOCpAvg = s.SOCp[c];
-  const double negSOC = SOCnAvg, posSOC = SOCpAvg;  // obs.negSOC / posSOC: pre-update (OB_step.m:226-227)
-  double cellSOC = (SOCnAvg - r.th0n) / (r.th100n - r.th0n);
-  const double Cdleffn = et.f(0, EF_CDL, s.SOC0n[c]), Cdleffp = et.f(1, EF_CDL, s.SOC0p[c]);  // OB_step.m:212-219
-  double dUn = et.f(0, EF_DU, SOCnAvg), dUp = et.f(1, EF_DU, SOCpAvg);
-  double dQn = fabs(r.th100n - r.th0n), dQp = fabs(r.th100p - r.th0p);
-  double res0n = -dQn / (3600 * r.Q - Cdleffn * dQn * dUn);
-  double res0p = dQp / (3600 * r.Q - Cdleffp * dQp * dUp);
-  SOCnAvg = SOCnAvg + res0n * Iapp * r.Ts;
-  SOCpAvg = SOCpAvg + res0p * Iapp * r.Ts;
-  if (SOCnAvg < 0) SOCnAvg = 0;
-  if (SOCnAvg > 1) SOCnAvg = 1;
-  if (SOCpAvg < 0) SOCpAvg = 0;
-  if (SOCpAvg > 1) SOCpAvg = 1;
+struct PlantCorners {
+  int iZu, iZl, iTu, iTl;
+};
+// the two nearest SOC and temperature set points (0 on a single-set-point axis)
+__device__ __forceinline__ PlantCorners plant_corners(const KRom &r, const double *Tp, const double *Zp,
+                                                      double cellSOC, double T) {
   int iZu = 0, iZl = 0, iTu = 0, iTl = 0;
   if (r.nZ > 1) {
     int a, b;
@@ -1651,57 +1619,106 @@ __global__ void __launch_bounds__(256) k_plant(const KRom r, const KState s, con
     two_nearest(Tp, r.nT, T, a, b);
     iTu = a > b ? a : b; iTl = a < b ? a : b;
   }
-  double Zu = Zp[iZu], Zl = Zp[iZl], Tu = Tp[iTu], Tl = Tp[iTl];
-  int mm[4] = {iTl * r.nZ + iZl, iTl * r.nZ + iZu, iTu * r.nZ + iZl, iTu * r.nZ + iZu};
-  double y[4][NPLANT];
-  double *bx = s.bigx + (size_t)c * r.NM * 6;
-  // the 4 corner states as of step t-1: all loads before any store (duplicate corners)
-  double xs[4][6];
+  return {iZu, iZl, iTu, iTl};
+}
+// corner j's model: mm = {Tl Zl, Tl Zu, Tu Zl, Tu Zu}[j] (OB_step.m:251-275)
+__device__ __forceinline__ int corner_model(const KRom &r, const PlantCorners &pc, int j) {
+  return ((j & 2) ? pc.iTu : pc.iTl) * r.nZ + ((j & 1) ? pc.iZu : pc.iZl);
+}
+__device__ __forceinline__ void corner_models(const KRom &r, const PlantCorners &pc, int mm[4]) {
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const double2 *p = reinterpret_cast<const double2 *>(bx + (size_t)mm[j] * 6);
-    double2 q0 = p[0], q1 = p[1], q2 = p[2];
-    xs[j][0] = q0.x; xs[j][1] = q0.y; xs[j][2] = q1.x; xs[j][3] = q1.y; xs[j][4] = q2.x; xs[j][5] = q2.y;
-  }
-  int tsj[4] = {0, 0, 0, 0};
-  if (lazy_t) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      tsj[j] = s.ts_plant[c * r.NM + mm[j]];
-      const double *a = L + mm[j] * PREC + NPLANT * NX + 2 * NPLANT;
-      for (int k = tsj[j] + 1; k < lazy_t; ++k) {  // OB_step.m:198-200 for the skipped steps
-        const double u = s.hist_u[(size_t)(k % LAZY_H) * s.n + c];
-#pragma unroll
-        for (int e = 0; e < 6; ++e) xs[j][e] = __builtin_fma(a[e], xs[j][e], u);
-      }
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    double x[6];
-#pragma unroll
-    for (int e = 0; e < 6; ++e) x[e] = xs[j][e];
-    const double *B = L + mm[j] * PREC;
-#pragma unroll
-    for (int q = 0; q < NPLANT; ++q) {
-      double acc = 0.0;
-#pragma unroll
-      for (int k = 0; k < NX; ++k) acc = acc + B[q * NX + k] * x[k];
-      acc = acc + B[NPLANT * NX + q] * x[5];
-      y[j][q] = acc + B[NPLANT * NX + NPLANT + q] * Iapp;
-      launder(y[j][q]);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  double aZ = 0.0, aT = 0.0;
+  for (int j = 0; j < 4; ++j) mm[j] = corner_model(r, pc, j);
+}
+// the blend weights of OB_step.m:285 (0 between duplicate corners)
+__device__ __forceinline__ void plant_weights(const double *Tp, const double *Zp, const PlantCorners &pc,
+                                              double cellSOC, double T, double &aZ, double &aT) {
+  const double Zu = Zp[pc.iZu], Zl = Zp[pc.iZl], Tu = Tp[pc.iTu], Tl = Tp[pc.iTl];
+  aZ = 0.0;
+  aT = 0.0;
   if (Zu != Zl) aZ = (cellSOC - Zl) / (Zu - Zl);
   if (Tu != Tl) aT = (T - Tl) / (Tu - Tl);
-  double yk[NPLANT];
+}
+// a corner's 6 states (48 B of bigx)
+__device__ __forceinline__ void load_corner(const double *bx, double xs[6]) {
+  const double2 *p = reinterpret_cast<const double2 *>(bx);
+  const double2 q0 = p[0], q1 = p[1], q2 = p[2];
+  xs[0] = q0.x; xs[1] = q0.y; xs[2] = q1.x; xs[3] = q1.y; xs[4] = q2.x; xs[5] = q2.y;
+}
+__device__ __forceinline__ void store_corner(double *bx, const double x[6]) {
+  double2 *p = reinterpret_cast<double2 *>(bx);
+  p[0] = make_double2(x[0], x[1]);
+  p[1] = make_double2(x[2], x[3]);
+  p[2] = make_double2(x[4], x[5]);
+}
+// SOCnAvg / SOCpAvg through this step (OB_step.m:212-219)
+__device__ __forceinline__ void plant_soc_step(const KRom &r, const ETab &et, double SOC0n, double SOC0p, double Iapp,
+                                               double &SOCnAvg, double &SOCpAvg) {
+  const double Cdleffn = et.f(0, EF_CDL, SOC0n), Cdleffp = et.f(1, EF_CDL, SOC0p);
+  double dUn = et.f(0, EF_DU, SOCnAvg), dUp = et.f(1, EF_DU, SOCpAvg);
+  double dQn = fabs(r.th100n - r.th0n), dQp = fabs(r.th100p - r.th0p);
+  double res0n = -dQn / (3600 * r.Q - Cdleffn * dQn * dUn);
+  double res0p = dQp / (3600 * r.Q - Cdleffp * dQp * dUp);
+  SOCnAvg = SOCnAvg + res0n * Iapp * r.Ts;
+  SOCpAvg = SOCpAvg + res0p * Iapp * r.Ts;
+  if (SOCnAvg < 0) SOCnAvg = 0;
+  if (SOCnAvg > 1) SOCnAvg = 1;
+  if (SOCpAvg < 0) SOCpAvg = 0;
+  if (SOCpAvg > 1) SOCpAvg = 1;
+}
+// x = a .* xs + u (OB_step.m:198-200, 278; x may be xs).  A5: the integrator's a[5] = 1 is read
+// from the blob (the plant and obs blobs carry it as data); otherwise a has NX entries and
+// the 1 is a literal (the cell blob, checked by build_rom).
+template <bool A5>
+__device__ __forceinline__ void plant_advance(const double *a, const double xs[6], double u, double x[6]) {
 #pragma unroll
-  for (int q = 0; q < NPLANT; ++q)
-    yk[q] = (1 - aT) * ((1 - aZ) * y[0][q] + aZ * y[1][q]) + aT * ((1 - aZ) * y[2][q] + aZ * y[3][q]);
-  double th0 = fmin(fmax(yk[R_TH0] + s.SOC0n[c], 1e-6), 1 - 1e-6);
-  double th3 = fmin(fmax(yk[R_TH3] + s.SOC0p[c], 1e-6), 1 - 1e-6);
+  for (int e = 0; e < NX; ++e) x[e] = __builtin_fma(a[e], xs[e], u);
+  x[NX] = __builtin_fma(A5 ? a[NX] : 1.0, xs[NX], u);
+}
+// the skipped steps tsj + 1 .. lazy_t - 1 of a corner, RCH ring inputs per round trip
+template <bool A5>
+__device__ __forceinline__ void plant_replay(double xs[6], const double *a, const KState &s, int64_t c, int tsj,
+                                             int lazy_t) {
+  for (int k0 = tsj + 1; k0 < lazy_t; k0 += RCH) {
+    double u[RCH];
+    ring_chunk(s.hist_u, s, c, k0, lazy_t - 1, u);
+#pragma unroll
+    for (int i = 0; i < RCH; ++i)
+      if (k0 + i < lazy_t) plant_advance<A5>(a, xs, u[i], xs);
+  }
+}
+// one output row of a corner, C x + res0 x5 + D Iapp summed from +0.0 (OB_step.m:251-275)
+__device__ __forceinline__ double plant_row(const double *C, double r0, double d, const double xs[6], double Iapp) {
+  double acc = 0.0;
+#pragma unroll
+  for (int k = 0; k < NX; ++k) acc = acc + C[k] * xs[k];
+  acc = acc + r0 * xs[5];
+  return acc + d * Iapp;
+}
+// the same row from the obs blob's [C 5][res0][D][0] record
+__device__ __forceinline__ double obs_row(const double *B, const double xs[6], double Iapp) {
+  const double2 *p = reinterpret_cast<const double2 *>(B);
+  const double2 c01 = p[0], c23 = p[1], c4r = p[2], d = p[3];
+  double acc = 0.0;
+  acc = acc + c01.x * xs[0];
+  acc = acc + c01.y * xs[1];
+  acc = acc + c23.x * xs[2];
+  acc = acc + c23.y * xs[3];
+  acc = acc + c4r.x * xs[4];
+  acc = acc + c4r.y * xs[5];
+  return acc + d.x * Iapp;
+}
+// the four corners' rows blended (OB_step.m:285); quad_blend: lane j of a quad holds corner j's
+__device__ __forceinline__ double blend4(double y0, double y1, double y2, double y3, double aZ, double aT) {
+  return (1 - aT) * ((1 - aZ) * y0 + aZ * y1) + aT * ((1 - aZ) * y2 + aZ * y3);
+}
+__device__ __forceinline__ double quad_blend(double y, double aZ, double aT) {
+  return blend4(qbc<0>(y), qbc<1>(y), qbc<2>(y), qbc<3>(y), aZ, aT);
+}
+// Vcell from the blended role rows (OB_step.m:329-356); reads yk only at the R_* indices
+__device__ __forceinline__ double plant_vcell(const KRom &r, const ETab &et, const double *yk, double T, double Iapp,
+                                              double negSOC, double posSOC, double SOC0n, double SOC0p) {
+  double th0 = fmin(fmax(yk[R_TH0] + SOC0n, 1e-6), 1 - 1e-6);
+  double th3 = fmin(fmax(yk[R_TH3] + SOC0p, 1e-6), 1 - 1e-6);
   double te1 = fmax(yk[R_TE1] + 1, 1e-6);
   double teE = fmax(yk[R_TEE] + 1, 1e-6);
   double i0n = et.f(0, EF_K0, negSOC) * sqrt(te1 * (1 - th0) * th0);  // OB_step.m:329-332
@@ -1711,41 +1728,20 @@ __global__ void __launch_bounds__(256) k_plant(const KRom r, const KState s, con
   double Uocpn0 = et.f(0, EF_U, th0), Uocpp3 = et.f(1, EF_U, th3);
   const double Rfn = et.f(0, EF_RF, negSOC), Rfp = et.f(1, EF_RF, posSOC);  // OB_step.m:339-340
   double V = posEta3 - negEta0 + yk[R_PHIE] + Uocpp3 - Uocpn0 + (Rfp * yk[R_IFDL3] - Rfn * yk[R_IFDL0]);
-  V = V - r.Rc * Iapp;
-  s.SOCn[c] = SOCnAvg;
-  s.SOCp[c] = SOCpAvg;
-  vout[c] = V;
-  if (lazy_t) {  // advance the corners through step t in place (eager mode: k_bulk does all models)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      if (tsj[j] >= lazy_t) continue;
-      const double *a = L + mm[j] * PREC + NPLANT * NX + 2 * NPLANT;
-      double2 *p = reinterpret_cast<double2 *>(bx + (size_t)mm[j] * 6);
-      double x[6];
-#pragma unroll
-      for (int e = 0; e < 6; ++e) x[e] = __builtin_fma(a[e], xs[j][e], Iapp);
-      p[0] = make_double2(x[0], x[1]);
-      p[1] = make_double2(x[2], x[3]);
-      p[2] = make_double2(x[4], x[5]);
-      s.ts_plant[c * r.NM + mm[j]] = lazy_t;
-    }
-  }
+  return V - r.Rc * Iapp;
 }
 
 // ---------------------------------------------------------------------------
-// k_plant4: k_plant with a lane quad per cell, lane j = corner j of OB_step.m:251-275.
-// Lane-per-cell k_plant runs 65,536 cells as one wave per SIMD, so every round trip
-// (the per-cell scalars, then the corner gathers they select) and every dependent FP64
-// chain is exposed (60 % of its cycles in s_waitcnt, VALU 15 %).  Here lane j gathers and
+// k_plant4: OB_step simStep outputs for every cell, a lane quad per cell, lane j = corner j
+// of OB_step.m:251-275.  A lane per cell runs 65,536 cells as one wave per SIMD, so every
+// round trip (the per-cell scalars, then the corner gathers they select) and every dependent
+// FP64 chain is exposed (60 % of its cycles in s_waitcnt, VALU 15 %).  Here lane j gathers and
 // replays only its corner's 48-B state and forms its 9 output rows; the blend of
 // OB_step.m:281-285 takes the four corners' rows by DPP quad broadcasts in the one-lane
 // expression order, and the per-cell scalar chain (bracket, clamps, asinh, Vcell) is the
 // same instruction stream for the whole quad.  1024-thread blocks: 256 cells share one
-// staged plant blob per CU at 4 waves per SIMD.  Results: k_plant's bits.
+// staged plant blob per CU at 4 waves per SIMD.
 // ---------------------------------------------------------------------------
-#ifndef MPCEKF_PLANT_QUAD
-#define MPCEKF_PLANT_QUAD 1
-#endif
 constexpr int PLANT4_BLOCK = 1024;
 template <bool GR, bool PL>
 __global__ void __launch_bounds__(PLANT4_BLOCK) k_plant4(const KRom r, const KState s, const double *iapp,
@@ -1789,83 +1785,30 @@ __global__ void __launch_bounds__(PLANT4_BLOCK) k_plant4(const KRom r, const KSt
   const ETab et = etab<PL>(r, tb + r.plant_tab, T);
   const double negSOC = SOCnAvg, posSOC = SOCpAvg;  // obs.negSOC / posSOC: pre-update (OB_step.m:226-227)
   double cellSOC = (SOCnAvg - r.th0n) / (r.th100n - r.th0n);
-  int iZu = 0, iZl = 0, iTu = 0, iTl = 0;
-  if (r.nZ > 1) {
-    int a, b;
-    two_nearest(Zp, r.nZ, cellSOC, a, b);
-    iZu = a > b ? a : b; iZl = a < b ? a : b;
-  }
-  if (r.nT > 1) {
-    int a, b;
-    two_nearest(Tp, r.nT, T, a, b);
-    iTu = a > b ? a : b; iTl = a < b ? a : b;
-  }
+  const PlantCorners pc = plant_corners(r, Tp, Zp, cellSOC, T);
   STAMPP(1);
-  // this lane's corner: mm = {Tl Zl, Tl Zu, Tu Zl, Tu Zu}[j]
-  const int mj = ((j & 2) ? iTu : iTl) * r.nZ + ((j & 1) ? iZu : iZl);
+  const int mj = corner_model(r, pc, j);  // this lane's corner
   double *bx = s.bigx + ((size_t)c * r.NM + mj) * 6;
   double xs[6];
-  {
-    const double2 *p = reinterpret_cast<const double2 *>(bx);
-    const double2 q0 = p[0], q1 = p[1], q2 = p[2];
-    xs[0] = q0.x; xs[1] = q0.y; xs[2] = q1.x; xs[3] = q1.y; xs[4] = q2.x; xs[5] = q2.y;
-  }
+  load_corner(bx, xs);
   const int tsj = lazy_t ? s.ts_plant[c * r.NM + mj] : 0;
   // the per-cell scalar chain runs while the corner gathers are in flight
-  const double Cdleffn = et.f(0, EF_CDL, SOC0n), Cdleffp = et.f(1, EF_CDL, SOC0p);  // OB_step.m:212-219
-  double dUn = et.f(0, EF_DU, SOCnAvg), dUp = et.f(1, EF_DU, SOCpAvg);
-  double dQn = fabs(r.th100n - r.th0n), dQp = fabs(r.th100p - r.th0p);
-  double res0n = -dQn / (3600 * r.Q - Cdleffn * dQn * dUn);
-  double res0p = dQp / (3600 * r.Q - Cdleffp * dQp * dUp);
-  SOCnAvg = SOCnAvg + res0n * Iapp * r.Ts;
-  SOCpAvg = SOCpAvg + res0p * Iapp * r.Ts;
-  if (SOCnAvg < 0) SOCnAvg = 0;
-  if (SOCnAvg > 1) SOCnAvg = 1;
-  if (SOCpAvg < 0) SOCpAvg = 0;
-  if (SOCpAvg > 1) SOCpAvg = 1;
-  const double Zu = Zp[iZu], Zl = Zp[iZl], Tu = Tp[iTu], Tl = Tp[iTl];
-  double aZ = 0.0, aT = 0.0;
-  if (Zu != Zl) aZ = (cellSOC - Zl) / (Zu - Zl);
-  if (Tu != Tl) aT = (T - Tl) / (Tu - Tl);
+  plant_soc_step(r, et, SOC0n, SOC0p, Iapp, SOCnAvg, SOCpAvg);
+  double aZ, aT;
+  plant_weights(Tp, Zp, pc, cellSOC, T, aZ, aT);
   STAMPP(2);
   const double *a = L + mj * PREC + NPLANT * NX + 2 * NPLANT;
-  if (lazy_t)  // OB_step.m:198-200 for the skipped steps, RCH ring inputs per round trip
-    for (int k0 = tsj + 1; k0 < lazy_t; k0 += RCH) {
-      double u[RCH];
-      ring_chunk(s.hist_u, s, c, k0, lazy_t - 1, u);
-#pragma unroll
-      for (int i = 0; i < RCH; ++i)
-        if (k0 + i < lazy_t)
-#pragma unroll
-          for (int e = 0; e < 6; ++e) xs[e] = __builtin_fma(a[e], xs[e], u[i]);
-    }
+  if (lazy_t) plant_replay<true>(xs, a, s, c, tsj, lazy_t);
   STAMPP(3);
   const double *B = L + mj * PREC;
   double yk[NPLANT];
 #pragma unroll
   for (int q = 0; q < NPLANT; ++q) {
-    double acc = 0.0;
-#pragma unroll
-    for (int k = 0; k < NX; ++k) acc = acc + B[q * NX + k] * xs[k];
-    acc = acc + B[NPLANT * NX + q] * xs[5];
-    const double y = acc + B[NPLANT * NX + NPLANT + q] * Iapp;
-    const double y0 = qbc<0>(y), y1 = qbc<1>(y), y2 = qbc<2>(y), y3 = qbc<3>(y);
-    yk[q] = (1 - aT) * ((1 - aZ) * y0 + aZ * y1) + aT * ((1 - aZ) * y2 + aZ * y3);
+    yk[q] = quad_blend(plant_row(B + q * NX, B[NPLANT * NX + q], B[NPLANT * NX + NPLANT + q], xs, Iapp), aZ, aT);
     __builtin_amdgcn_sched_barrier(0);  // one row's LDS operands at a time: 128 VGPRs at 4 waves/SIMD
   }
   STAMPP(4);
-  double th0 = fmin(fmax(yk[R_TH0] + SOC0n, 1e-6), 1 - 1e-6);
-  double th3 = fmin(fmax(yk[R_TH3] + SOC0p, 1e-6), 1 - 1e-6);
-  double te1 = fmax(yk[R_TE1] + 1, 1e-6);
-  double teE = fmax(yk[R_TEE] + 1, 1e-6);
-  double i0n = et.f(0, EF_K0, negSOC) * sqrt(te1 * (1 - th0) * th0);  // OB_step.m:329-332
-  double i0p = et.f(1, EF_K0, posSOC) * sqrt(teE * (1 - th3) * th3);
-  double negEta0 = 2 * r.R * T / r.F * dasinh(yk[R_IF0] / (2 * i0n));
-  double posEta3 = 2 * r.R * T / r.F * dasinh(yk[R_IF3] / (2 * i0p));
-  double Uocpn0 = et.f(0, EF_U, th0), Uocpp3 = et.f(1, EF_U, th3);
-  const double Rfn = et.f(0, EF_RF, negSOC), Rfp = et.f(1, EF_RF, posSOC);  // OB_step.m:339-340
-  double V = posEta3 - negEta0 + yk[R_PHIE] + Uocpp3 - Uocpn0 + (Rfp * yk[R_IFDL3] - Rfn * yk[R_IFDL0]);
-  V = V - r.Rc * Iapp;
+  const double V = plant_vcell(r, et, yk, T, Iapp, negSOC, posSOC, SOC0n, SOC0p);
   STAMPP(5);
   if (j == 0) {
     s.SOCn[c] = SOCnAvg;
@@ -1875,13 +1818,9 @@ __global__ void __launch_bounds__(PLANT4_BLOCK) k_plant4(const KRom r, const KSt
   // advance this corner through step t in place (eager mode: k_bulk does all models); a
   // duplicate corner (single-set-point grids) is written by two lanes with the same bits
   if (lazy_t && tsj < lazy_t) {
-    double2 *p = reinterpret_cast<double2 *>(bx);
     double x[6];
-#pragma unroll
-    for (int e = 0; e < 6; ++e) x[e] = __builtin_fma(a[e], xs[e], Iapp);
-    p[0] = make_double2(x[0], x[1]);
-    p[1] = make_double2(x[2], x[3]);
-    p[2] = make_double2(x[4], x[5]);
+    plant_advance<true>(a, xs, Iapp, x);
+    store_corner(bx, x);
     s.ts_plant[c * r.NM + mj] = lazy_t;
   }
   STAMPP(6);
@@ -1892,7 +1831,7 @@ __global__ void __launch_bounds__(PLANT4_BLOCK) k_plant4(const KRom r, const KSt
 // (mpcekf_plant_step_obs), a lane quad per cell as k_plant4.  It is launched BEFORE the
 // call's k_plant4 / k_bulk and only reads the plant state (SOCn/SOCp, bigx at step t-1), so
 // Vcell and the state the call leaves are k_plant4's own; this kernel recomputes Vcell with
-// k_plant4's expressions (the same bits) for posPhis and the record's Vcell slot.
+// the shared plant helpers (the same bits) for posPhis and the record's Vcell slot.
 // The obs blob (host build_rom) holds, per model, all nz rows in the permuted order as
 // [C 5][res0][D][0] -- res0 zeroed on the Phise rows, OB_step.m:178-181 -- then the plant
 // blob's tables.  Pass 1 forms role rows 0..R_PHISE0 (unrolled, registers) for Vcell and
@@ -1900,21 +1839,56 @@ __global__ void __launch_bounds__(PLANT4_BLOCK) k_plant4(const KRom r, const KSt
 // its one or two record slots, all from the row's uniform descriptor word.  The record is
 // slot-major [nobs][n]; lane j of the quad stores the slots = j (mod 4).
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ double obs_row(const double *B, const double xs[6], double Iapp) {
-  const double2 *p = reinterpret_cast<const double2 *>(B);
-  const double2 c01 = p[0], c23 = p[1], c4r = p[2], d = p[3];
-  double acc = 0.0;
-  acc = acc + c01.x * xs[0];
-  acc = acc + c01.y * xs[1];
-  acc = acc + c23.x * xs[2];
-  acc = acc + c23.y * xs[3];
-  acc = acc + c4r.x * xs[4];
-  acc = acc + c4r.y * xs[5];
-  return acc + d.x * Iapp;
+// The prologue of the two obs kernels.  obs_stage: the block's obs blob in LDS (GR: tables
+// only, model rows from the global blob).  obs_cell: lane j's view of cell c at temperature T,
+// from the pre-update averages through the blend weights; *tsj, where asked for, is the step
+// the corner's stored state is current through.
+struct ObsBlob {
+  const double *tb, *L, *Tp, *Zp;
+};
+template <bool GR>
+__device__ __forceinline__ ObsBlob obs_stage(const KObs &o, double *lds) {
+  const int lo = GR ? o.tab : 0;
+  stage_lds(lds, o.blob + lo, o.len - lo);
+  __syncthreads();
+  const double *tb = lds - lo;
+  const double *Tp = tb + o.tab + o.tablen;
+  return {tb, GR ? o.blob : lds, Tp, Tp + MAXT};
 }
-__device__ __forceinline__ double quad_blend(double y, double aZ, double aT) {  // OB_step.m:285
-  const double y0 = qbc<0>(y), y1 = qbc<1>(y), y2 = qbc<2>(y), y3 = qbc<3>(y);
-  return (1 - aT) * ((1 - aZ) * y0 + aZ * y1) + aT * ((1 - aZ) * y2 + aZ * y3);
+struct ObsCell {
+  double negSOC, posSOC, SOC0n, SOC0p, cellSOC, aZ, aT;
+  ETab et;
+  double xs[6];     // lane j's corner state
+  const double *B;  // and its rows of the obs blob
+  int mj;
+};
+template <bool PL>
+__device__ __forceinline__ void obs_cell(const KRom &r, const KState &s, const KObs &o, const ObsBlob &ob, int64_t c,
+                                         int j, double T, ObsCell &k, int *tsj = nullptr) {
+  k.negSOC = s.SOCn[c], k.posSOC = s.SOCp[c];  // OB_step.m:226-227
+  k.SOC0n = s.SOC0n[c], k.SOC0p = s.SOC0p[c];
+  k.et = etab<PL>(r, ob.tb + o.tab, T);
+  k.cellSOC = (k.negSOC - r.th0n) / (r.th100n - r.th0n);  // OB_step.m:228
+  const PlantCorners pc = plant_corners(r, ob.Tp, ob.Zp, k.cellSOC, T);
+  k.mj = corner_model(r, pc, j);
+  load_corner(s.bigx + ((size_t)c * r.NM + k.mj) * 6, k.xs);
+  if (tsj) *tsj = s.ts_plant[c * r.NM + k.mj];
+  plant_weights(ob.Tp, ob.Zp, pc, k.cellSOC, T, k.aZ, k.aT);
+  k.B = ob.L + (size_t)k.mj * o.stride;
+}
+// a blended row's correction by its OBS_* kind (OB_step.m:302-326, 348)
+__device__ __forceinline__ double obs_correct(int kind, double v, const ObsCell &k, double UocpnAvg, double UocppAvg,
+                                              double negPhise0, double V) {
+  switch (kind) {
+    case OBS_NTHSS: return fmin(fmax(v + k.SOC0n, 1e-6), 1 - 1e-6);  // OB_step.m:302-310
+    case OBS_PTHSS: return fmin(fmax(v + k.SOC0p, 1e-6), 1 - 1e-6);
+    case OBS_NPHISE: return v + UocpnAvg;                            // OB_step.m:315-317
+    case OBS_PPHISE: return v + UocppAvg;
+    case OBS_PHIE: return v - negPhise0;                             // OB_step.m:322
+    case OBS_THETAE: return fmax(v + 1, 1e-6);                       // OB_step.m:325-326
+    case OBS_PPHIS: return v + V;                                    // OB_step.m:348
+    default: return v;
+  }
 }
 constexpr int OBS_BLOCK = 512;  // 256 VGPRs a lane: no scratch (at 1024 / 128 the quintic lookups spilled)
 template <bool GR, bool PL>
@@ -1924,13 +1898,7 @@ __global__ void __launch_bounds__(OBS_BLOCK) k_plant_obs(const KRom r, const KSt
   const int64_t gt = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int j = (int)(gt & 3);
   const int64_t c = gt >> 2;  // a quad is one cell: every exit below is quad-uniform
-  const int lo = GR ? o.tab : 0;
-  stage_lds(lds, o.blob + lo, o.len - lo);
-  __syncthreads();
-  const double *tb = lds - lo;
-  const double *L = GR ? o.blob : lds;
-  const double *Tp = tb + o.tab + o.tablen;
-  const double *Zp = Tp + MAXT;
+  const ObsBlob ob = obs_stage<GR>(o, lds);
   if (c >= s.n) return;
   const size_t n = (size_t)s.n;
   double *rec = o.rec + c;
@@ -1943,75 +1911,30 @@ __global__ void __launch_bounds__(OBS_BLOCK) k_plant_obs(const KRom r, const KSt
   }
   const double Iapp = iapp[c];
   const double T = s.Tc[c] + 273.15;  // OB_step.m:75
-  const double negSOC = s.SOCn[c], posSOC = s.SOCp[c];  // OB_step.m:226-227
-  const double SOC0n = s.SOC0n[c], SOC0p = s.SOC0p[c];
-  const ETab et = etab<PL>(r, tb + o.tab, T);
-  const double cellSOC = (negSOC - r.th0n) / (r.th100n - r.th0n);  // OB_step.m:228
-  int iZu = 0, iZl = 0, iTu = 0, iTl = 0;
-  if (r.nZ > 1) {
-    int a, b;
-    two_nearest(Zp, r.nZ, cellSOC, a, b);
-    iZu = a > b ? a : b; iZl = a < b ? a : b;
-  }
-  if (r.nT > 1) {
-    int a, b;
-    two_nearest(Tp, r.nT, T, a, b);
-    iTu = a > b ? a : b; iTl = a < b ? a : b;
-  }
-  const int mj = ((j & 2) ? iTu : iTl) * r.nZ + ((j & 1) ? iZu : iZl);
-  double xs[6];
-  {
-    const double2 *p = reinterpret_cast<const double2 *>(s.bigx + ((size_t)c * r.NM + mj) * 6);
-    const double2 q0 = p[0], q1 = p[1], q2 = p[2];
-    xs[0] = q0.x; xs[1] = q0.y; xs[2] = q1.x; xs[3] = q1.y; xs[4] = q2.x; xs[5] = q2.y;
-  }
-  const double Zu = Zp[iZu], Zl = Zp[iZl], Tu = Tp[iTu], Tl = Tp[iTl];
-  double aZ = 0.0, aT = 0.0;
-  if (Zu != Zl) aZ = (cellSOC - Zl) / (Zu - Zl);
-  if (Tu != Tl) aT = (T - Tl) / (Tu - Tl);
-  const double *B = L + (size_t)mj * o.stride;
+  ObsCell k;
+  obs_cell<PL>(r, s, o, ob, c, j, T, k);
   double yk[R_PHISE0 + 1];
 #pragma unroll
   for (int q = 0; q <= R_PHISE0; ++q) {
-    yk[q] = quad_blend(obs_row(B + q * OBS_ROW, xs, Iapp), aZ, aT);
+    yk[q] = quad_blend(obs_row(k.B + q * OBS_ROW, k.xs, Iapp), k.aZ, k.aT);
     __builtin_amdgcn_sched_barrier(0);  // one row's operands at a time (k_plant4)
   }
-  const double th0 = fmin(fmax(yk[R_TH0] + SOC0n, 1e-6), 1 - 1e-6);
-  const double th3 = fmin(fmax(yk[R_TH3] + SOC0p, 1e-6), 1 - 1e-6);
-  const double te1 = fmax(yk[R_TE1] + 1, 1e-6);
-  const double teE = fmax(yk[R_TEE] + 1, 1e-6);
-  double i0n = et.f(0, EF_K0, negSOC) * sqrt(te1 * (1 - th0) * th0);  // OB_step.m:329-332
-  double i0p = et.f(1, EF_K0, posSOC) * sqrt(teE * (1 - th3) * th3);
-  double negEta0 = 2 * r.R * T / r.F * dasinh(yk[R_IF0] / (2 * i0n));
-  double posEta3 = 2 * r.R * T / r.F * dasinh(yk[R_IF3] / (2 * i0p));
-  double Uocpn0 = et.f(0, EF_U, th0), Uocpp3 = et.f(1, EF_U, th3);
-  const double Rfn = et.f(0, EF_RF, negSOC), Rfp = et.f(1, EF_RF, posSOC);  // OB_step.m:339-340
-  double V = posEta3 - negEta0 + yk[R_PHIE] + Uocpp3 - Uocpn0 + (Rfp * yk[R_IFDL3] - Rfn * yk[R_IFDL0]);
-  V = V - r.Rc * Iapp;
+  const double V = plant_vcell(r, k.et, yk, T, Iapp, k.negSOC, k.posSOC, k.SOC0n, k.SOC0p);
   __builtin_amdgcn_sched_barrier(0);  // Vcell's lookups done before the two of the averages start
-  const double UocpnAvg = et.f(0, EF_U, negSOC), UocppAvg = et.f(1, EF_U, posSOC);  // OB_step.m:313-314
-  const double negPhise0 = yk[R_PHISE0] + UocpnAvg;                                 // OB_step.m:317
+  const double UocpnAvg = k.et.f(0, EF_U, k.negSOC), UocppAvg = k.et.f(1, EF_U, k.posSOC);  // OB_step.m:313-314
+  const double negPhise0 = yk[R_PHISE0] + UocpnAvg;                                         // OB_step.m:317
   __builtin_amdgcn_sched_barrier(0);
-  put(OBS_S_NEGSOC, negSOC);
-  put(OBS_S_POSSOC, posSOC);
-  put(OBS_S_CELLSOC, cellSOC);
+  put(OBS_S_NEGSOC, k.negSOC);
+  put(OBS_S_POSSOC, k.posSOC);
+  put(OBS_S_CELLSOC, k.cellSOC);
   put(o.slot_phie0, -negPhise0);  // OB_step.m:321
   put(o.nobs - 1, V);             // OB_step.m:356
   for (int q = 0; q < r.nz; ++q) {
     const unsigned d = o.desc[q];
     const int kind = (int)(d & 15u), s1 = (int)(d >> 4 & 1023u) - 1, s2 = (int)(d >> 14 & 1023u) - 1;
     if (s1 < 0 && s2 < 0) continue;  // a Phie row at x = 0 (OB_step.m:151-155): in no field
-    double v = quad_blend(obs_row(B + q * OBS_ROW, xs, Iapp), aZ, aT);
-    switch (kind) {
-      case OBS_NTHSS: v = fmin(fmax(v + SOC0n, 1e-6), 1 - 1e-6); break;  // OB_step.m:302-310
-      case OBS_PTHSS: v = fmin(fmax(v + SOC0p, 1e-6), 1 - 1e-6); break;
-      case OBS_NPHISE: v = v + UocpnAvg; break;                          // OB_step.m:315-317
-      case OBS_PPHISE: v = v + UocppAvg; break;
-      case OBS_PHIE: v = v - negPhise0; break;                           // OB_step.m:322
-      case OBS_THETAE: v = fmax(v + 1, 1e-6); break;                     // OB_step.m:325-326
-      case OBS_PPHIS: v = v + V; break;                                  // OB_step.m:348
-      default: break;
-    }
+    const double v = obs_correct(kind, quad_blend(obs_row(k.B + q * OBS_ROW, k.xs, Iapp), k.aZ, k.aT), k, UocpnAvg,
+                                 UocppAvg, negPhise0, V);
     if (s1 >= 0) put(s1, v);
     if (s2 >= 0) put(s2, v);
   }
@@ -2041,13 +1964,7 @@ __global__ void __launch_bounds__(OBS_BLOCK) k_obs_traj(const KRom r, const KSta
   const int64_t gt = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int j = (int)(gt & 3);
   const int64_t c = gt >> 2;  // a quad is one cell: every exit below is quad-uniform
-  const int lo = GR ? o.tab : 0;
-  stage_lds(lds, o.blob + lo, o.len - lo);
-  __syncthreads();
-  const double *tb = lds - lo;
-  const double *L = GR ? o.blob : lds;
-  const double *Tp = tb + o.tab + o.tablen;
-  const double *Zp = Tp + MAXT;
+  const ObsBlob ob = obs_stage<GR>(o, lds);
   if (c >= s.n) return;
   const size_t n = (size_t)s.n;
   double *out = q.out + c;
@@ -2057,99 +1974,46 @@ __global__ void __launch_bounds__(OBS_BLOCK) k_obs_traj(const KRom r, const KSta
   }
   const double Iapp = s.uk[c];
   const double T = (tc_in ? tc_in[c] : s.Tc[c]) + 273.15;  // OB_step.m:75
-  const double negSOC = s.SOCn[c], posSOC = s.SOCp[c];      // OB_step.m:226-227
-  const double SOC0n = s.SOC0n[c], SOC0p = s.SOC0p[c];
-  const ETab et = etab<PL>(r, tb + o.tab, T);
-  const double cellSOC = (negSOC - r.th0n) / (r.th100n - r.th0n);  // OB_step.m:228
-  int iZu = 0, iZl = 0, iTu = 0, iTl = 0;
-  if (r.nZ > 1) {
-    int a, b;
-    two_nearest(Zp, r.nZ, cellSOC, a, b);
-    iZu = a > b ? a : b; iZl = a < b ? a : b;
-  }
-  if (r.nT > 1) {
-    int a, b;
-    two_nearest(Tp, r.nT, T, a, b);
-    iTu = a > b ? a : b; iTl = a < b ? a : b;
-  }
-  const int mj = ((j & 2) ? iTu : iTl) * r.nZ + ((j & 1) ? iZu : iZl);
-  double xs[6];
-  {
-    const double2 *p = reinterpret_cast<const double2 *>(s.bigx + ((size_t)c * r.NM + mj) * 6);
-    const double2 q0 = p[0], q1 = p[1], q2 = p[2];
-    xs[0] = q0.x; xs[1] = q0.y; xs[2] = q1.x; xs[3] = q1.y; xs[4] = q2.x; xs[5] = q2.y;
-  }
-  const int tsj = s.ts_plant[c * r.NM + mj];
-  const double Zu = Zp[iZu], Zl = Zp[iZl], Tu = Tp[iTu], Tl = Tp[iTl];
-  double aZ = 0.0, aT = 0.0;
-  if (Zu != Zl) aZ = (cellSOC - Zl) / (Zu - Zl);
-  if (Tu != Tl) aT = (T - Tl) / (Tu - Tl);
-  if (tsj + 1 < lazy_t) {  // OB_step.m:198-200 for the skipped steps, RCH ring inputs per round trip
+  ObsCell k;
+  int tsj;
+  obs_cell<PL>(r, s, o, ob, c, j, T, k, &tsj);
+  if (tsj + 1 < lazy_t) {  // OB_step.m:198-200 for the skipped steps
     double a[6];
     {
-      const double *ap = r.plant_blob + (size_t)mj * PREC + NPLANT * NX + 2 * NPLANT;  // diag(A), a[5] = 1
+      const double *ap = r.plant_blob + (size_t)k.mj * PREC + NPLANT * NX + 2 * NPLANT;  // diag(A), a[5] = 1
 #pragma unroll
       for (int e = 0; e < 6; ++e) a[e] = ap[e];
     }
-    for (int k0 = tsj + 1; k0 < lazy_t; k0 += RCH) {
-      double u[RCH];
-      ring_chunk(s.hist_u, s, c, k0, lazy_t - 1, u);
-#pragma unroll
-      for (int i = 0; i < RCH; ++i)
-        if (k0 + i < lazy_t)
-#pragma unroll
-          for (int e = 0; e < 6; ++e) xs[e] = __builtin_fma(a[e], xs[e], u[i]);
-    }
+    plant_replay<true>(k.xs, a, s, c, tsj, lazy_t);
   }
-  const double *B = L + (size_t)mj * o.stride;
   double V = 0.0, UocpnAvg = 0.0, UocppAvg = 0.0, negPhise0 = 0.0;
   if (q.need & OBS_NEED_V) {  // the Vcell chain of k_plant4 / k_plant_obs
     double yk[R_PHIE + 1];
 #pragma unroll
     for (int i = 0; i <= R_PHIE; ++i) {
-      yk[i] = quad_blend(obs_row(B + i * OBS_ROW, xs, Iapp), aZ, aT);
+      yk[i] = quad_blend(obs_row(k.B + i * OBS_ROW, k.xs, Iapp), k.aZ, k.aT);
       __builtin_amdgcn_sched_barrier(0);  // one row's operands at a time (k_plant4)
     }
-    const double th0 = fmin(fmax(yk[R_TH0] + SOC0n, 1e-6), 1 - 1e-6);
-    const double th3 = fmin(fmax(yk[R_TH3] + SOC0p, 1e-6), 1 - 1e-6);
-    const double te1 = fmax(yk[R_TE1] + 1, 1e-6);
-    const double teE = fmax(yk[R_TEE] + 1, 1e-6);
-    double i0n = et.f(0, EF_K0, negSOC) * sqrt(te1 * (1 - th0) * th0);  // OB_step.m:329-332
-    double i0p = et.f(1, EF_K0, posSOC) * sqrt(teE * (1 - th3) * th3);
-    double negEta0 = 2 * r.R * T / r.F * dasinh(yk[R_IF0] / (2 * i0n));
-    double posEta3 = 2 * r.R * T / r.F * dasinh(yk[R_IF3] / (2 * i0p));
-    double Uocpn0 = et.f(0, EF_U, th0), Uocpp3 = et.f(1, EF_U, th3);
-    const double Rfn = et.f(0, EF_RF, negSOC), Rfp = et.f(1, EF_RF, posSOC);  // OB_step.m:339-340
-    V = posEta3 - negEta0 + yk[R_PHIE] + Uocpp3 - Uocpn0 + (Rfp * yk[R_IFDL3] - Rfn * yk[R_IFDL0]);
-    V = V - r.Rc * Iapp;
+    V = plant_vcell(r, k.et, yk, T, Iapp, k.negSOC, k.posSOC, k.SOC0n, k.SOC0p);
     __builtin_amdgcn_sched_barrier(0);
   }
   if (q.need & OBS_NEED_UN) {  // OB_step.m:313,317
-    UocpnAvg = et.f(0, EF_U, negSOC);
-    negPhise0 = quad_blend(obs_row(B + R_PHISE0 * OBS_ROW, xs, Iapp), aZ, aT) + UocpnAvg;
+    UocpnAvg = k.et.f(0, EF_U, k.negSOC);
+    negPhise0 = quad_blend(obs_row(k.B + R_PHISE0 * OBS_ROW, k.xs, Iapp), k.aZ, k.aT) + UocpnAvg;
     __builtin_amdgcn_sched_barrier(0);
   }
   if (q.need & OBS_NEED_UP) {  // OB_step.m:314
-    UocppAvg = et.f(1, EF_U, posSOC);
+    UocppAvg = k.et.f(1, EF_U, k.posSOC);
     __builtin_amdgcn_sched_barrier(0);
   }
   for (int p = 0; p < q.nsel; ++p) {
     const int src = q.plan[p];  // wave-uniform
     double v;
     if (src >= 0) {
-      v = quad_blend(obs_row(B + src * OBS_ROW, xs, Iapp), aZ, aT);
-      switch ((int)(o.desc[src] & 15u)) {
-        case OBS_NTHSS: v = fmin(fmax(v + SOC0n, 1e-6), 1 - 1e-6); break;  // OB_step.m:302-310
-        case OBS_PTHSS: v = fmin(fmax(v + SOC0p, 1e-6), 1 - 1e-6); break;
-        case OBS_NPHISE: v = v + UocpnAvg; break;                          // OB_step.m:315-317
-        case OBS_PPHISE: v = v + UocppAvg; break;
-        case OBS_PHIE: v = v - negPhise0; break;                           // OB_step.m:322
-        case OBS_THETAE: v = fmax(v + 1, 1e-6); break;                     // OB_step.m:325-326
-        case OBS_PPHIS: v = v + V; break;                                  // OB_step.m:348
-        default: break;
-      }
+      v = obs_correct((int)(o.desc[src] & 15u), quad_blend(obs_row(k.B + src * OBS_ROW, k.xs, Iapp), k.aZ, k.aT), k,
+                      UocpnAvg, UocppAvg, negPhise0, V);
     } else {
-      v = src == OBS_SRC_NEGSOC ? negSOC : src == OBS_SRC_POSSOC ? posSOC : src == OBS_SRC_CELLSOC ? cellSOC
+      v = src == OBS_SRC_NEGSOC ? k.negSOC : src == OBS_SRC_POSSOC ? k.posSOC : src == OBS_SRC_CELLSOC ? k.cellSOC
           : src == OBS_SRC_PHIE0 ? -negPhise0 : V;  // OB_step.m:226-228, 321, 356
     }
     if ((p & 3) == j) out[(size_t)p * n] = v;
@@ -2688,18 +2552,15 @@ __device__ __forceinline__ void plant_store(const KRom &r, const KState &s, int6
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     if (!o.adv[j]) continue;
-    double2 *p = reinterpret_cast<double2 *>(bx + (size_t)o.mm[j] * 6);
-    p[0] = make_double2(o.x[j][0], o.x[j][1]);
-    p[1] = make_double2(o.x[j][2], o.x[j][3]);
-    p[2] = make_double2(o.x[j][4], o.x[j][5]);
+    store_corner(bx + (size_t)o.mm[j] * 6, o.x[j]);
     s.ts_plant[c * r.NM + o.mm[j]] = lazy_t;
   }
 }
 // OB_step's simStep (OB_step.m:188-357) for one cell at the start of k_cell's fused step:
-// k_plant's arithmetic, read from the cell blob (the plant's 9 role rows are the blob's
+// the shared plant helpers, read from the cell blob (the plant's 9 role rows are the blob's
 // first C rows, D at nzp*5, diag(A) after them -- the integrator's a = 1 exactly, checked
 // by build_rom -- and the res0 column after the Sigma coefficients).  Returns Vcell; the
-// plant state, averages, ring inputs and timestamps are stored as k_plant stores them.
+// plant state, averages, ring inputs and timestamps are stored as k_plant4 stores them.
 // (ring_p / po: the ring input and the state stores handed back for the caller to issue
 // after its last load, MPCEKF_RING_LATE / MPCEKF_PLANT_STORE_LATE.)
 template <int NZ, bool PL>
@@ -2724,57 +2585,23 @@ __device__ __forceinline__ double cell_plant(const KRom &r, const KState &s, con
   const double SOC0n = s.SOC0n[c], SOC0p = s.SOC0p[c];
   const double negSOC = SOCnAvg, posSOC = SOCpAvg;  // obs.negSOC / posSOC: pre-update (OB_step.m:226-227)
   double cellSOC = (SOCnAvg - r.th0n) / (r.th100n - r.th0n);
-  int iZu = 0, iZl = 0, iTu = 0, iTl = 0;
-  if (r.nZ > 1) {
-    int a, b;
-    two_nearest(Zp, r.nZ, cellSOC, a, b);
-    iZu = a > b ? a : b; iZl = a < b ? a : b;
-  }
-  if (r.nT > 1) {
-    int a, b;
-    two_nearest(Tp, r.nT, T, a, b);
-    iTu = a > b ? a : b; iTl = a < b ? a : b;
-  }
-  const int mm[4] = {iTl * r.nZ + iZl, iTl * r.nZ + iZu, iTu * r.nZ + iZl, iTu * r.nZ + iZu};
+  const PlantCorners pc = plant_corners(r, Tp, Zp, cellSOC, T);
+  int mm[4];
+  corner_models(r, pc, mm);
   double *bx = s.bigx + (size_t)c * r.NM * 6;
   // the 4 corner states as of step t-1: all loads before any store (duplicate corners)
   double xs[4][6];
   int tsj[4] = {0, 0, 0, 0};
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    const double2 *p = reinterpret_cast<const double2 *>(bx + (size_t)mm[j] * 6);
-    const double2 q0 = p[0], q1 = p[1], q2 = p[2];
-    xs[j][0] = q0.x; xs[j][1] = q0.y; xs[j][2] = q1.x; xs[j][3] = q1.y; xs[j][4] = q2.x; xs[j][5] = q2.y;
+    load_corner(bx + (size_t)mm[j] * 6, xs[j]);
     if (lazy_t) tsj[j] = s.ts_plant[c * r.NM + mm[j]];
   }
   // the per-cell scalar chain while the corner gathers are in flight
-  const double Cdleffn = et.f(0, EF_CDL, SOC0n), Cdleffp = et.f(1, EF_CDL, SOC0p);  // OB_step.m:212-219
-  double dUn = et.f(0, EF_DU, SOCnAvg), dUp = et.f(1, EF_DU, SOCpAvg);
-  double dQn = fabs(r.th100n - r.th0n), dQp = fabs(r.th100p - r.th0p);
-  double res0n = -dQn / (3600 * r.Q - Cdleffn * dQn * dUn);
-  double res0p = dQp / (3600 * r.Q - Cdleffp * dQp * dUp);
-  SOCnAvg = SOCnAvg + res0n * Iapp * r.Ts;
-  SOCpAvg = SOCpAvg + res0p * Iapp * r.Ts;
-  if (SOCnAvg < 0) SOCnAvg = 0;
-  if (SOCnAvg > 1) SOCnAvg = 1;
-  if (SOCpAvg < 0) SOCpAvg = 0;
-  if (SOCpAvg > 1) SOCpAvg = 1;
+  plant_soc_step(r, et, SOC0n, SOC0p, Iapp, SOCnAvg, SOCpAvg);
   if (lazy_t) {
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {  // OB_step.m:198-200 for the skipped steps, RCH inputs per round trip
-      const double *a = L + mm[j] * stride + OA;
-      for (int k0 = tsj[j] + 1; k0 < lazy_t; k0 += RCH) {
-        double u[RCH];
-        ring_chunk(s.hist_u, s, c, k0, lazy_t - 1, u);
-#pragma unroll
-        for (int i = 0; i < RCH; ++i)
-          if (k0 + i < lazy_t) {
-#pragma unroll
-            for (int e = 0; e < NX; ++e) xs[j][e] = __builtin_fma(a[e], xs[j][e], u[i]);
-            xs[j][NX] = __builtin_fma(1.0, xs[j][NX], u[i]);  // the integrator: a = 1
-          }
-      }
-    }
+    for (int j = 0; j < 4; ++j) plant_replay<false>(xs[j], L + mm[j] * stride + OA, s, c, tsj[j], lazy_t);
   }
   double y[4][NPLANT];
 #pragma unroll
@@ -2782,35 +2609,17 @@ __device__ __forceinline__ double cell_plant(const KRom &r, const KState &s, con
     const double *B = L + mm[j] * stride;
 #pragma unroll
     for (int q = 0; q < NPLANT; ++q) {
-      double acc = 0.0;
-#pragma unroll
-      for (int k = 0; k < NX; ++k) acc = acc + B[q * NX + k] * xs[j][k];
-      acc = acc + B[OR0 + q] * xs[j][5];
-      y[j][q] = acc + B[OD + q] * Iapp;
+      y[j][q] = plant_row(B + q * NX, B[OR0 + q], B[OD + q], xs[j], Iapp);
       launder(y[j][q]);
     }
     __builtin_amdgcn_sched_barrier(0);
   }
-  const double Zu = Zp[iZu], Zl = Zp[iZl], Tu = Tp[iTu], Tl = Tp[iTl];
-  double aZ = 0.0, aT = 0.0;
-  if (Zu != Zl) aZ = (cellSOC - Zl) / (Zu - Zl);
-  if (Tu != Tl) aT = (T - Tl) / (Tu - Tl);
+  double aZ, aT;
+  plant_weights(Tp, Zp, pc, cellSOC, T, aZ, aT);
   double yk[NPLANT];
 #pragma unroll
-  for (int q = 0; q < NPLANT; ++q)
-    yk[q] = (1 - aT) * ((1 - aZ) * y[0][q] + aZ * y[1][q]) + aT * ((1 - aZ) * y[2][q] + aZ * y[3][q]);
-  double th0 = fmin(fmax(yk[R_TH0] + SOC0n, 1e-6), 1 - 1e-6);
-  double th3 = fmin(fmax(yk[R_TH3] + SOC0p, 1e-6), 1 - 1e-6);
-  double te1 = fmax(yk[R_TE1] + 1, 1e-6);
-  double teE = fmax(yk[R_TEE] + 1, 1e-6);
-  double i0n = et.f(0, EF_K0, negSOC) * sqrt(te1 * (1 - th0) * th0);  // OB_step.m:329-332
-  double i0p = et.f(1, EF_K0, posSOC) * sqrt(teE * (1 - th3) * th3);
-  double negEta0 = 2 * r.R * T / r.F * dasinh(yk[R_IF0] / (2 * i0n));
-  double posEta3 = 2 * r.R * T / r.F * dasinh(yk[R_IF3] / (2 * i0p));
-  double Uocpn0 = et.f(0, EF_U, th0), Uocpp3 = et.f(1, EF_U, th3);
-  const double Rfn = et.f(0, EF_RF, negSOC), Rfp = et.f(1, EF_RF, posSOC);  // OB_step.m:339-340
-  double V = posEta3 - negEta0 + yk[R_PHIE] + Uocpp3 - Uocpn0 + (Rfp * yk[R_IFDL3] - Rfn * yk[R_IFDL0]);
-  V = V - r.Rc * Iapp;
+  for (int q = 0; q < NPLANT; ++q) yk[q] = blend4(y[0][q], y[1][q], y[2][q], y[3][q], aZ, aT);
+  const double V = plant_vcell(r, et, yk, T, Iapp, negSOC, posSOC, SOC0n, SOC0p);
   if (po) {  // the caller stores them after its last load
     po->on = true;
     po->socn = SOCnAvg;
@@ -2819,10 +2628,7 @@ __device__ __forceinline__ double cell_plant(const KRom &r, const KState &s, con
     for (int j = 0; j < 4; ++j) {
       po->mm[j] = mm[j];
       po->adv[j] = lazy_t && tsj[j] < lazy_t;
-      const double *a = L + mm[j] * stride + OA;
-#pragma unroll
-      for (int e = 0; e < NX; ++e) po->x[j][e] = __builtin_fma(a[e], xs[j][e], Iapp);
-      po->x[j][NX] = __builtin_fma(1.0, xs[j][NX], Iapp);
+      plant_advance<false>(L + mm[j] * stride + OA, xs[j], Iapp, po->x[j]);
     }
     return V;
   }
@@ -2832,15 +2638,9 @@ __device__ __forceinline__ double cell_plant(const KRom &r, const KState &s, con
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       if (tsj[j] >= lazy_t) continue;
-      const double *a = L + mm[j] * stride + OA;
-      double2 *p = reinterpret_cast<double2 *>(bx + (size_t)mm[j] * 6);
       double x[6];
-#pragma unroll
-      for (int e = 0; e < NX; ++e) x[e] = __builtin_fma(a[e], xs[j][e], Iapp);
-      x[NX] = __builtin_fma(1.0, xs[j][NX], Iapp);
-      p[0] = make_double2(x[0], x[1]);
-      p[1] = make_double2(x[2], x[3]);
-      p[2] = make_double2(x[4], x[5]);
+      plant_advance<false>(L + mm[j] * stride + OA, xs[j], Iapp, x);
+      store_corner(bx + (size_t)mm[j] * 6, x);
       s.ts_plant[c * r.NM + mm[j]] = lazy_t;
     }
   }
@@ -2933,7 +2733,7 @@ __device__ __forceinline__ void hild_cell(const KCfg &cf, const KState &s, const
 template <int NZ, int PARTS, bool MB = false, bool GR = false, bool PL = false>
 __global__ void __launch_bounds__(256) k_cell(const KRom r, const KCfg cf, const KState s, const KIO io) {
   extern __shared__ double lds[];
-  const int lo = GR ? r.cell_tab : 0;  // GR: model rows from the global blob (k_plant)
+  const int lo = GR ? r.cell_tab : 0;  // GR: model rows from the global blob (k_plant4)
   stage_lds(lds, r.cell_blob + lo, r.cell_len - lo);
   __syncthreads();
   const double *tb = lds - lo;
@@ -3200,7 +3000,7 @@ __global__ void __launch_bounds__(256) k_cell(const KRom r, const KCfg cf, const
       else load_x(cc.erec + (size_t)xi.m[j] * REC, xr[j]);
       tsj[j] = t ? s.ts_ekf[c * r.NM + xi.m[j]] : 0;
     }
-    // step t's ring input: the plant stores this cell's priorI there (k_plant, or cell_plant
+    // step t's ring input: the plant stores this cell's priorI there (k_plant4, or cell_plant
     // below, which may not have run yet)
     const double pt = t ? (fplant ? s.priorI[c] : s.hist_p[(size_t)(t % LAZY_H) * s.n + c]) : 0.0;
     run_plant();  // the records above are in flight while the plant's chain runs
@@ -3496,7 +3296,8 @@ __global__ void __launch_bounds__(256) k_cell(const KRom r, const KCfg cf, const
 // broadcasts in the one-lane order; the per-cell scalar chain the same in all four lanes)
 // on cell_plant's cell-blob layout.  Every live lane stores the per-cell values (the same
 // bits), so each lane's later reads of them (the ring slot of this step) follow its own
-// store.  Returns Vcell in every lane of the quad; k_plant / cell_plant's bits.
+// store.  Returns Vcell in every lane of the quad: the shared plant helpers' expressions,
+// hence k_plant4's and cell_plant's bits.
 template <int NZ, bool PL>
 __device__ __forceinline__ double quad_plant(const KRom &r, const KState &s, const double *L, const double *tb,
                                              const double *Tp, const double *Zp, int64_t c, int j, bool live,
@@ -3515,92 +3316,31 @@ __device__ __forceinline__ double quad_plant(const KRom &r, const KState &s, con
   const double SOC0n = s.SOC0n[c], SOC0p = s.SOC0p[c];
   const double negSOC = SOCnAvg, posSOC = SOCpAvg;  // obs.negSOC / posSOC: pre-update (OB_step.m:226-227)
   double cellSOC = (SOCnAvg - r.th0n) / (r.th100n - r.th0n);
-  int iZu = 0, iZl = 0, iTu = 0, iTl = 0;
-  if (r.nZ > 1) {
-    int a, b;
-    two_nearest(Zp, r.nZ, cellSOC, a, b);
-    iZu = a > b ? a : b; iZl = a < b ? a : b;
-  }
-  if (r.nT > 1) {
-    int a, b;
-    two_nearest(Tp, r.nT, T, a, b);
-    iTu = a > b ? a : b; iTl = a < b ? a : b;
-  }
-  // this lane's corner: mm = {Tl Zl, Tl Zu, Tu Zl, Tu Zu}[j]
-  const int mj = ((j & 2) ? iTu : iTl) * r.nZ + ((j & 1) ? iZu : iZl);
+  const PlantCorners pc = plant_corners(r, Tp, Zp, cellSOC, T);
+  const int mj = corner_model(r, pc, j);  // this lane's corner
   double *bx = s.bigx + ((size_t)c * r.NM + mj) * 6;
   double xs[6];
-  {
-    const double2 *p = reinterpret_cast<const double2 *>(bx);
-    const double2 q0 = p[0], q1 = p[1], q2 = p[2];
-    xs[0] = q0.x; xs[1] = q0.y; xs[2] = q1.x; xs[3] = q1.y; xs[4] = q2.x; xs[5] = q2.y;
-  }
+  load_corner(bx, xs);
   const int tsj = lazy_t ? s.ts_plant[c * r.NM + mj] : 0;
-  const double Cdleffn = et.f(0, EF_CDL, SOC0n), Cdleffp = et.f(1, EF_CDL, SOC0p);  // OB_step.m:212-219
-  double dUn = et.f(0, EF_DU, SOCnAvg), dUp = et.f(1, EF_DU, SOCpAvg);
-  double dQn = fabs(r.th100n - r.th0n), dQp = fabs(r.th100p - r.th0p);
-  double res0n = -dQn / (3600 * r.Q - Cdleffn * dQn * dUn);
-  double res0p = dQp / (3600 * r.Q - Cdleffp * dQp * dUp);
-  SOCnAvg = SOCnAvg + res0n * Iapp * r.Ts;
-  SOCpAvg = SOCpAvg + res0p * Iapp * r.Ts;
-  if (SOCnAvg < 0) SOCnAvg = 0;
-  if (SOCnAvg > 1) SOCnAvg = 1;
-  if (SOCpAvg < 0) SOCpAvg = 0;
-  if (SOCpAvg > 1) SOCpAvg = 1;
-  const double Zu = Zp[iZu], Zl = Zp[iZl], Tu = Tp[iTu], Tl = Tp[iTl];
-  double aZ = 0.0, aT = 0.0;
-  if (Zu != Zl) aZ = (cellSOC - Zl) / (Zu - Zl);
-  if (Tu != Tl) aT = (T - Tl) / (Tu - Tl);
+  plant_soc_step(r, et, SOC0n, SOC0p, Iapp, SOCnAvg, SOCpAvg);
+  double aZ, aT;
+  plant_weights(Tp, Zp, pc, cellSOC, T, aZ, aT);
   const double *a = L + mj * stride + OA;
-  if (lazy_t)  // OB_step.m:198-200 for the skipped steps, RCH ring inputs per round trip
-    for (int k0 = tsj + 1; k0 < lazy_t; k0 += RCH) {
-      double u[RCH];
-      ring_chunk(s.hist_u, s, c, k0, lazy_t - 1, u);
-#pragma unroll
-      for (int i = 0; i < RCH; ++i)
-        if (k0 + i < lazy_t) {
-#pragma unroll
-          for (int e = 0; e < NX; ++e) xs[e] = __builtin_fma(a[e], xs[e], u[i]);
-          xs[NX] = __builtin_fma(1.0, xs[NX], u[i]);  // the integrator: a = 1
-        }
-    }
+  if (lazy_t) plant_replay<false>(xs, a, s, c, tsj, lazy_t);
   const double *B = L + mj * stride;
   double yk[NPLANT];
 #pragma unroll
-  for (int q = 0; q < NPLANT; ++q) {
-    double acc = 0.0;
-#pragma unroll
-    for (int k = 0; k < NX; ++k) acc = acc + B[q * NX + k] * xs[k];
-    acc = acc + B[OR0 + q] * xs[5];
-    const double y = acc + B[OD + q] * Iapp;
-    const double y0 = qbc<0>(y), y1 = qbc<1>(y), y2 = qbc<2>(y), y3 = qbc<3>(y);
-    yk[q] = (1 - aT) * ((1 - aZ) * y0 + aZ * y1) + aT * ((1 - aZ) * y2 + aZ * y3);
-  }
-  double th0 = fmin(fmax(yk[R_TH0] + SOC0n, 1e-6), 1 - 1e-6);
-  double th3 = fmin(fmax(yk[R_TH3] + SOC0p, 1e-6), 1 - 1e-6);
-  double te1 = fmax(yk[R_TE1] + 1, 1e-6);
-  double teE = fmax(yk[R_TEE] + 1, 1e-6);
-  double i0n = et.f(0, EF_K0, negSOC) * sqrt(te1 * (1 - th0) * th0);  // OB_step.m:329-332
-  double i0p = et.f(1, EF_K0, posSOC) * sqrt(teE * (1 - th3) * th3);
-  double negEta0 = 2 * r.R * T / r.F * dasinh(yk[R_IF0] / (2 * i0n));
-  double posEta3 = 2 * r.R * T / r.F * dasinh(yk[R_IF3] / (2 * i0p));
-  double Uocpn0 = et.f(0, EF_U, th0), Uocpp3 = et.f(1, EF_U, th3);
-  const double Rfn = et.f(0, EF_RF, negSOC), Rfp = et.f(1, EF_RF, posSOC);  // OB_step.m:339-340
-  double V = posEta3 - negEta0 + yk[R_PHIE] + Uocpp3 - Uocpn0 + (Rfp * yk[R_IFDL3] - Rfn * yk[R_IFDL0]);
-  V = V - r.Rc * Iapp;
+  for (int q = 0; q < NPLANT; ++q)
+    yk[q] = quad_blend(plant_row(B + q * NX, B[OR0 + q], B[OD + q], xs, Iapp), aZ, aT);
+  const double V = plant_vcell(r, et, yk, T, Iapp, negSOC, posSOC, SOC0n, SOC0p);
   if (live) {
     s.SOCn[c] = SOCnAvg;
     s.SOCp[c] = SOCpAvg;
   }
   if (live && lazy_t && tsj < lazy_t) {  // advance this corner through step t in place
-    double2 *p = reinterpret_cast<double2 *>(bx);
     double x[6];
-#pragma unroll
-    for (int e = 0; e < NX; ++e) x[e] = __builtin_fma(a[e], xs[e], Iapp);
-    x[NX] = __builtin_fma(1.0, xs[NX], Iapp);
-    p[0] = make_double2(x[0], x[1]);
-    p[1] = make_double2(x[2], x[3]);
-    p[2] = make_double2(x[4], x[5]);
+    plant_advance<false>(a, xs, Iapp, x);
+    store_corner(bx, x);
     s.ts_plant[c * r.NM + mj] = lazy_t;
   }
   return V;
@@ -3619,7 +3359,7 @@ __device__ __forceinline__ double quad_plant(const KRom &r, const KState &s, con
 template <int NZ, int BLOCK, bool GR, bool PL>
 __global__ void __launch_bounds__(BLOCK) k_ekf4(const KRom r, const KCfg cf, const KState s, const KIO io) {
   extern __shared__ double lds[];
-  const int lo = GR ? r.cell_tab : 0;  // GR: model rows from the global blob (k_plant)
+  const int lo = GR ? r.cell_tab : 0;  // GR: model rows from the global blob (k_plant4)
   stage_lds(lds, r.cell_blob + lo, r.cell_len - lo);
   __syncthreads();
   const double *tb = lds - lo;
@@ -4496,35 +4236,42 @@ int plant_lds_bytes(const KRom &r) {
 
 bool cell_kernel_supported(int nzp) { return nzp == 26 || nzp == 32; }
 
+// The <GR, PL> of a launch, handed to f as two std::bool_constant values.  GR: the model rows
+// are read from the global blob (only the tables staged in LDS); PL: the ABI v3 polynomial
+// tables.
+template <class F>
+static void with_gr_pl(bool global, bool poly, F &&f) {
+  using Y = std::true_type;
+  using N = std::false_type;
+  if (poly) {
+    if (global) f(Y{}, Y{});
+    else f(N{}, Y{});
+  } else {
+    if (global) f(Y{}, N{});
+    else f(N{}, N{});
+  }
+}
+
 int launch_plant(const KRom &r, const KState &s, const double *iapp, double *vout, int lazy_t, const double *tc_in,
                  void *stream) {
   if (s.n == 0) return 0;
   const hipStream_t st = (hipStream_t)stream;
   const int lds = plant_lds_bytes(r);
-  if (MPCEKF_PLANT_QUAD) {
-    const int block = spread_block(s.n, 4, PLANT4_BLOCK);
-    const dim3 g(grid_for(4 * s.n, block)), b(block);
-    if (r.npoly) {
-      if (r.rom_global) hipLaunchKernelGGL((k_plant4<true, true>), g, b, lds, st, r, s, iapp, vout, lazy_t, tc_in);
-      else hipLaunchKernelGGL((k_plant4<false, true>), g, b, lds, st, r, s, iapp, vout, lazy_t, tc_in);
-    } else {
-      if (r.rom_global) hipLaunchKernelGGL((k_plant4<true, false>), g, b, lds, st, r, s, iapp, vout, lazy_t, tc_in);
-      else hipLaunchKernelGGL((k_plant4<false, false>), g, b, lds, st, r, s, iapp, vout, lazy_t, tc_in);
-    }
-    return (int)hipGetLastError();
-  }
-  const dim3 g(grid_for(s.n, 256)), b(256);
-  if (r.npoly) {
-    if (r.rom_global) hipLaunchKernelGGL((k_plant<true, true>), g, b, lds, st, r, s, iapp, vout, lazy_t, tc_in);
-    else hipLaunchKernelGGL((k_plant<false, true>), g, b, lds, st, r, s, iapp, vout, lazy_t, tc_in);
-  } else {
-    if (r.rom_global) hipLaunchKernelGGL((k_plant<true, false>), g, b, lds, st, r, s, iapp, vout, lazy_t, tc_in);
-    else hipLaunchKernelGGL((k_plant<false, false>), g, b, lds, st, r, s, iapp, vout, lazy_t, tc_in);
-  }
+  const int block = spread_block(s.n, 4, PLANT4_BLOCK);
+  const dim3 g(grid_for(4 * s.n, block)), b(block);
+  with_gr_pl(r.rom_global, r.npoly, [&](auto gr, auto pl) {
+    hipLaunchKernelGGL((k_plant4<decltype(gr)::value, decltype(pl)::value>), g, b, lds, st, r, s, iapp, vout, lazy_t,
+                       tc_in);
+  });
   return (int)hipGetLastError();
 }
 
 int obs_lds_bytes(const KObs &o) { return (int)((o.len - (o.global ? o.tab : 0) + 1) * sizeof(double)); }
+
+// dynamic LDS above the 64 KiB default (the obs blob: all nz rows of every model, from ~40 models)
+static void max_lds_attr(const void *kern) {
+  (void)hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+}
 
 int launch_plant_obs(const KRom &r, const KState &s, const KObs &o, const double *iapp, void *stream) {
   if (s.n == 0) return 0;
@@ -4532,17 +4279,11 @@ int launch_plant_obs(const KRom &r, const KState &s, const KObs &o, const double
   const int lds = obs_lds_bytes(o);
   const int block = spread_block(s.n, 4, OBS_BLOCK);
   const dim3 g(grid_for(4 * s.n, block)), b(block);
-  auto go = [&](auto kern) {  // all nz rows of every model: above the 64 KiB default from ~40 models
-    (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  with_gr_pl(o.global, r.npoly, [&](auto gr, auto pl) {
+    const auto kern = k_plant_obs<decltype(gr)::value, decltype(pl)::value>;
+    max_lds_attr((const void *)kern);
     hipLaunchKernelGGL(kern, g, b, lds, st, r, s, o, iapp);
-  };
-  if (r.npoly) {
-    if (o.global) go(k_plant_obs<true, true>);
-    else go(k_plant_obs<false, true>);
-  } else {
-    if (o.global) go(k_plant_obs<true, false>);
-    else go(k_plant_obs<false, false>);
-  }
+  });
   return (int)hipGetLastError();
 }
 
@@ -4553,17 +4294,11 @@ int launch_obs_traj(const KRom &r, const KState &s, const KObs &o, const KObsSel
   const int lds = obs_lds_bytes(o);
   const int block = spread_block(s.n, 4, OBS_BLOCK);
   const dim3 g(grid_for(4 * s.n, block)), b(block);
-  auto go = [&](auto kern) {  // k_plant_obs's blob: above the 64 KiB default from ~40 models
-    (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  with_gr_pl(o.global, r.npoly, [&](auto gr, auto pl) {
+    const auto kern = k_obs_traj<decltype(gr)::value, decltype(pl)::value>;
+    max_lds_attr((const void *)kern);
     hipLaunchKernelGGL(kern, g, b, lds, st, r, s, o, q, lazy_t, tc_in);
-  };
-  if (r.npoly) {
-    if (o.global) go(k_obs_traj<true, true>);
-    else go(k_obs_traj<false, true>);
-  } else {
-    if (o.global) go(k_obs_traj<true, false>);
-    else go(k_obs_traj<false, false>);
-  }
+  });
   return (int)hipGetLastError();
 }
 
@@ -4595,34 +4330,21 @@ int launch_bulk(const KRom &r, const KCfg &c, const KState &s, const double *iap
   return (int)hipGetLastError();
 }
 
-template <int NZ, int PARTS, bool MB, bool GR, bool PL>
-static void launch_cell_g(const KRom &r, const KCfg &c, const KState &s, const KIO &io, hipStream_t st) {
-  static bool attr = false;
+template <int NZ, int PARTS, bool MB>
+static void launch_cell_t(const KRom &r, const KCfg &c, const KState &s, const KIO &io, hipStream_t st) {
   const int block = spread_block(s.n, 1, 256);
   int lds = cell_lds_bytes(r);
   const int hl = block / 64 * (int)HILD_LDS_PER_WAVE;
   if (io.hild) lds = lds > hl ? lds : hl;  // the Hildreth slots
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void *)k_cell<NZ, PARTS, MB, GR, PL>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              160 * 1024);
-    attr = true;
-  }
-  hipLaunchKernelGGL((k_cell<NZ, PARTS, MB, GR, PL>), dim3(grid_for(s.n, block)), dim3(block), lds, st, r, c, s, io);
-}
-
-template <int NZ, int PARTS, bool MB>
-static void launch_cell_t(const KRom &r, const KCfg &c, const KState &s, const KIO &io, hipStream_t st) {
-  if (r.npoly) {  // ABI v3 tables: the k_cell instantiations with the polynomial lookup
-    if (r.rom_global)
-      launch_cell_g<NZ, PARTS, MB, true, true>(r, c, s, io, st);
-    else
-      launch_cell_g<NZ, PARTS, MB, false, true>(r, c, s, io, st);
-    return;
-  }
-  if (r.rom_global)
-    launch_cell_g<NZ, PARTS, MB, true, false>(r, c, s, io, st);
-  else
-    launch_cell_g<NZ, PARTS, MB, false, false>(r, c, s, io, st);
+  with_gr_pl(r.rom_global, r.npoly, [&](auto gr, auto pl) {
+    const auto kern = k_cell<NZ, PARTS, MB, decltype(gr)::value, decltype(pl)::value>;
+    static bool attr = false;  // one per instantiation
+    if (!attr) {
+      max_lds_attr((const void *)kern);
+      attr = true;
+    }
+    hipLaunchKernelGGL(kern, dim3(grid_for(s.n, block)), dim3(block), lds, st, r, c, s, io);
+  });
 }
 
 template <int NZ>
@@ -4656,34 +4378,20 @@ int launch_cell(const KRom &r, const KCfg &c, const KState &s, const KIO &io, vo
   return (int)hipGetLastError();
 }
 
-template <int NZ, int BLOCK, bool GR, bool PL>
-static void launch_ekf4_g(const KRom &r, const KCfg &c, const KState &s, const KIO &io, hipStream_t st) {
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void *)k_ekf4<NZ, BLOCK, GR, PL>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              160 * 1024);
-    attr = true;
-  }
+template <int NZ, int BLOCK>
+static void launch_ekf4_t(const KRom &r, const KCfg &c, const KState &s, const KIO &io, hipStream_t st) {
   // BLOCK is the launch bound; the 256 instantiation (512 registers, no spills) runs the
   // fewest waves per block that cover the batch in one round of CUs (spread_block)
   const int block = BLOCK == 256 ? spread_block(s.n, 4, 256) : BLOCK;
-  hipLaunchKernelGGL((k_ekf4<NZ, BLOCK, GR, PL>), dim3(grid_for(s.n * 4, block)), dim3(block), cell_lds_bytes(r), st,
-                     r, c, s, io);
-}
-
-template <int NZ, int BLOCK>
-static void launch_ekf4_t(const KRom &r, const KCfg &c, const KState &s, const KIO &io, hipStream_t st) {
-  if (r.npoly) {
-    if (r.rom_global)
-      launch_ekf4_g<NZ, BLOCK, true, true>(r, c, s, io, st);
-    else
-      launch_ekf4_g<NZ, BLOCK, false, true>(r, c, s, io, st);
-    return;
-  }
-  if (r.rom_global)
-    launch_ekf4_g<NZ, BLOCK, true, false>(r, c, s, io, st);
-  else
-    launch_ekf4_g<NZ, BLOCK, false, false>(r, c, s, io, st);
+  with_gr_pl(r.rom_global, r.npoly, [&](auto gr, auto pl) {
+    const auto kern = k_ekf4<NZ, BLOCK, decltype(gr)::value, decltype(pl)::value>;
+    static bool attr = false;  // one per instantiation
+    if (!attr) {
+      max_lds_attr((const void *)kern);
+      attr = true;
+    }
+    hipLaunchKernelGGL(kern, dim3(grid_for(s.n * 4, block)), dim3(block), cell_lds_bytes(r), st, r, c, s, io);
+  });
 }
 
 // block = 256 (the small-batch mapping: 512 registers, one wave per SIMD, spread over the
@@ -4722,10 +4430,9 @@ static void launch_bounds_g(const KRom &r, const KState &s, const double *bnd, d
 
 template <int NZ>
 static void launch_bounds_t(const KRom &r, const KState &s, const double *bnd, double *zbk, hipStream_t st) {
-  if (r.rom_global)
-    launch_bounds_g<NZ, true>(r, s, bnd, zbk, st);
-  else
-    launch_bounds_g<NZ, false>(r, s, bnd, zbk, st);
+  // k_bounds reads no electrode table: PL fixed
+  with_gr_pl(r.rom_global, false,
+             [&](auto gr, auto) { launch_bounds_g<NZ, decltype(gr)::value>(r, s, bnd, zbk, st); });
 }
 
 int launch_bounds(const KRom &r, const KState &s, const double *bnd, double *zbk, void *stream) {
