@@ -158,7 +158,12 @@ typedef struct {
   double target_soc;       /* mpcData.ref, percent (runMPC.m:30)                 */
   double Crate;            /* u_min = -Q*Crate (initMPC.m:66-67)                 */
   double u_max, du_min, du_max, v_min, v_max, phise_min, z_max, z_tol;
-  int32_t use_current, use_voltage, use_eta; /* constraint switches (runMPC.m:33) */
+  /* constraint switches (initMPC.m opts.constraints, constraintsMPC.m:18-20; runMPC.m:33 sets
+   * all three).  Non-zero = on.  Np = 5 / Nc = 2 takes any combination; Np = 20 / Nc = 10
+   * needs all three on (else MPCEKF_E_UNSUPPORTED).  The enabled blocks are stacked in the
+   * reference's order, [Cu; -Cu; I; -I] (4 Nc rows), G_v (Np), -G_e (Np), then always G_soc
+   * (Np): nC = (cur ? 4 Nc : 0) + (v ? Np : 0) + (eta ? Np : 0) + Np rows. */
+  int32_t use_current, use_voltage, use_eta;
   int32_t max_hild;        /* mpcData.maxHild (initMPC.m:47)                     */
   double hild_tol;         /* hildreth.m:39 (1e-6)                               */
   double SigmaV, SigmaW;   /* runMPC.m:18-19                                     */
@@ -197,6 +202,7 @@ void mpcekf_config_defaults(mpcekf_config *cfg); /* the runMPC.m values */
 int mpcekf_ctx_create(const mpcekf_rom *rom, const mpcekf_config *cfg, int device, int64_t ncells,
                       mpcekf_ctx **out);
 int mpcekf_ctx_destroy(mpcekf_ctx *ctx);
+/* ncon: nC of the configuration's constraint switches (23 at Np = 5 / Nc = 2 with all on). */
 int mpcekf_ctx_info(const mpcekf_ctx *ctx, int64_t *ncells, int32_t *nmodels, int32_t *nz, int32_t *ncon);
 /* The configuration the context was created with (e.g. its method, for a checkpoint). */
 int mpcekf_ctx_config(const mpcekf_ctx *ctx, mpcekf_config *cfg);
@@ -340,7 +346,8 @@ int mpcekf_mpc_diag_async(mpcekf_ctx *ctx, const double *lin, const double *uk_1
  * predMat with A = diag(a), B = ones: a,C [n][6], D [n] -> Phi [n][Np][7], G [n][Np][Nc]. */
 int mpcekf_predmat(int device, int64_t n, int32_t Np, int32_t Nc, const double *a, const double *C,
                    const double *D, double *Phi, double *G);
-/* constraintsMPC: lin [n][LIN], uk_1/soc_k1 [n] -> M [n][ncon][Nc], gamma [n][ncon]. */
+/* constraintsMPC: lin [n][LIN], uk_1/soc_k1 [n] -> M [n][ncon][Nc], gamma [n][ncon], with
+ * ncon = nC of cfg's switches: only the enabled blocks' rows, in the reference's order. */
 int mpcekf_constraints(int device, const mpcekf_config *cfg, double Q, int64_t n, const double *lin,
                        const double *uk_1, const double *soc_k1, double *M, double *gamma);
 /* hildreth: E [n][Nc][Nc], F [n][Nc], M [n][ncon][Nc], gamma/lambda [n][ncon]; lambda is
@@ -355,7 +362,9 @@ int mpcekf_hildreth(int device, int64_t n, int32_t Nc, int32_t ncon, const doubl
  * (Np = 5, Nc = 2, all three switches): M = [Cu; -Cu; I; -I; G_v; -G_e; G_soc] given by
  * the Toeplitz columns Hv, He, Hs [n][5] (G_v(i,j) = Hv(i-j) for j <= i).  This is the
  * solver the fused step runs (rank-2 form, hildreth.m:17-46); E [n][2][2], F [n][2],
- * gamma/lambda [n][23], DU [n][2], nexec [n] as in mpcekf_hildreth. */
+ * gamma/lambda [n][23], DU [n][2], nexec [n] as in mpcekf_hildreth.  Always the all-on
+ * pattern: a stack with a block switched off goes through mpcekf_hildreth with its compact
+ * M (mpcekf_constraints). */
 int mpcekf_hildreth_structured(int device, int64_t n, const double *E, const double *F, const double *Hv,
                                const double *He, const double *Hs, const double *gamma, double *lambda,
                                int32_t max_iter, double tol, double *DU, int32_t *nexec);
@@ -386,8 +395,10 @@ int mpcekf_set_graph(mpcekf_ctx *ctx, int32_t enable);
 int mpcekf_get_timing(mpcekf_ctx *ctx, double *ms_sum, int64_t *launches);
 /* The Hildreth problem records of the last fused step, as k_cell left them for
  * k_hild (field-major [MPCEKF_PROB_DOUBLES][ncells]: E(2x2) F(2) Hv(5) He(5) Hs(5)
- * gamma(23) e(5) Ru uk_1), and hflag [ncells] (1 = the QP ran).  For replaying the
- * solver offline (tools/micro); either pointer may be NULL. */
+ * gamma(23) e(5) Ru uk_1), and hflag [ncells] (1 = the QP ran).  The layout does not
+ * depend on the constraint switches: gamma keeps the all-on row slots, and the fields of a
+ * disabled block (its Hv / He, its gamma rows) read 0.  For replaying the solver offline
+ * (tools/micro); either pointer may be NULL. */
 #define MPCEKF_PROB_DOUBLES 51
 int mpcekf_get_hild_problems(mpcekf_ctx *ctx, double *prob, int32_t *hflag);
 /* Profiling builds only (-DMPCEKF_STAMPS, tools/stamps.py): shader-clock stamps at the
@@ -422,7 +433,7 @@ typedef struct {
   double *bigX;    /* [ncells][NM][6]   OB_step cellState.bigX (column per model)     */
   double *ekf;     /* [ncells][NM][20]  per model: xhat[5], SigmaX packed upper [15] */
   double *scal;    /* [ncells][MPCEKF_NSCAL] scalars, see MPCEKF_S_*                 */
-  double *lambda;  /* [ncells][ncon]    mpcData.lambda                               */
+  double *lambda;  /* [ncells][ncon]    mpcData.lambda (ncon of mpcekf_ctx_info: enabled rows) */
   int32_t *warn;   /* [ncells]          iterEKF warnCount                            */
   int32_t *status; /* [ncells]          MPCEKF_ST_*                                   */
   double *mb;      /* [ncells][MPCEKF_MB_SIZE] method MB: ekfData.xhat(1:5), 0, SigmaX

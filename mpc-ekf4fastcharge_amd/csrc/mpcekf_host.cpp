@@ -53,6 +53,14 @@ int fail(int code, const char *fmt, ...) {
 
 constexpr int NCON_BUILT = 4 * 2 + 3 * 5;  // Np = 5, Nc = 2 compiled into the lane-per-cell kernels
 int ncon_of(int Np, int Nc) { return 4 * Nc + 3 * Np; }  // constraintsMPC.m, all switches on
+// initMPC.m's opts.constraints as the kernels' mask: bit 0 useCurrent, 1 useVoltage, 2 useEta
+int sw_of(const mpcekf_config *c) { return (c->use_current ? 1 : 0) | (c->use_voltage ? 2 : 0) | (c->use_eta ? 4 : 0); }
+// does all-on row i (of [Cu; -Cu; I; -I; G_v; -G_e; G_soc]) belong to an enabled block
+bool row_enabled(int Np, int Nc, int sw, int i) {
+  return i < 4 * Nc ? (sw & 1) != 0 : i < 4 * Nc + Np ? (sw & 2) != 0 : i < 4 * Nc + 2 * Np ? (sw & 4) != 0 : true;
+}
+// nC of constraintsMPC.m:15-101: the enabled blocks' rows, G_soc always
+int ncon_sw_of(int Np, int Nc, int sw) { return (sw & 1 ? 4 * Nc : 0) + (sw & 2 ? Np : 0) + (sw & 4 ? Np : 0) + Np; }
 
 template <class T>
 int dalloc(T **p, size_t n) {
@@ -174,7 +182,11 @@ struct mpcekf_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
   int64_t n = 0;
-  int NM = 0, nz = 0, nzp = 0, ncon = 0;
+  int NM = 0, nz = 0, nzp = 0;
+  // ncon: nC of the configuration's switches (what ctx_info, get_state and set_state speak);
+  // ncon_dev: the all-on row count, whose slots s.lam keeps (a disabled row's stays 0).
+  // sw: the switch mask (sw_of); != 7 only at Np = 5 / Nc = 2 (mpcekf_switch.hip)
+  int ncon = 0, ncon_dev = 0, sw = 7;
   bool initialized = false;
   KRom r{};
   KCfg k{};
@@ -894,8 +906,10 @@ static int check_cfg(const mpcekf_config *c) {
   if (!(c->Np == 5 && c->Nc == 2) && !wide_supported(c->Np, c->Nc))
     return fail(MPCEKF_E_UNSUPPORTED, "Np=%d Nc=%d: this build compiles the GPU step for Np/Nc = 5/2 and 20/10",
                 c->Np, c->Nc);
-  if (!c->use_current || !c->use_voltage || !c->use_eta)
-    return fail(MPCEKF_E_UNSUPPORTED, "constraint switches must all be on (runMPC.m:33) in this build");
+  if (sw_of(c) != 7 && !(c->Np == 5 && c->Nc == 2))
+    return fail(MPCEKF_E_UNSUPPORTED,
+                "Np=%d Nc=%d with a constraint switch off: the switches are built for Np/Nc = 5/2 only "
+                "(this horizon needs all three on)", c->Np, c->Nc);
   if (c->max_hild < 1) return fail(MPCEKF_E_ARG, "max_hild < 1");
   if (c->method != MPCEKF_METHOD_OB && c->method != MPCEKF_METHOD_MB)
     return fail(MPCEKF_E_ARG, "method %d: expected MPCEKF_METHOD_OB or _MB (initKF.m:44-49)", c->method);
@@ -934,7 +948,9 @@ int mpcekf_ctx_create(const mpcekf_rom *rom, const mpcekf_config *cfg, int devic
   X->device = device;
   X->n = ncells;
   X->cfg = *cfg;
-  X->ncon = ncon_of(cfg->Np, cfg->Nc);
+  X->sw = sw_of(cfg);
+  X->ncon_dev = ncon_of(cfg->Np, cfg->Nc);
+  X->ncon = ncon_sw_of(cfg->Np, cfg->Nc, X->sw);
   X->wide = wide_supported(cfg->Np, cfg->Nc);
   X->mb = cfg->method == MPCEKF_METHOD_MB;
   if ((rc = build_rom(X, rom))) { mpcekf_ctx_destroy(X); return rc; }
@@ -955,7 +971,10 @@ int mpcekf_ctx_create(const mpcekf_rom *rom, const mpcekf_config *cfg, int devic
   // MPCEKF_QUAD_MAX cells, default 8,192 (results identical whichever path runs; same-box
   // A/B, profiles/r05e_small_batch.txt: 1,024 cells 0.173 -> 0.160 ms per step, 4,096 0.176
   // -> 0.164, 16,384 0.189 either way).  MPCEKF_QUAD=0/1 forces it.
-  const bool quad_ok = rom->nT > 1 && rom->nZ > 1 && cfg->method == MPCEKF_METHOD_OB && !X->wide;
+  // A context with a constraint switch off runs k_cell<P_EKF | P_LIN> + mpcekf_switch.hip's
+  // kernels at every batch size (no k_ekf4 mapping, no MPCEKF_SPLIT_CELL form).
+  if (X->sw != 7) X->split_cell = false;
+  const bool quad_ok = rom->nT > 1 && rom->nZ > 1 && cfg->method == MPCEKF_METHOD_OB && !X->wide && X->sw == 7;
   {
     int64_t quad_max = 8192;
     if (const char *e = std::getenv("MPCEKF_QUAD_MAX")) quad_max = std::atoll(e);
@@ -993,7 +1012,7 @@ int mpcekf_ctx_create(const mpcekf_rom *rom, const mpcekf_config *cfg, int devic
   KState &s = X->s;
   s.n = ncells;
   if ((rc = dalloc(&s.bigx, n * NM * 6)) || (rc = dalloc(&s.ekf, n * NM * REC)) ||
-      (rc = dalloc(&X->d_scal, n * 10)) || (rc = dalloc(&s.lam, n * X->ncon)) ||
+      (rc = dalloc(&X->d_scal, n * 10)) || (rc = dalloc(&s.lam, n * X->ncon_dev)) ||
       (rc = hipMalloc((void **)&X->d_int, (n * 4 + 1) * sizeof(int)) == hipSuccess ? 0 : MPCEKF_E_HIP) || (rc = dalloc(&X->d_prob, n * PROB_DOUBLES)) || (rc = dalloc(&X->d_const, n * 8)) ||
       (rc = dalloc(&X->d_zk, n * (X->nz + 2))) || (rc = dalloc(&X->d_zbk, n * (X->nz + 2))) ||
       (rc = dalloc(&X->d_bnd, n * NBND)) || (rc = dalloc(&X->d_xg, n * 4)) ||
@@ -1023,6 +1042,10 @@ int mpcekf_ctx_create(const mpcekf_rom *rom, const mpcekf_config *cfg, int devic
   if (X->d_stamps) HIPCHK(hipMemset(X->d_stamps, 0, (size_t)n * NSTAMPS * sizeof(long long)));
   double *cs = X->d_const;
   s.Tc = cs; s.SOC0 = cs + n; s.SOC0n = cs + 2 * n; s.SOC0p = cs + 3 * n;
+  if (X->sw != 7 && ((rc = dalloc(&X->d_lin, n * MPCEKF_LIN_SIZE)) || (rc = dalloc(&X->d_zsoc, n)))) {
+    mpcekf_ctx_destroy(X);  // the hand-off k_cell<P_EKF | P_LIN> -> k_mpc_sw
+    return rc;
+  }
   if (X->wide) {
     KWide &w = X->w;
     w.Np = cfg->Np; w.Nc = cfg->Nc; w.ncon = X->ncon;
@@ -1138,7 +1161,7 @@ int mpcekf_init_cells(mpcekf_ctx *X, const double *soc0_pct, const double *tc_de
   }
   HIPCHK(hipMemcpyAsync(X->d_const, cst.data(), cst.size() * 8, hipMemcpyHostToDevice, X->stream));
   HIPCHK(hipMemcpyAsync(X->d_scal, sc.data(), sc.size() * 8, hipMemcpyHostToDevice, X->stream));
-  HIPCHK(hipMemsetAsync(X->s.lam, 0, n * X->ncon * 8, X->stream));
+  HIPCHK(hipMemsetAsync(X->s.lam, 0, n * X->ncon_dev * 8, X->stream));
   HIPCHK(hipMemsetAsync(X->d_int, 0, n * 4 * sizeof(int), X->stream));
   HIPCHK(hipMemsetAsync(X->d_ts, 0, n * X->NM * 2 * sizeof(int), X->stream));  // every model current
   int rc = launch_init_state(X->n, X->NM, X->s.ekf, X->s.bigx, X->cfg.SigmaX0, X->stream);
@@ -1192,7 +1215,8 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
   // OB_step's simStep inside k_cell (KRom::cell_plant): no k_plant launch
   const bool plant_in_cell = X->r.cell_plant && !X->mb;  // k_cell, or k_ekf4's lane quad (quad_plant)
   // hildreth.m at the end of k_cell (Np = 5, one k_cell per step): no k_hild launch
-  const bool hild_in_cell = cell_runs_hild() && !X->wide && !X->split_cell && !X->quad;
+  const bool switched = X->sw != 7;  // a constraint block off: the split route of mpcekf_switch.hip
+  const bool hild_in_cell = cell_runs_hild() && !X->wide && !X->split_cell && !X->quad && !switched;
   const size_t n = (size_t)X->n, per = n * (size_t)nsteps, nzz = (size_t)X->nz + 2;
   // the output fields, their element size and elements per cell-step
   struct F {
@@ -1325,8 +1349,10 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
       io.normdu_out = (double *)row(10, k);
       io.nviol_out = (int *)row(11, k);
       if (diag) io.lin_out = X->d_lin;
-      KIO iow{};  // wide horizons: iterMPC in mpcekf_wide.hip from the linearisation record
-      if (X->wide) {
+      // wide horizons, or a constraint switch off: iterMPC in mpcekf_wide.hip / mpcekf_switch.hip
+      // from the linearisation record
+      KIO iow{};
+      if (X->wide || switched) {
         io.lin_out = X->d_lin;
         io.zsoc_out = X->d_zsoc;
         if ((rc = lerr(launch_cell(X->r, X->k, X->s, io, X->stream, P_EKF | P_LIN), "cell"))) return rc;
@@ -1339,7 +1365,11 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
         iow.jfin_out = io.jfin_out;
         iow.normdu_out = io.normdu_out;
         iow.nviol_out = io.nviol_out;
-        if ((rc = lerr(launch_mpc_wide(X->k, X->s, iow, X->w, X->stream), "mpc_wide"))) return rc;
+        if (switched) {
+          if ((rc = lerr(launch_mpc_sw(X->sw, X->k, X->s, iow, X->stream), "mpc_sw"))) return rc;
+        } else if ((rc = lerr(launch_mpc_wide(X->k, X->s, iow, X->w, X->stream), "mpc_wide"))) {
+          return rc;
+        }
       } else if (X->split_cell || X->quad) {  // iterEKF, then EKFmatsHandler + iterMPC from zk and Xind in HBM
         io.xm_out = X->d_xm;
         io.xg_out = X->d_xg;
@@ -1395,6 +1425,8 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
       if (E) HIPCHK(hipEventRecord(E[hstart], X->stream));
       if (X->wide) {
         if ((rc = lerr(launch_hild_wide(X->k, X->s, iow, X->w, X->stream), "hild_wide"))) return rc;
+      } else if (switched) {
+        if ((rc = lerr(launch_hild_sw(X->sw, X->k, X->s, iow, X->stream), "hild_sw"))) return rc;
       } else if (!hild_in_cell && (rc = lerr(launch_hild(X->k, X->s, io, X->stream), "hild"))) {
         return rc;
       }
@@ -1935,6 +1967,9 @@ static int mpc_step_ex_impl(mpcekf_ctx *X, const double *lin, const double *soc_
   if (X->wide) {
     if ((rc = lerr(launch_mpc_wide(X->k, X->s, io, X->w, X->stream), "mpc_wide"))) return rc;
     if ((rc = lerr(launch_hild_wide(X->k, X->s, io, X->w, X->stream), "hild_wide"))) return rc;
+  } else if (X->sw != 7) {
+    if ((rc = lerr(launch_mpc_sw(X->sw, X->k, X->s, io, X->stream), "mpc_sw"))) return rc;
+    if ((rc = lerr(launch_hild_sw(X->sw, X->k, X->s, io, X->stream), "hild_sw"))) return rc;
   } else {
     if ((rc = lerr(launch_cell(X->r, X->k, X->s, io, X->stream), "cell"))) return rc;
     if ((rc = lerr(launch_hild(X->k, X->s, io, X->stream), "hild"))) return rc;
@@ -2038,14 +2073,15 @@ int mpcekf_constraints(int device, const mpcekf_config *cfg, double Q, int64_t n
   HIPCHK(hipSetDevice(device));
   DevScope d;
   HIPCHK(hipStreamCreateWithFlags(&d.st, hipStreamNonBlocking));
-  const int ncon = ncon_of(cfg->Np, cfg->Nc), Nc = cfg->Nc;
+  const int sw = sw_of(cfg), ncon = ncon_sw_of(cfg->Np, cfg->Nc, sw), Nc = cfg->Nc;  // check_cfg: sw != 7 only at 5/2
   HIPCHK(hipMalloc((void **)&d.buf, (size_t)n * (MPCEKF_LIN_SIZE + 2 + ncon * Nc + ncon) * 8 + 1024));
   double *dl = (double *)d.buf, *du = dl + n * MPCEKF_LIN_SIZE, *ds = du + n, *dM = ds + n, *dg = dM + n * ncon * Nc;
   HIPCHK(hipMemcpyAsync(dl, lin, n * MPCEKF_LIN_SIZE * 8, hipMemcpyHostToDevice, d.st));
   HIPCHK(hipMemcpyAsync(du, uk_1, n * 8, hipMemcpyHostToDevice, d.st));
   HIPCHK(hipMemcpyAsync(ds, soc_k1, n * 8, hipMemcpyHostToDevice, d.st));
   if ((rc = lerr(wide_supported(cfg->Np, Nc) ? launch_constraints_wide(k, cfg->Np, Nc, n, dl, du, ds, dM, dg, d.st)
-                                               : launch_constraints(k, n, dl, du, ds, dM, dg, d.st),
+                 : sw != 7                   ? launch_constraints_sw(sw, k, n, dl, du, ds, dM, dg, d.st)
+                                             : launch_constraints(k, n, dl, du, ds, dM, dg, d.st),
                  "constraints")))
     return rc;
   HIPCHK(hipMemcpyAsync(M, dM, n * ncon * Nc * 8, hipMemcpyDeviceToHost, d.st));
@@ -2152,23 +2188,24 @@ int mpcekf_get_state(mpcekf_ctx *X, mpcekf_state *st) {
   int rc = need_init(X);
   if (rc) return rc;
   if (!st) return fail(MPCEKF_E_ARG, "get_state: null");
-  const size_t n = (size_t)X->n, NM = (size_t)X->NM, nc = (size_t)X->ncon;
+  const size_t n = (size_t)X->n, NM = (size_t)X->NM, nc = (size_t)X->ncon, ncd = (size_t)X->ncon_dev;
   if (st->bigX) HIPCHK(hipMemcpyAsync(st->bigX, X->s.bigx, n * NM * 6 * 8, hipMemcpyDeviceToHost, X->stream));
   if (st->ekf) HIPCHK(hipMemcpyAsync(st->ekf, X->s.ekf, n * NM * REC * 8, hipMemcpyDeviceToHost, X->stream));
   if (st->mb && X->mb) HIPCHK(hipMemcpyAsync(st->mb, X->d_mb, n * MBREC * 8, hipMemcpyDeviceToHost, X->stream));
   // only the requested fields cross PCIe (a MEX drop-in reading SOCnAvg/SOCpAvg each
   // step moves the 64-B scalar block per cell, not the NM-model records)
-  std::vector<double> sc(st->scal ? n * 8 : 0), lam(st->lambda ? n * nc : 0);
+  std::vector<double> sc(st->scal ? n * 8 : 0), lam(st->lambda ? n * ncd : 0);
   std::vector<int> iv(st->warn || st->status ? n * 2 : 0);
   if (st->scal) HIPCHK(hipMemcpyAsync(sc.data(), X->d_scal, n * 8 * 8, hipMemcpyDeviceToHost, X->stream));
-  if (st->lambda) HIPCHK(hipMemcpyAsync(lam.data(), X->s.lam, n * nc * 8, hipMemcpyDeviceToHost, X->stream));
+  if (st->lambda) HIPCHK(hipMemcpyAsync(lam.data(), X->s.lam, n * ncd * 8, hipMemcpyDeviceToHost, X->stream));
   if (!iv.empty()) HIPCHK(hipMemcpyAsync(iv.data(), X->d_int, n * 2 * 4, hipMemcpyDeviceToHost, X->stream));
   HIPCHK(hipStreamSynchronize(X->stream));
   for (size_t c = 0; c < n; ++c) {
     if (st->scal)
       for (int k = 0; k < MPCEKF_NSCAL; ++k) st->scal[c * MPCEKF_NSCAL + k] = sc[kScalMap[k] * n + c];
-    if (st->lambda)
-      for (size_t i = 0; i < nc; ++i) st->lambda[c * nc + i] = lam[i * n + c];
+    if (st->lambda)  // the enabled rows in the reference's order (mpcData.lambda): [ncells][nC]
+      for (size_t i = 0, ci = 0; i < ncd; ++i)
+        if (row_enabled(X->cfg.Np, X->cfg.Nc, X->sw, (int)i)) st->lambda[c * nc + ci++] = lam[i * n + c];
     if (st->warn) st->warn[c] = iv[c];
     if (st->status) st->status[c] = iv[n + c];
   }
@@ -2218,13 +2255,13 @@ int mpcekf_set_state(mpcekf_ctx *X, const mpcekf_state *st) {
   int rc = need_init(X);
   if (rc) return rc;
   if (!st) return fail(MPCEKF_E_ARG, "set_state: null");
-  const size_t n = (size_t)X->n, NM = (size_t)X->NM, nc = (size_t)X->ncon;
+  const size_t n = (size_t)X->n, NM = (size_t)X->NM, nc = (size_t)X->ncon, ncd = (size_t)X->ncon_dev;
   if (st->bigX) HIPCHK(hipMemcpyAsync(X->s.bigx, st->bigX, n * NM * 6 * 8, hipMemcpyHostToDevice, X->stream));
   if (st->ekf) HIPCHK(hipMemcpyAsync(X->s.ekf, st->ekf, n * NM * REC * 8, hipMemcpyHostToDevice, X->stream));
   if (st->mb && X->mb) HIPCHK(hipMemcpyAsync(X->d_mb, st->mb, n * MBREC * 8, hipMemcpyHostToDevice, X->stream));
   // scal and lambda are whole blocks (every slot given); warn and status share one block,
   // read back first when only one of them is given
-  std::vector<double> sc(st->scal ? n * 8 : 0), lam(st->lambda ? n * nc : 0);
+  std::vector<double> sc(st->scal ? n * 8 : 0), lam(st->lambda ? n * ncd : 0);  // a disabled row's slot: 0
   std::vector<int> iv(st->warn || st->status ? n * 2 : 0);
   if (!iv.empty() && !(st->warn && st->status)) {
     HIPCHK(hipMemcpyAsync(iv.data(), X->d_int, n * 2 * 4, hipMemcpyDeviceToHost, X->stream));
@@ -2234,12 +2271,13 @@ int mpcekf_set_state(mpcekf_ctx *X, const mpcekf_state *st) {
     if (st->scal)
       for (int k = 0; k < MPCEKF_NSCAL; ++k) sc[kScalMap[k] * n + c] = st->scal[c * MPCEKF_NSCAL + k];
     if (st->lambda)
-      for (size_t i = 0; i < nc; ++i) lam[i * n + c] = st->lambda[c * nc + i];
+      for (size_t i = 0, ci = 0; i < ncd; ++i)
+        if (row_enabled(X->cfg.Np, X->cfg.Nc, X->sw, (int)i)) lam[i * n + c] = st->lambda[c * nc + ci++];
     if (st->warn) iv[c] = st->warn[c];
     if (st->status) iv[n + c] = st->status[c];
   }
   if (st->scal) HIPCHK(hipMemcpyAsync(X->d_scal, sc.data(), n * 8 * 8, hipMemcpyHostToDevice, X->stream));
-  if (st->lambda) HIPCHK(hipMemcpyAsync(X->s.lam, lam.data(), n * nc * 8, hipMemcpyHostToDevice, X->stream));
+  if (st->lambda) HIPCHK(hipMemcpyAsync(X->s.lam, lam.data(), n * ncd * 8, hipMemcpyHostToDevice, X->stream));
   if (!iv.empty()) HIPCHK(hipMemcpyAsync(X->d_int, iv.data(), n * 2 * 4, hipMemcpyHostToDevice, X->stream));
   HIPCHK(hipStreamSynchronize(X->stream));
   return MPCEKF_OK;

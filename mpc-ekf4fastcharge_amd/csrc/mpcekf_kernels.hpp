@@ -262,6 +262,18 @@ int launch_predmat_wide(int64_t n, int Np, int Nc, const double *a, const double
                         double *G, void *stream);
 int launch_constraints_wide(const KCfg &c, int Np, int Nc, int64_t n, const double *lin, const double *uk_1,
                             const double *soc_k1, double *M, double *gam, void *stream);
+// Np = 5 / Nc = 2 with a constraint block switched off (mpcekf_switch.hip).  sw: bit 0
+// useCurrent, bit 1 useVoltage, bit 2 useEta (initMPC.m opts.constraints), 0..6 here (7, all
+// on, is launch_cell / launch_hild / launch_constraints).
+// iterMPC.m:17-66 from the linearisation records io.lin_in [n][35] and io.soc_k1_in [n]:
+// the problem record and hflag, or the finished cell when no QP is needed
+int launch_mpc_sw(int sw, const KCfg &c, const KState &s, const KIO &io, void *stream);
+// hildreth.m over the enabled rows (fast sweep + exact finisher) and iterMPC.m:68-95
+int launch_hild_sw(int sw, const KCfg &c, const KState &s, const KIO &io, void *stream);
+// compact M [n][nC][Nc], gamma [n][nC]
+int launch_constraints_sw(int sw, const KCfg &c, int64_t n, const double *lin, const double *uk_1,
+                          const double *soc_k1, double *M, double *gam, void *stream);
+int spread_block(int64_t n, int lpc, int maxb);
 // selected columns of [n][stride] records to / from a compact [n][k] buffer (mpcekf_io.hip)
 int launch_cols(double *rec, int64_t n, int stride, const int *slots, int k, double *compact, bool scatter,
                 void *stream);

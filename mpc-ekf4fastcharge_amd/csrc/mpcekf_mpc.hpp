@@ -279,6 +279,39 @@ __device__ __forceinline__ void lin_load(const double *o, Lin &L) {
   L.Dsoc = o[12]; L.Dv = o[19]; L.Dphi = o[26]; L.bv = o[27]; L.bphi = o[28];
 }
 
+// initMPC.m's opts.constraints = [useCurrent useVoltage useEta] (constraintsMPC.m:18-20) as a
+// 3-bit mask SW.  The device keeps the all-on row numbering i = 0 .. 4 NC + 3 NP - 1 (storage
+// slots of lambda, gamma and the per-lane LDS); a disabled block's rows are absent from every
+// loop (row_on is a constant of the unrolled row loops), and the position of an enabled row in
+// the reference's compact stack is row_cidx.  SW_ALL folds every test away.
+constexpr int SW_CUR = 1, SW_V = 2, SW_ETA = 4, SW_ALL = 7;
+template <int NP, int NC, int SW>
+__host__ __device__ constexpr bool row_on(int i) {
+  return i < 4 * NC ? (SW & SW_CUR) != 0
+       : i < 4 * NC + NP ? (SW & SW_V) != 0
+       : i < 4 * NC + 2 * NP ? (SW & SW_ETA) != 0
+                             : true;
+}
+template <int NP, int NC, int SW>
+__host__ __device__ constexpr int ncon_sw() {
+  return ((SW & SW_CUR) ? 4 * NC : 0) + ((SW & SW_V) ? NP : 0) + ((SW & SW_ETA) ? NP : 0) + NP;
+}
+// compact index (constraintsMPC.m's row number) of the enabled all-on row i
+template <int NP, int NC, int SW>
+__host__ __device__ constexpr int row_cidx(int i) {
+  return i - (!(SW & SW_CUR) && i >= 4 * NC ? 4 * NC : 0) - (!(SW & SW_V) && i >= 4 * NC + NP ? NP : 0) -
+         (!(SW & SW_ETA) && i >= 4 * NC + 2 * NP ? NP : 0);
+}
+// all-on row of compact index ci
+template <int NP, int NC, int SW>
+__host__ __device__ constexpr int row_full(int ci) {
+  int i = ci;
+  if (!(SW & SW_CUR)) i += 4 * NC;
+  if (!(SW & SW_V) && i >= 4 * NC) i += NP;
+  if (!(SW & SW_ETA) && i >= 4 * NC + NP) i += NP;
+  return i;
+}
+
 // The constraint matrix of constraintsMPC.m (all switches on) has a fixed
 // pattern: rows [Cu; -Cu; I; -I] are constants and the voltage / eta / SOC rows
 // are lower-triangular Toeplitz in the impulse responses Hv, He, Hs.  Only those
@@ -303,49 +336,66 @@ __device__ __forceinline__ double mval(const ConsT<NP, NC> &C, int i, int k) {
   return k <= r ? C.Hs[r - k] : 0.0;                                   // G_soc
 }
 
-// constraintsMPC.m:11-112 for NP x NC (terminal row off, as runMPC)
-template <int NP, int NC>
+// constraintsMPC.m:11-112 for NP x NC (terminal row off, as runMPC).  A disabled block
+// (SW) is not formed: no predMat for it, its Hv / He and gamma slots are +0.
+template <int NP, int NC, int SW = SW_ALL>
 __device__ __forceinline__ void constraints_s(const KCfg &cf, const Lin &L, const double dx[NA], double uk_1,
                                               double SOCk_1, const double (&Phis)[NP][NA], const double (&Hs)[NP],
                                               ConsT<NP, NC> &C) {
   int nr = 0;
+  if constexpr ((SW & SW_CUR) != 0) {
 #pragma unroll
-  for (int i = 0; i < NC; ++i) C.gam[nr + i] = (cf.u_max - uk_1) * 1.0;
-  nr += NC;
+    for (int i = 0; i < NC; ++i) C.gam[nr + i] = (cf.u_max - uk_1) * 1.0;
+    nr += NC;
 #pragma unroll
-  for (int i = 0; i < NC; ++i) C.gam[nr + i] = -(cf.u_min - uk_1) * 1.0;
-  nr += NC;
+    for (int i = 0; i < NC; ++i) C.gam[nr + i] = -(cf.u_min - uk_1) * 1.0;
+    nr += NC;
 #pragma unroll
-  for (int i = 0; i < NC; ++i) C.gam[nr + i] = cf.du_max * 1.0;
-  nr += NC;
+    for (int i = 0; i < NC; ++i) C.gam[nr + i] = cf.du_max * 1.0;
+    nr += NC;
 #pragma unroll
-  for (int i = 0; i < NC; ++i) C.gam[nr + i] = -cf.du_min * 1.0;
-  nr += NC;
+    for (int i = 0; i < NC; ++i) C.gam[nr + i] = -cf.du_min * 1.0;
+    nr += NC;
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4 * NC; ++i) C.gam[i] = 0.0;
+    nr += 4 * NC;
+  }
   double Phi[NP][NA], Cb[7];
+  if constexpr ((SW & SW_V) != 0) {
 #pragma unroll
-  for (int k = 0; k < 6; ++k) Cb[k] = L.Cv[k];
-  Cb[6] = L.Dv;
-  predmat_s<NP>(L.a, Cb, Phi, C.Hv);
+    for (int k = 0; k < 6; ++k) Cb[k] = L.Cv[k];
+    Cb[6] = L.Dv;
+    predmat_s<NP>(L.a, Cb, Phi, C.Hv);
 #pragma unroll
-  for (int i = 0; i < NP; ++i) {
-    double acc = 0.0;
+    for (int i = 0; i < NP; ++i) {
+      double acc = 0.0;
 #pragma unroll
-    for (int k = 0; k < NA; ++k) acc = acc + Phi[i][k] * dx[k];
-    double rhs = acc + L.bv * 1.0;
-    C.gam[nr + i] = cf.v_max - rhs;
+      for (int k = 0; k < NA; ++k) acc = acc + Phi[i][k] * dx[k];
+      double rhs = acc + L.bv * 1.0;
+      C.gam[nr + i] = cf.v_max - rhs;
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < NP; ++i) { C.Hv[i] = 0.0; C.gam[nr + i] = 0.0; }
   }
   nr += NP;
+  if constexpr ((SW & SW_ETA) != 0) {
 #pragma unroll
-  for (int k = 0; k < 6; ++k) Cb[k] = L.Cphi[k];
-  Cb[6] = L.Dphi;
-  predmat_s<NP>(L.a, Cb, Phi, C.He);
+    for (int k = 0; k < 6; ++k) Cb[k] = L.Cphi[k];
+    Cb[6] = L.Dphi;
+    predmat_s<NP>(L.a, Cb, Phi, C.He);
 #pragma unroll
-  for (int i = 0; i < NP; ++i) {
-    double acc = 0.0;
+    for (int i = 0; i < NP; ++i) {
+      double acc = 0.0;
 #pragma unroll
-    for (int k = 0; k < NA; ++k) acc = acc + Phi[i][k] * dx[k];
-    double rhs = acc + L.bphi * 1.0;
-    C.gam[nr + i] = -cf.phise_min + rhs;
+      for (int k = 0; k < NA; ++k) acc = acc + Phi[i][k] * dx[k];
+      double rhs = acc + L.bphi * 1.0;
+      C.gam[nr + i] = -cf.phise_min + rhs;
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < NP; ++i) { C.He[i] = 0.0; C.gam[nr + i] = 0.0; }
   }
   nr += NP;
 #pragma unroll
@@ -473,7 +523,7 @@ __device__ __forceinline__ void mpc_core(const KCfg &cf, const Lin &L, double uk
     for (int b = 0; b < NC; ++b) P.E[a][b] = 2 * (GtG[a][b] + P.Ru * (a == b ? 1.0 : 0.0));
 }
 
-template <int NP, int NC>
+template <int NP, int NC, int SW = SW_ALL>
 __device__ __forceinline__ bool mpc_setup(const KCfg &cf, const Lin &L, double uk_1, double SOCk_1,
                                           MpcSetupT<NP, NC> &P, MpcOut &o, const double *smin_cache = nullptr) {
   constexpr int NCON = 4 * NC + 3 * NP;
@@ -486,10 +536,11 @@ __device__ __forceinline__ bool mpc_setup(const KCfg &cf, const Lin &L, double u
     for (int b = 0; b < NC; ++b) mE[a][b] = -P.E[a][b];
   lu_solve_n<NC>(mE, P.F, P.DU);
   o.J_unc = mpc_cost<NP, NC>(Hs, P.e, P.Ru, P.DU);
-  constraints_s<NP, NC>(cf, L, dx, uk_1, SOCk_1, Phis, Hs, P.Cn);
+  constraints_s<NP, NC, SW>(cf, L, dx, uk_1, SOCk_1, Phis, Hs, P.Cn);
   int nv = 0;
 #pragma unroll
   for (int i = 0; i < NCON; ++i) {
+    if (!row_on<NP, NC, SW>(i)) continue;
     double acc = 0.0;
 #pragma unroll
     for (int j = 0; j < NC; ++j) acc = acc + mval(P.Cn, i, j) * P.DU[j];
@@ -499,7 +550,7 @@ __device__ __forceinline__ bool mpc_setup(const KCfg &cf, const Lin &L, double u
 }
 
 // iterMPC.m:75-95 after the (optional) Hildreth solve
-template <int NP, int NC>
+template <int NP, int NC, int SW = SW_ALL>
 __device__ __forceinline__ void mpc_finish(const ConsT<NP, NC> &Cn, const double (&e)[NP], double Ru,
                                            const double (&DU)[NC], double &uk_1, MpcOut &o) {
   constexpr int NCON = 4 * NC + 3 * NP;
@@ -509,6 +560,7 @@ __device__ __forceinline__ void mpc_finish(const ConsT<NP, NC> &Cn, const double
   int nviol = 0;
 #pragma unroll
   for (int i = 0; i < NCON; ++i) {
+    if (!row_on<NP, NC, SW>(i)) continue;
     double acc = 0.0;
 #pragma unroll
     for (int j = 0; j < NC; ++j) acc = acc + mval(Cn, i, j) * DU[j];

@@ -25,7 +25,7 @@ from . import _lib
 from ._lib import LIN_SIZE, MpcekfError, check, dptr, iptr
 from .rom import EL_TABLES, OBS_FIELDS, ROM, TF_CODE
 
-__all__ = ["Context", "DeviceBuffer", "hip_runtimes", "tc_grid", "make_config", "predMat", "constraintsMPC", "hildreth", "runMPC", "MpcekfError",
+__all__ = ["Context", "DeviceBuffer", "hip_runtimes", "tc_grid", "make_config", "predMat", "constraintsMPC", "constraint_rows", "hildreth", "runMPC", "MpcekfError",
            "LIN_SIZE"]
 
 LIN_FIELDS = dict(A=slice(0, 6), Csoc=slice(6, 12), Dsoc=12, Cv=slice(13, 19), Dv=19,
@@ -619,15 +619,23 @@ def predMat(a, Cr, D, Np=5, Nc=2, device=0):
     return Phi, G
 
 
+def constraint_rows(cfg):
+    """nC of constraintsMPC.m:15-101 for cfg's switches: [Cu; -Cu; I; -I] (4 Nc rows) if
+    useCurrent, G_v (Np) if useVoltage, -G_e (Np) if useEta, then always G_soc (Np)."""
+    return (4 * cfg.Nc if cfg.use_current else 0) + (cfg.Np if cfg.use_voltage else 0) + \
+           (cfg.Np if cfg.use_eta else 0) + cfg.Np
+
+
 def constraintsMPC(lin, uk_1, SOCk_1, Q, cfg=None, device=0):
-    """constraintsMPC.m: lin [n,35] -> M [n,ncon,Nc], gamma [n,ncon]."""
+    """constraintsMPC.m: lin [n,35] -> M [n,ncon,Nc], gamma [n,ncon]; ncon = constraint_rows(cfg),
+    the enabled blocks only (cfg = make_config(constraints=(cur, v, eta)))."""
     L = _lib.load()
     cfg = cfg if cfg is not None else make_config()
     lin = np.ascontiguousarray(np.atleast_2d(lin), dtype=np.float64)
     n = lin.shape[0]
     u = np.ascontiguousarray(np.broadcast_to(uk_1, (n,)), dtype=np.float64)
     s = np.ascontiguousarray(np.broadcast_to(SOCk_1, (n,)), dtype=np.float64)
-    ncon = 4 * cfg.Nc + 3 * cfg.Np
+    ncon = constraint_rows(cfg)
     M = np.empty((n, ncon, cfg.Nc))
     g = np.empty((n, ncon))
     check(L.mpcekf_constraints(device, C.byref(cfg), float(Q), n, dptr(lin), dptr(u), dptr(s), dptr(M), dptr(g)))
