@@ -543,6 +543,44 @@ int orc_is_pd(const double *a /*full, symmetric*/) {
   return 1;
 }
 
+/* Branch counters of the measurement update's covariance step (test infrastructure: the
+ * tests of the Jacobi and Q-bump branches prove with them that their inputs are on the
+ * branch).  Process-wide, atomic (orc_run is OpenMP over cells); they enter no arithmetic. */
+enum { BC_OB_UPD, BC_OB_NONPD, BC_OB_BUMP, BC_MB_UPD, BC_MB_NONPD, BC_MB_BUMP, BC_OB_BOTH, BC_MB_BOTH, BC_N };
+static long branch_count[BC_N];
+
+static void branch_hit(int upd, int nonpd, int bump) {
+#pragma omp atomic
+  branch_count[upd] += 1;
+  if (nonpd) {
+#pragma omp atomic
+    branch_count[upd + 1] += 1;
+  }
+  if (bump) {
+#pragma omp atomic
+    branch_count[upd + 2] += 1;
+  }
+  if (nonpd && bump) {
+#pragma omp atomic
+    branch_count[upd == BC_OB_UPD ? BC_OB_BOTH : BC_MB_BOTH] += 1;
+  }
+}
+
+/* out: OB updates, OB non-PD, OB bump, MB updates, MB non-PD, MB bump since the last call
+ * (the counters are reset); both[2], when given: OB and MB updates that were non-PD and
+ * bumped at once. */
+void orc_branch_counts_ex(long out[6], long both[2]) {
+  for (int i = 0; i < BC_N; ++i) {
+    long v;
+#pragma omp atomic capture
+    { v = branch_count[i]; branch_count[i] = 0; }
+    if (i < 6) out[i] = v;
+    else if (both) both[i - 6] = v;
+  }
+}
+
+void orc_branch_counts(long out[6]) { orc_branch_counts_ex(out, 0); }
+
 void orc_meas_cov(double *S /*packed*/, const double *L, double St, int bump) {
   double P[NX][NX], a[NX * NX], V[NX * NX], w[NX];
   double LS[NX];
@@ -556,7 +594,9 @@ void orc_meas_cov(double *S /*packed*/, const double *L, double St, int bump) {
    * is a itself: take it directly (no reconstruction rounding) and skip the
    * eigen-decomposition. */
   double HH[NX][NX];
-  if (orc_is_pd(a)) {
+  const int pd = orc_is_pd(a);
+  branch_hit(BC_OB_UPD, !pd, bump);
+  if (pd) {
     for (int r = 0; r < NX; ++r)
       for (int c = 0; c < NX; ++c) HH[r][c] = a[r * NX + c];
   } else {
@@ -1057,7 +1097,9 @@ static void meas_cov_mb(double *S, const double *L, double St, int bump) {
     for (int c = 0; c < NA; ++c) P[r * NA + c] = fma(-(L[r] * St), L[c], S[r * NA + c]);
   for (int r = 0; r < NA; ++r)
     for (int c = 0; c < NA; ++c) a[r * NA + c] = (P[r * NA + c] + P[c * NA + r]) * 0.5;
-  if (is_pd_n(NA, a)) {
+  const int pd = is_pd_n(NA, a);
+  branch_hit(BC_MB_UPD, !pd, bump);
+  if (pd) {
     memcpy(HH, a, sizeof(HH));
   } else {
     orc_jacobi(NA, a, V, w);

@@ -105,6 +105,8 @@ def lib():
         L.orc_sigma_min.argtypes = [C.c_int, _dp]
         L.orc_meas_cov.argtypes = [_dp, _dp, C.c_double, C.c_int]
         L.orc_jacobi.argtypes = [C.c_int, _dp, _dp, _dp]
+        L.orc_branch_counts_ex.restype = None
+        L.orc_branch_counts_ex.argtypes = [C.POINTER(C.c_long), C.POINTER(C.c_long)]
         L.orc_exp.restype = C.c_double      # the v3 Arrhenius factor's defined exp
         L.orc_exp.argtypes = [C.c_double]
         _lib = L
@@ -285,6 +287,18 @@ def hildreth(E, F, M, gamma, lam0, maxIter=100, tol=1e-6):
     it = lib().orc_hildreth(E.shape[0], M.shape[0], _p(E), _p(np.ascontiguousarray(F, float)), _p(M),
                             _p(np.ascontiguousarray(gamma, float)), _p(lam), maxIter, tol, _p(DU))
     return DU, lam, it
+
+
+def branch_counts():
+    """Measurement updates since the last call, by branch of the covariance step
+    (iterEKF.m:141-151 / 164-173), and a reset of the counters: per filter ("ob", "mb") the
+    updates, those whose (P + P')/2 was not positive definite (the Jacobi polar factor), those
+    with the Q-bump, and those with both."""
+    out = (C.c_long * 6)()
+    both = (C.c_long * 2)()
+    lib().orc_branch_counts_ex(out, both)
+    return {f: dict(updates=out[3 * i], nonpd=out[3 * i + 1], bump=out[3 * i + 2], both=both[i])
+            for i, f in enumerate(("ob", "mb"))}
 
 
 def sigma_min(G):

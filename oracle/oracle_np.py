@@ -1107,7 +1107,8 @@ def _run_cell(rom, SOC0, TC, nsteps, cfg, record_state, tc_traj=None):
     c = dict(RUNMPC_DEFAULTS)
     if cfg:
         c.update(cfg)
-    SigmaX0 = np.diag([1.0] * rom.n + [2e6])
+    # runMPC.m's SigmaX0, or cfg["SigmaX0"]: the n + 1 diagonal entries (oracle_c.make_cfg's form)
+    SigmaX0 = np.diag(np.asarray(c.get("SigmaX0", [1.0] * rom.n + [2e6]), dtype=float))
     hm = bool(c.get("handles", False))   # cellData.function handles called directly (Cell)
     ekf = init_kf(rom, SOC0, TC, SigmaX0, c["SigmaV"], c["SigmaW"], c.get("method", "OB"), hm)
     mpc = init_mpc(rom, SOC0, c["Np"], c["Nc"], c["targetSOC"], c)

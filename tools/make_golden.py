@@ -50,6 +50,27 @@ def make_mb(rom, hsh):
     np.savez_compressed(os.path.join(OUT, "mb_batch4_200.npz"), rom_hash=hsh, soc0=soc0, tc=tc, **r)
 
 
+BRANCH_CASES = (("branch_sigv_8x100", {"SigmaV": 1e-5}),
+                ("branch_x0zero_ob_8x100", {"SigmaX0": (0.0, 0.0, 0.0, 0.0, 0.0, 2e6)}),
+                ("branch_x0zero_mb_8x100", {"SigmaX0": (0.0, 0.0, 0.0, 0.0, 0.0, 2e6), "method": "MB"}))
+
+
+def make_branches(rom, hsh):
+    """The measurement update's Jacobi symmetrisation and Q-bump (iterEKF.m:141-151 / 164-173),
+    which runMPC.m's filter tuning never reaches: 8 cells of the batched workload x 100 steps
+    with initKF arguments that do (a small SigmaV: non-PD updates and bumps; a zero SigmaX0:
+    non-PD updates from the first step on, OB and MB).  LAPACK svd, no PD shortcut.  Each
+    file stores its SigmaV, SigmaW, SigmaX0 and method."""
+    rng = np.random.Generator(np.random.PCG64(0x5EED))
+    soc0, tc = rng.uniform(5, 30, 8), rng.uniform(20, 30, 8)
+    for name, cfg in BRANCH_CASES:
+        r = run_cells(rom, soc0, tc, 100, cfg)
+        np.savez_compressed(os.path.join(OUT, name + ".npz"), rom_hash=hsh, soc0=soc0, tc=tc,
+                            SigmaV=cfg.get("SigmaV", O.RUNMPC_DEFAULTS["SigmaV"]), SigmaW=O.RUNMPC_DEFAULTS["SigmaW"],
+                            SigmaX0=np.array(cfg.get("SigmaX0", (1.0, 1.0, 1.0, 1.0, 1.0, 2e6))),
+                            method=cfg.get("method", "OB"), **r)
+
+
 def tprofile(steps):
     k = np.arange(steps)[:, None]
     base = np.array([[20.0, 25.0, 10.0, 30.0]])
@@ -349,6 +370,13 @@ def main():
         make_tab_handles()
         print(f"lookup-table handle fixtures written in {time.time() - t0:.0f} s")
         return
+    if "--branches-only" in sys.argv:
+        P = importlib.import_module("mpc-ekf4fastcharge_amd")
+        rom = P.make_synth_rom()
+        t0 = time.time()
+        make_branches(rom, rom_hash(rom))
+        print(f"EKF branch fixtures written in {time.time() - t0:.0f} s")
+        return
     if "--handles-only" in sys.argv:
         t0 = time.time()
         make_handles()
@@ -404,6 +432,8 @@ def main():
                         tc=[25.0, 22.0], **r)
     # 5. model-blend EKF variant
     make_mb(rom, hsh)
+    # 5a. filter tunings that reach the Jacobi symmetrisation and the Q-bump
+    make_branches(rom, hsh)
     # 5b. a temperature profile per step (OB_step / iterEKF / EKFmatsHandler take Tc every
     #     call): warming ramps with a ripple, one profile crossing a set-point and the table
     #     grid ends (0 and 50 degC, clamped), 300 steps
