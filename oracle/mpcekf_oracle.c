@@ -1548,8 +1548,18 @@ void orc_mpc_step(const orc_rom *r, const orc_cfg *cf, orc_cell *s, const orc_li
 /* iterMPC.m:17-95 on given EKFmatsHandler records (the 35-double layout of orc_lin,
  * include/mpcekf.h MPCEKF_LIN_*): open-loop parity of the MPC stage.  uk_1 and lam
  * ([n][nC]) are the mpcData state in and out. */
+int orc_mpc_lin_ex(const orc_rom *r, const orc_cfg *c, int n, const double *lin, const double *soc_k1, double *uk_1,
+                   double *lam, double *uk, int32_t *nexec, double *J_unc, double *J_fin, double *norm_du,
+                   int32_t *nviol);
 int orc_mpc_lin(const orc_rom *r, const orc_cfg *c, int n, const double *lin, const double *soc_k1, double *uk_1,
                 double *lam, double *uk, int32_t *nexec) {
+  return orc_mpc_lin_ex(r, c, n, lin, soc_k1, uk_1, lam, uk, nexec, 0, 0, 0, 0);
+}
+
+/* orc_mpc_lin with each call's mpcData.cost row (iterMPC.m:89-95; any of the four may be null) */
+int orc_mpc_lin_ex(const orc_rom *r, const orc_cfg *c, int n, const double *lin, const double *soc_k1, double *uk_1,
+                   double *lam, double *uk, int32_t *nexec, double *J_unc, double *J_fin, double *norm_du,
+                   int32_t *nviol) {
   if (c->Np > NPMAX || c->Nc > NCMAX) return -10;
   const int nC = (c->use_cur ? 4 * c->Nc : 0) + (c->use_v ? c->Np : 0) + (c->use_eta ? c->Np : 0) + c->Np;
   for (int i = 0; i < n; ++i) {
@@ -1563,6 +1573,10 @@ int orc_mpc_lin(const orc_rom *r, const orc_cfg *c, int n, const double *lin, co
     orc_mpc_step(r, c, &s, &L, soc_k1[i], &o);
     uk[i] = o.uk;
     nexec[i] = o.nexec;
+    if (J_unc) J_unc[i] = o.J_unc;
+    if (J_fin) J_fin[i] = o.J_fin;
+    if (norm_du) norm_du[i] = o.norm_du;
+    if (nviol) nviol[i] = o.nviol;
     uk_1[i] = s.uk_1;
     for (int j = 0; j < nC; ++j) lam[(size_t)i * nC + j] = s.lam[j];
   }

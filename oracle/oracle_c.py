@@ -101,6 +101,8 @@ def lib():
                                    _dp, _dp, _dp, _dp, _ip, _ip, _dp, _dp, C.POINTER(_Traj), C.c_int]
         L.orc_mpc_lin.restype = C.c_int
         L.orc_mpc_lin.argtypes = [C.POINTER(_Rom), C.POINTER(_Cfg), C.c_int, _dp, _dp, _dp, _dp, _dp, _ip]
+        L.orc_mpc_lin_ex.restype = C.c_int
+        L.orc_mpc_lin_ex.argtypes = L.orc_mpc_lin.argtypes + [_dp, _dp, _dp, _ip]
         L.orc_sigma_min.restype = C.c_double
         L.orc_sigma_min.argtypes = [C.c_int, _dp]
         L.orc_meas_cov.argtypes = [_dp, _dp, C.c_double, C.c_int]
@@ -253,9 +255,10 @@ def run(rom, soc0, tc, nsteps, nthreads=0, want_zk=False, traj=False, tc_traj=No
     return out
 
 
-def mpc_lin(rom, lin, soc_k1, uk_1, lam, **cfg):
+def mpc_lin(rom, lin, soc_k1, uk_1, lam, cost=False, **cfg):
     """iterMPC.m on given linearisation records [n, 35]; uk_1 [n] and lam [n, ncon] are the
-    mpcData state (copied).  Returns uk, nexec, uk_1 after, lam after."""
+    mpcData state (copied).  Returns uk, nexec, uk_1 after, lam after; with cost=True also
+    each call's mpcData.cost row (iterMPC.m:89-95) as a dict of J_uncon, J_final, norm_DU, viol."""
     lin = np.ascontiguousarray(lin, dtype=np.float64)
     n = lin.shape[0]
     pr = PackedRom(rom)
@@ -264,10 +267,14 @@ def mpc_lin(rom, lin, soc_k1, uk_1, lam, **cfg):
     lm = np.array(lam, dtype=np.float64, order="C")
     uk = np.empty(n)
     ne = np.empty(n, dtype=np.int32)
-    rc = lib().orc_mpc_lin(C.byref(pr.s), C.byref(c), n, _p(lin), _p(np.ascontiguousarray(soc_k1, dtype=np.float64)),
-                           _p(u1), _p(lm), _p(uk), ne.ctypes.data_as(_ip))
+    ju, jf, nd, nv = np.empty(n), np.empty(n), np.empty(n), np.empty(n, dtype=np.int32)
+    rc = lib().orc_mpc_lin_ex(C.byref(pr.s), C.byref(c), n, _p(lin), _p(np.ascontiguousarray(soc_k1, dtype=np.float64)),
+                              _p(u1), _p(lm), _p(uk), ne.ctypes.data_as(_ip), _p(ju), _p(jf), _p(nd),
+                              nv.ctypes.data_as(_ip))
     if rc:
         raise RuntimeError(f"orc_mpc_lin failed: {rc}")
+    if cost:
+        return uk, ne, u1, lm, dict(J_uncon=ju, J_final=jf, norm_DU=nd, viol=nv)
     return uk, ne, u1, lm
 
 

@@ -303,8 +303,10 @@ def test_flush_period_is_exact(rom, M):
 def test_mpc_stage_edge_records(rom, oc, M):
     """iterMPC (Np = 5, k_cell's MPC part + k_hild / k_hild_slow) on linearisation records
     built to leave the fast rank-2 sweep, next to plain ones: overflowing and infinite G
-    rows, H_ii outside [2^-400, 2^400], a NaN bound.  uk, nexec and lambda bitwise against
-    the oracle (NaN where the oracle has NaN)."""
+    rows, H_ii outside [2^-400, 2^400], a NaN bound, NaN / overflowing SOC columns (a NaN E:
+    mpc_setup's DU is NaN and the cell ends without a QP; the E Cholesky rejects inside a QP
+    is test_gpu_switches_edges.py::test_indefinite_E_matches_oracle's).  uk, nexec and lambda
+    bitwise against the oracle (NaN where the oracle has NaN)."""
     n = 64
     soc0, tc = batch_inputs(n, seed=51)
     with M.Context(rom, n) as ctx:
@@ -324,9 +326,13 @@ def test_mpc_stage_edge_records(rom, oc, M):
         lin[g == 3, 20:26] = np.inf    # Cphi: G_e rows non-finite
         lin[g == 4, 27] = np.nan       # bv: a NaN bound
         lin[g == 5, 13:20] *= 1e-170   # G_v rows tiny: H_ii below 2^-400
+        six = np.nonzero(g == 6)[0]    # the SOC columns: F, E and DU = -E\\F NaN, no QP, uk NaN
+        lin[six[0::2], 12] = np.nan    # Dsoc
+        lin[six[1::2], 6:13] *= 1e160  # Csoc, Dsoc: G_soc' G_soc overflows
         zend = zk[:, -1]
         st = ctx.get_state()
         uk_r, ne_r, _, lam_r = oc.mpc_lin(rom, lin, zend, st["scal"][:, 5], st["lam"])
+        assert np.isnan(uk_r[six]).all() and (ne_r[six] == 0).all()
         uk, ne = ctx.iterMPC(lin, zend)
         lam = ctx.get_state()["lam"]
     for k, (a, b) in {"uk": (uk, uk_r), "lam": (lam, lam_r)}.items():

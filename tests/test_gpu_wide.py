@@ -130,6 +130,78 @@ def test_wide_mpc_stage_edge_records(rom, oc, M):
     np.testing.assert_array_equal(ne, ne_r)
 
 
+DU_MAX_NEG = -1e7   # Ru = |F| / (2 du_max sqrt(Nc)) - sigma_min < -sigma_min: E finite, indefinite
+
+
+def test_wide_mpc_stage_rejected_E(rom, oc, M):
+    """iterMPC at Np = 20 / Nc = 10 on an E that Cholesky rejects, next to plain cells; uk,
+    nexec and lambda bitwise against oc.mpc_lin(..., Np=20, Nc=10).
+
+    Group 6 (cell % 8 == 6), alternating Dsoc = NaN and the SOC columns times 1e160: Hs, F,
+    G'G, Ru and E are NaN, so DU = -E\\F (mpcekf_wide.hip:243) is NaN, no row test `acc - g > 0`
+    (:259, :282, :306, :319) holds and k_mpc_wide returns at :324-335 with hflag = 0 (:168):
+    both variants are no-QP cells with uk NaN and never reach k_hild_prep -- the oracle alone
+    says the same (nexec = 0; tests/test_switches_oracle.py).  No edit of the SOC columns gives
+    a non-SPD E with a non-NaN DU, so the input that does reach hflag = 3 is a negative du_max:
+    the input weight Ru falls below -sigma_min(G'G), E = 2 (G'G + Ru I) is finite and indefinite
+    on every cell, k_mpc_wide sets hflag = 1 (:337), k_hild_prep's chol_n rejects E and sets
+    hflag = 3 (:418-419), and k_hild_wide_slow rebuilds K, X and H_ii by lu_solve_n (:975-1000).
+    Group 7: lambda0 = inf in the last G_soc row, zk(end) at 0.9497 so that the SOC rows bind
+    (hflag 1 -> the exact path)."""
+    n = 64
+    soc0, tc = batch_inputs(n, seed=49)
+    with M.Context(rom, n, _cfg(M)) as ctx:
+        ctx.init_cells(soc0, tc)
+        uk = np.zeros(n)
+        for _ in range(4):
+            v = ctx.OB_step(uk)
+            zk, _, xind = ctx.iterEKF(v, uk)
+            lin = ctx.EKFmatsHandler(zk, xind)
+            uk, _ = ctx.iterMPC(lin, zk[:, -1])
+        v = ctx.OB_step(uk)
+        zk, _, xind = ctx.iterEKF(v, uk)
+        clean = np.array(ctx.EKFmatsHandler(zk, xind), dtype=np.float64)
+        st = ctx.get_state()
+        g = np.arange(n) % 8
+        lin = clean.copy()
+        six = np.nonzero(g == 6)[0]
+        lin[six[0::2], 12] = np.nan     # Dsoc
+        lin[six[1::2], 6:13] *= 1e160   # Csoc, Dsoc
+        zend = zk[:, -1].copy()
+        zend[g == 7] = 0.9497
+        lam0 = st["lam"].copy()
+        lam0[g == 7, -1] = np.inf
+        ctx.set_state(dict(st, lam=lam0))
+        uk_r, ne_r, _, lam_r = oc.mpc_lin(rom, lin, zend, st["scal"][:, 5], lam0, Np=NP, Nc=NC)
+        uk, ne = ctx.iterMPC(lin, zend)
+        lam = ctx.get_state()["lam"]
+    assert (ne_r[six] == 0).all() and np.isnan(uk_r[six]).all() and (ne_r[g == 7] > 0).all()
+    print(f"\nWIDE g6 nexec {ne[six].tolist()} g7 nexec {ne[g == 7].tolist()}")
+    for k, (a, b) in {"uk": (uk, uk_r), "lam": (lam, lam_r)}.items():
+        assert np.array_equal(a, b, equal_nan=True), (k, np.nonzero(~((a == b) | (np.isnan(a) & np.isnan(b))))[0][:8])
+    np.testing.assert_array_equal(ne, ne_r)
+    # the finite indefinite E: the clean record and state through a du_max < 0 context
+    import oracle_np
+    for c in range(0, n, 8):
+        _, G = oracle_np.pred_mat(clean[c, 0:6], clean[c, 6:12], clean[c, 12], NP, NC)
+        e = 95.0 - oracle_np.pred_mat(clean[c, 0:6], clean[c, 6:12], clean[c, 12], NP, NC)[0] @ np.append(clean[c, 29:35], st["scal"][c, 5])
+        GtG = G.T @ G
+        Ru = np.linalg.norm(-2 * G.T @ e) / (2 * DU_MAX_NEG * np.sqrt(NC)) - np.linalg.eigvalsh(GtG)[0]
+        assert np.linalg.eigvalsh(2 * (GtG + Ru * np.eye(NC)))[0] < 0, c
+    with M.Context(rom, n, _cfg(M, du_max=DU_MAX_NEG)) as ctx:
+        ctx.init_cells(soc0, tc)
+        ctx.set_state(st)
+        uk_r, ne_r, _, lam_r = oc.mpc_lin(rom, clean, zk[:, -1], st["scal"][:, 5], st["lam"], Np=NP, Nc=NC,
+                                          du_max=DU_MAX_NEG)
+        uk, ne = ctx.iterMPC(clean, zk[:, -1])
+        lam = ctx.get_state()["lam"]
+    assert (ne_r > 0).all()   # every cell set up a QP (hflag 1 -> 3)
+    print(f"WIDE du_max<0 nexec {int(ne.min())}..{int(ne.max())}")
+    for k, (a, b) in {"uk": (uk, uk_r), "lam": (lam, lam_r)}.items():
+        assert np.array_equal(a, b, equal_nan=True), (k, np.nonzero(~((a == b) | (np.isnan(a) & np.isnan(b))))[0][:8])
+    np.testing.assert_array_equal(ne, ne_r)
+
+
 def test_wide_stage_entry_points_match_fused(rom, M):
     n, steps = 128, 12
     soc0, tc = batch_inputs(n, seed=43)
