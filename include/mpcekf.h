@@ -410,6 +410,41 @@ int mpcekf_get_hild_problems(mpcekf_ctx *ctx, double *prob, int32_t *hflag);
 #define MPCEKF_NSTAMPS 20
 int mpcekf_get_stamps(mpcekf_ctx *ctx, int64_t *stamps, int32_t *nstamps);
 
+/* ---- per-cell MPC limits and targets (the charging protocol of runMPC.m:30-44 per cell) ----
+ * mpcekf_config holds one targetSOC, C-rate and limits set for the whole context.  These
+ * entry points give cells of one context their own: a protocol sweep (phise_min against
+ * v_max against C-rate), per-cell targets in a pack.  The field ids name mpcekf_config's
+ * fields, in its units. */
+enum {
+  MPCEKF_LIM_TARGET_SOC = 0, MPCEKF_LIM_CRATE, MPCEKF_LIM_U_MAX, MPCEKF_LIM_DU_MIN, MPCEKF_LIM_DU_MAX,
+  MPCEKF_LIM_V_MAX, MPCEKF_LIM_PHISE_MIN, MPCEKF_LIM_Z_MAX, MPCEKF_LIM_Z_TOL, MPCEKF_NLIM
+};
+/* mpcData.ref and mpcData.const of runMPC.m:30-44 per cell: fields[nfields] are distinct
+ * MPCEKF_LIM_* ids, values [nfields][ncells] (row i = field fields[i] of every cell).  A
+ * field never named keeps the context's scalar.  The MPC kernels read u_min = -Q * Crate
+ * (initMPC.m:66-67) and zmax = z_max + z_tol (constraintsMPC.m:90-91), formed on the host by
+ * the expressions the scalar configuration goes through, so arrays constant at the
+ * configuration's values give the bits of the scalar context.  May be called at any point
+ * after mpcekf_ctx_create, mid-charge included; ordered on the context's stream, it takes
+ * effect at the next MPC stage (the fused step, mpcekf_mpc_step(_ex)(_async), mpcekf_mpc_diag)
+ * and leaves the stage route's device-resident zk / Xind / lin records valid.  No value is
+ * refused (mpcekf_ctx_create checks none of these fields either).  Np = 5 / Nc = 2 takes
+ * every constraint mask; Np = 20 / Nc = 10 all three switches on, as ever.  The first call
+ * moves the context to the split launch sequence and retires its captured
+ * graphs; later calls rewrite the same device buffer.  MPCEKF_E_ARG: a NULL pointer, nfields
+ * outside 1..MPCEKF_NLIM, an unknown or repeated field id.
+ * The context-free mpcekf_constraints / mpcekf_predmat / mpcekf_hildreth* keep their scalar
+ * mpcekf_config. */
+int mpcekf_set_limits(mpcekf_ctx *ctx, int32_t nfields, const int32_t *fields, const double *values);
+/* The values in force, values [nfields][ncells]: what mpcekf_set_limits stored, the
+ * configuration's scalar (broadcast) for a field never set or after mpcekf_clear_limits
+ * (runMPC.m:30-44 / initMPC.m:66-67 / constraintsMPC.m:90-91 in mpcekf_config's terms). */
+int mpcekf_get_limits(mpcekf_ctx *ctx, int32_t nfields, const int32_t *fields, double *values);
+/* Back to the configuration's scalars of runMPC.m:30-44 (initMPC.m:66-67,
+ * constraintsMPC.m:90-91) and to the launch sequence the context had before its first
+ * mpcekf_set_limits; a no-op on a context that never set any. */
+int mpcekf_clear_limits(mpcekf_ctx *ctx);
+
 /* ---- device memory (not part of the reference interface) ----
  * Device buffers for outputs_on_device calls, allocated by the library's own HIP
  * runtime so a host process never holds a second one (a framework's bundled

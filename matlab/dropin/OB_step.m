@@ -42,6 +42,10 @@ function [Vcell, obs, cellState] = OB_step(Iapp, Tc, cellState, ROM, initCfg)
     h = mpcekf_mex('create', R, cfg, S.device, n);
     mpcekf_session('set', 'h', h);
     mpcekf_mex('init', h, reshape(initCfg.SOC0, 1, n), Tc .* ones(1, n));
+    % initMPC's vector-valued targetSOC / Crate / limits: one entry per cell (runMPC.m:30-44)
+    if isfield(S.mpc, 'mpcekf_limits') && ~isempty(S.mpc.mpcekf_limits.idx)
+      mpcekf_mex('setlimits', h, S.mpc.mpcekf_limits.idx, S.mpc.mpcekf_limits.values);
+    end
     fn = ROM.cellData.function.neg;
     cellState = struct('initialized', true, 'h', h, 'n', n, 'Ts', ROM.xraData.Tsamp, ...
                        'theta0n', fn.theta0(), 'theta100n', fn.theta100(), 'tab_error', terr);

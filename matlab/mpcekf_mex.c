@@ -43,6 +43,14 @@
  *                       SOCnAvg/SOCpAvg, 3 x0, 4 SigmaX0, 5 priorI, 6 uk_1, 7 uk, 8 vk):
  *                       what the drop-ins read every step, 8 B per slot and cell
  *                       mpcekf_mex('graph', h, enable)                 mpcekf_set_graph (replay repeated step calls)
+ *                       mpcekf_mex('setlimits', h, idx, values)        mpcekf_set_limits (runMPC.m:30-44 per cell)
+ *                       idx: 1-based MPCEKF_LIM_* field numbers (1 target_soc, 2 Crate, 3 u_max,
+ *                       4 du_min, 5 du_max, 6 v_max, 7 phise_min, 8 z_max, 9 z_tol), each once;
+ *                       values: ncells x numel(idx), column j = field idx(j) of every cell, in
+ *                       the cfg struct's units.  A field not named keeps what it had
+ *   values            = mpcekf_mex('getlimits', h, idx)                mpcekf_get_limits
+ *                       ncells x numel(idx): what 'setlimits' stored, else the cfg scalar
+ *                       mpcekf_mex('clearlimits', h)                   mpcekf_clear_limits
  * Per-cell vectors are 1 x ncells or ncells x 1; zk / zbk are (nz+2) x ncells, xm / xg
  * 4 x ncells (xm: 0-based model index t*nZ+z), lin 35 x ncells -- MATLAB's column-major
  * k x ncells is the library's cell-major [ncells][k], so no copy is made for them.
@@ -356,7 +364,8 @@ static void gateway(mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
   }
   static const char *const with_handle[] = {"destroy", "init", "step", "plant", "ekf", "linearize", "mpc",
                                             "graph", "mpcdiag", "get_state", "set_state", "scalars", "linfields",
-                                            "plantobs", "obsslots", "obslayout", "stepobs"};
+                                            "plantobs", "obsslots", "obslayout", "stepobs", "setlimits", "getlimits",
+                                            "clearlimits"};
   int known = 0;
   for (size_t i = 0; i < sizeof with_handle / sizeof *with_handle; ++i) known = known || !strcmp(cmd, with_handle[i]);
   if (!known) mexErrMsgIdAndTxt("mpcekf:arg", "unknown command %s", cmd);
@@ -377,6 +386,31 @@ static void gateway(mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
     for (size_t j = 0; j < k; ++j)
       if (!(idx[j] >= 1 && idx[j] <= 2147483647.0) || idx[j] != (double)(int32_t)idx[j])
         mexErrMsgIdAndTxt("mpcekf:arg", "%s: idx(%zu) = %g is not a slot 1..nobs", cmd, j + 1, idx[j]);
+  }
+  /* the limits commands likewise: output count, field numbers 1..MPCEKF_NLIM, each once */
+  const int setlim = !strcmp(cmd, "setlimits"), getlim = !strcmp(cmd, "getlimits");
+  int32_t limf[MPCEKF_NLIM];
+  size_t nlimf = 0;
+  if (!strcmp(cmd, "clearlimits") && g_nlhs > 0) mexErrMsgIdAndTxt("mpcekf:arg", "clearlimits: no output");
+  if (setlim || getlim) {
+    if (setlim && g_nlhs > 0) mexErrMsgIdAndTxt("mpcekf:arg", "setlimits: no output");
+    if (getlim && g_nlhs > 1) mexErrMsgIdAndTxt("mpcekf:arg", "getlimits: at most 1 output");
+    if (setlim) need(nrhs, 4, "'setlimits', h, idx, values");
+    else need(nrhs, 3, "'getlimits', h, idx");
+    nlimf = mxGetNumberOfElements(prhs[2]);
+    if (nlimf < 1 || nlimf > MPCEKF_NLIM)
+      mexErrMsgIdAndTxt("mpcekf:arg", "%s: idx: expected 1..%d field numbers", cmd, (int)MPCEKF_NLIM);
+    const double *idx = dvec(prhs[2], nlimf, "idx");
+    unsigned seen = 0;
+    for (size_t j = 0; j < nlimf; ++j) {
+      if (!(idx[j] >= 1 && idx[j] <= MPCEKF_NLIM) || idx[j] != (double)(int)idx[j])
+        mexErrMsgIdAndTxt("mpcekf:arg", "%s: idx(%zu) = %g is not a field 1..%d", cmd, j + 1, idx[j], (int)MPCEKF_NLIM);
+      limf[j] = (int32_t)idx[j] - 1;
+      if (seen >> limf[j] & 1) mexErrMsgIdAndTxt("mpcekf:arg", "%s: idx(%zu) = %g is given twice", cmd, j + 1, idx[j]);
+      seen |= 1u << limf[j];
+    }
+    if (setlim && (!mxIsDouble(prhs[3]) || mxIsComplex(prhs[3])))
+      mexErrMsgIdAndTxt("mpcekf:arg", "setlimits: values: expected a real double ncells x %zu array", nlimf);
   }
   mpcekf_ctx *h = handle(prhs[1]);
   int64_t n = 0;
@@ -525,6 +559,14 @@ static void gateway(mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
   } else if (!strcmp(cmd, "graph")) {
     if (nrhs < 3) mexErrMsgIdAndTxt("mpcekf:arg", "graph: enable flag");
     chk(mpcekf_set_graph(h, (int32_t)(mxGetScalar(prhs[2]) != 0.0)));
+  } else if (setlim) {
+    /* ncells x numel(idx) column-major is the library's [nfields][ncells] as it stands */
+    chk(mpcekf_set_limits(h, (int32_t)nlimf, limf, dvec(prhs[3], nc * nlimf, "setlimits: values (ncells x numel(idx))")));
+  } else if (getlim) {
+    plhs[0] = dmat(nc, nlimf);
+    chk(mpcekf_get_limits(h, (int32_t)nlimf, limf, mxGetDoubles(plhs[0])));
+  } else if (!strcmp(cmd, "clearlimits")) {
+    chk(mpcekf_clear_limits(h));
   } else if (!strcmp(cmd, "mpcdiag")) {
     need(nrhs, 3, "'mpcdiag', h, lin[, uk_1]");
     plhs[0] = mxCreateDoubleMatrix(7, (mwSize)nc, mxCOMPLEX);  /* interleaved (re, im): [ncells][7][2] */

@@ -23,6 +23,8 @@ MB_SIZE = 42
 METHOD_OB, METHOD_MB = 0, 1
 S_SOCNAVG, S_SOCPAVG, S_X0, S_SIGMAX0, S_PRIORI, S_UK_1, S_UK, S_VK = range(8)
 OBS_COUNT = 25   # MPCEKF_OBS_COUNT: the fields of OB_step's obs (rom.py OBS_FIELDS)
+# MPCEKF_LIM_*: the per-cell limit fields of mpcekf_set_limits, by mpcekf_config's field names
+LIMIT_FIELDS = ("target_soc", "Crate", "u_max", "du_min", "du_max", "v_max", "phise_min", "z_max", "z_tol")
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
@@ -83,6 +85,7 @@ EXPORTS = [
     "mpcekf_dev_alloc", "mpcekf_dev_free", "mpcekf_dev_copy", "mpcekf_dev_copy2d", "mpcekf_sync",
     "mpcekf_get_scalars", "mpcekf_lin_fields",
     "mpcekf_obs_layout", "mpcekf_plant_step_obs", "mpcekf_plant_obs_slots", "mpcekf_step_ex_obs",
+    "mpcekf_set_limits", "mpcekf_get_limits", "mpcekf_clear_limits",
     # the _async stage twins (include/mpcekf.h)
     "mpcekf_plant_step_async", "mpcekf_ekf_step_async", "mpcekf_linearize_async", "mpcekf_lin_fields_async",
     "mpcekf_mpc_step_async", "mpcekf_mpc_step_ex_async", "mpcekf_mpc_diag_async", "mpcekf_get_scalars_async",
@@ -149,6 +152,9 @@ def load():
     L.mpcekf_obs_layout.argtypes = [vp, _ip]
     L.mpcekf_plant_step_obs.argtypes = [vp, _dp, _dp, _dp, _dp]
     L.mpcekf_plant_obs_slots.argtypes = [vp, _ip, C.c_int32, _dp]
+    L.mpcekf_set_limits.argtypes = [vp, C.c_int32, _ip, _dp]
+    L.mpcekf_get_limits.argtypes = [vp, C.c_int32, _ip, _dp]
+    L.mpcekf_clear_limits.argtypes = [vp]
     for nm in ("plant_step", "ekf_step", "linearize", "lin_fields", "mpc_step", "mpc_step_ex", "mpc_diag",
                "get_scalars", "plant_step_obs", "plant_obs_slots"):   # the _async twins take the synchronous call's arguments
         getattr(L, f"mpcekf_{nm}_async").argtypes = getattr(L, f"mpcekf_{nm}").argtypes

@@ -214,6 +214,14 @@ struct mpcekf_ctx {
   bool wide = false;
   KWide w{};
   double *d_lin = nullptr, *d_zsoc = nullptr;  // [n][35], [n]
+  // mpcekf_set_limits (runMPC.m:30-44 per cell): h_lim [MPCEKF_NLIM][n] in mpcekf_config's
+  // units (what mpcekf_get_limits returns; empty until the first set), d_lim [NLIMK][n] the
+  // kernels' record, allocated by the first set and kept to the end (a captured graph may name
+  // it).  percell: the MPC stages launch the per-cell kernel variants
+  std::vector<double> h_lim;
+  double *d_lim = nullptr;
+  bool percell = false;
+  const double *lim() const { return percell ? d_lim : nullptr; }
   double *d_uk1p = nullptr;                      // [n] uk_1 before the step (poles / sv)
   int flush_period = LAZY_H;      // steps between all-model flushes (<= LAZY_H)
   // rolling flush (MPCEKF_FLUSH_ROLL=1, off by default): step t flushes the cell slice
@@ -1087,7 +1095,7 @@ int mpcekf_ctx_destroy(mpcekf_ctx *X) {
                   X->d_zbk,       X->d_tmp,        X->s.bigx, X->s.ekf,   X->s.lam,   X->d_ts, X->d_hist, X->d_stamps, X->d_bnd, X->d_xm, X->d_xg,
                   X->w.prob, X->w.X, X->w.R, X->w.K, X->w.hii, X->w.it, X->w.smin, X->d_lin, X->d_zsoc, X->d_mb, X->d_uk1p,
                   X->w.q, X->w.list, X->w.hist, X->d_poly, X->d_szk, X->d_sxg, X->d_sxm, X->d_slin, X->d_sv, X->d_zslot,
-                  X->d_obs_blob, X->d_obs, X->d_obs_plan};
+                  X->d_obs_blob, X->d_obs, X->d_obs_plan, X->d_lim};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   for (auto &g : X->graphs) (void)hipGraphExecDestroy(g.exec);
@@ -1211,12 +1219,16 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
   if (tr->zbk && !bounds) return fail(MPCEKF_E_ARG, "step_ex: a boundzk trajectory needs MPCEKF_CF_BOUNDS");
   // boundzk in k_cell itself, or from its hand-off record in k_bounds (the lane-quad
   // k_ekf4 path writes only the record; MB writes boundzk in k_cell)
-  const bool bnd_kernel = bounds && !X->mb && (!cell_computes_bounds() || X->quad);
+  // per-cell limits (mpcekf_set_limits): the split route at every batch size, no k_ekf4 mapping
+  const double *lim = X->lim();
+  const bool quad = X->quad && !lim, split_cell = X->split_cell && !lim;
+  const bool bnd_kernel = bounds && !X->mb && (!cell_computes_bounds() || quad);
   // OB_step's simStep inside k_cell (KRom::cell_plant): no k_plant launch
   const bool plant_in_cell = X->r.cell_plant && !X->mb;  // k_cell, or k_ekf4's lane quad (quad_plant)
   // hildreth.m at the end of k_cell (Np = 5, one k_cell per step): no k_hild launch
-  const bool switched = X->sw != 7;  // a constraint block off: the split route of mpcekf_switch.hip
-  const bool hild_in_cell = cell_runs_hild() && !X->wide && !X->split_cell && !X->quad && !switched;
+  // a constraint block off, or per-cell limits at Np = 5: the split route of mpcekf_switch.hip
+  const bool switched = X->sw != 7 || (lim && !X->wide);
+  const bool hild_in_cell = cell_runs_hild() && !X->wide && !split_cell && !quad && !switched;
   const size_t n = (size_t)X->n, per = n * (size_t)nsteps, nzz = (size_t)X->nz + 2;
   // the output fields, their element size and elements per cell-step
   struct F {
@@ -1366,14 +1378,14 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
         iow.normdu_out = io.normdu_out;
         iow.nviol_out = io.nviol_out;
         if (switched) {
-          if ((rc = lerr(launch_mpc_sw(X->sw, X->k, X->s, iow, X->stream), "mpc_sw"))) return rc;
-        } else if ((rc = lerr(launch_mpc_wide(X->k, X->s, iow, X->w, X->stream), "mpc_wide"))) {
+          if ((rc = lerr(launch_mpc_sw(X->sw, X->k, X->s, iow, X->stream, lim), "mpc_sw"))) return rc;
+        } else if ((rc = lerr(launch_mpc_wide(X->k, X->s, iow, X->w, X->stream, lim), "mpc_wide"))) {
           return rc;
         }
-      } else if (X->split_cell || X->quad) {  // iterEKF, then EKFmatsHandler + iterMPC from zk and Xind in HBM
+      } else if (split_cell || quad) {  // iterEKF, then EKFmatsHandler + iterMPC from zk and Xind in HBM
         io.xm_out = X->d_xm;
         io.xg_out = X->d_xg;
-        if (X->quad) {
+        if (quad) {
           if ((rc = lerr(launch_ekf4(X->r, X->k, X->s, io, X->stream, X->ekf4_block), "ekf4"))) return rc;
         } else if ((rc = lerr(launch_cell(X->r, X->k, X->s, io, X->stream, P_EKF), "cell"))) {
           return rc;
@@ -1425,6 +1437,8 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
       if (E) HIPCHK(hipEventRecord(E[hstart], X->stream));
       if (X->wide) {
         if ((rc = lerr(launch_hild_wide(X->k, X->s, iow, X->w, X->stream), "hild_wide"))) return rc;
+      } else if (switched && X->sw == 7) {  // per-cell, every switch on: k_mpc_pc<7> left k_cell's hand-off
+        if ((rc = lerr(launch_hild(X->k, X->s, iow, X->stream), "hild"))) return rc;
       } else if (switched) {
         if ((rc = lerr(launch_hild_sw(X->sw, X->k, X->s, iow, X->stream), "hild_sw"))) return rc;
       } else if (!hild_in_cell && (rc = lerr(launch_hild(X->k, X->s, io, X->stream), "hild"))) {
@@ -1432,8 +1446,8 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
       }
       if (diag) {
         double *pk = (double *)row(12, k), *sk = (double *)row(13, k);
-        rc = X->wide ? launch_cl_diag_wide(X->k, X->n, X->d_lin, X->d_uk1p, pk, sk, X->stream)
-                     : launch_cl_diag(X->k, X->n, X->d_lin, X->d_uk1p, pk, sk, X->stream);
+        rc = X->wide ? launch_cl_diag_wide(X->k, X->n, X->d_lin, X->d_uk1p, pk, sk, X->stream, lim)
+                     : launch_cl_diag(X->k, X->n, X->d_lin, X->d_uk1p, pk, sk, X->stream, lim);
         if ((rc = lerr(rc, "cl_diag"))) return rc;
       }
       if (E) HIPCHK(hipEventRecord(E[4], X->stream));
@@ -1458,6 +1472,7 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
     for (const F &e : f) key.push_back((uintptr_t)e.dev);
     key.push_back((uintptr_t)osel.plan);  // a regrown plan buffer retires the graphs that named the old one
     key.push_back((uintptr_t)nslots);
+    key.push_back((uintptr_t)lim);  // set / clear change the launch sequence: graphs of the other one are not replayed
     for (int i = 0; i < nslots; ++i) key.push_back((uintptr_t)slots[i]);
     if ((rc = X->graph_launch(key, run_steps))) return rc;
   } else if ((rc = run_steps())) {
@@ -1530,6 +1545,97 @@ int mpcekf_step(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, double *tr
 int mpcekf_set_graph(mpcekf_ctx *X, int32_t enable) {
   if (!X) return fail(MPCEKF_E_ARG, "null ctx");
   X->graph = enable != 0;
+  return MPCEKF_OK;
+}
+
+// ---- per-cell limits (runMPC.m:30-44 / initMPC.m:66-67 / constraintsMPC.m:90-91 per cell) ----
+static double cfg_limit(const mpcekf_config &c, int f) {
+  switch (f) {
+    case MPCEKF_LIM_TARGET_SOC: return c.target_soc;
+    case MPCEKF_LIM_CRATE: return c.Crate;
+    case MPCEKF_LIM_U_MAX: return c.u_max;
+    case MPCEKF_LIM_DU_MIN: return c.du_min;
+    case MPCEKF_LIM_DU_MAX: return c.du_max;
+    case MPCEKF_LIM_V_MAX: return c.v_max;
+    case MPCEKF_LIM_PHISE_MIN: return c.phise_min;
+    case MPCEKF_LIM_Z_MAX: return c.z_max;
+    default: return c.z_tol;
+  }
+}
+
+// nfields / fields of mpcekf_set_limits and mpcekf_get_limits
+static int check_limit_fields(const char *who, int32_t nfields, const int32_t *fields) {
+  if (nfields < 1 || nfields > MPCEKF_NLIM)
+    return fail(MPCEKF_E_ARG, "%s: nfields = %d outside 1..%d", who, nfields, (int)MPCEKF_NLIM);
+  if (!fields) return fail(MPCEKF_E_ARG, "%s: null fields", who);
+  unsigned seen = 0;
+  for (int i = 0; i < nfields; ++i) {
+    if (fields[i] < 0 || fields[i] >= MPCEKF_NLIM)
+      return fail(MPCEKF_E_ARG, "%s: fields[%d] = %d is not a MPCEKF_LIM_* id (0..%d)", who, i, fields[i],
+                  (int)MPCEKF_NLIM - 1);
+    if (seen >> fields[i] & 1) return fail(MPCEKF_E_ARG, "%s: fields: id %d given twice", who, fields[i]);
+    seen |= 1u << fields[i];
+  }
+  return MPCEKF_OK;
+}
+
+int mpcekf_set_limits(mpcekf_ctx *X, int32_t nfields, const int32_t *fields, const double *values) {
+  if (!X) return fail(MPCEKF_E_ARG, "set_limits: null ctx");
+  int rc = check_limit_fields("set_limits", nfields, fields);
+  if (rc) return rc;
+  if (!values) return fail(MPCEKF_E_ARG, "set_limits: null values");
+  // check_cfg puts no condition on the scalar form of any of these fields, so none is put on
+  // an element either (a negative du_max is a legitimate configuration)
+  HIPCHK(hipSetDevice(X->device));
+  const size_t n = (size_t)X->n;
+  if (!X->d_lim && (rc = dalloc(&X->d_lim, std::max<size_t>(n, 1) * NLIMK))) return rc;
+  // the split route's hand-off k_cell<P_EKF | P_LIN> -> k_mpc_pc (a switched or wide context has it)
+  if (!X->d_lin && (rc = dalloc(&X->d_lin, std::max<size_t>(n, 1) * MPCEKF_LIN_SIZE))) return rc;
+  if (!X->d_zsoc && (rc = dalloc(&X->d_zsoc, std::max<size_t>(n, 1)))) return rc;
+  if (X->h_lim.empty()) {
+    X->h_lim.resize((size_t)MPCEKF_NLIM * n);
+    for (int f = 0; f < MPCEKF_NLIM; ++f) std::fill_n(X->h_lim.begin() + (size_t)f * n, n, cfg_limit(X->cfg, f));
+  }
+  for (int i = 0; i < nfields; ++i) std::copy_n(values + (size_t)i * n, n, X->h_lim.begin() + (size_t)fields[i] * n);
+  // the kernels' record by fill_kcfg's expressions: an array constant at the configuration's
+  // value gives the scalar's bits
+  std::vector<double> rec((size_t)NLIMK * n);
+  const double *h = X->h_lim.data();
+  const double Q = X->r.Q;
+  for (size_t c = 0; c < n; ++c) {
+    rec[LK_REF * n + c] = h[MPCEKF_LIM_TARGET_SOC * n + c];
+    rec[LK_U_MAX * n + c] = h[MPCEKF_LIM_U_MAX * n + c];
+    rec[LK_U_MIN * n + c] = -Q * h[MPCEKF_LIM_CRATE * n + c];  // initMPC.m:66-67
+    rec[LK_DU_MIN * n + c] = h[MPCEKF_LIM_DU_MIN * n + c];
+    rec[LK_DU_MAX * n + c] = h[MPCEKF_LIM_DU_MAX * n + c];
+    rec[LK_V_MAX * n + c] = h[MPCEKF_LIM_V_MAX * n + c];
+    rec[LK_PHISE_MIN * n + c] = h[MPCEKF_LIM_PHISE_MIN * n + c];
+    rec[LK_ZMAX * n + c] = h[MPCEKF_LIM_Z_MAX * n + c] + h[MPCEKF_LIM_Z_TOL * n + c];  // constraintsMPC.m:90-91
+  }
+  // on the context's stream, after every launch already queued; the wait makes rec's lifetime safe
+  if (n) HIPCHK(hipMemcpyAsync(X->d_lim, rec.data(), rec.size() * 8, hipMemcpyHostToDevice, X->stream));
+  HIPCHK(hipStreamSynchronize(X->stream));
+  X->percell = true;
+  return MPCEKF_OK;
+}
+
+int mpcekf_get_limits(mpcekf_ctx *X, int32_t nfields, const int32_t *fields, double *values) {
+  if (!X) return fail(MPCEKF_E_ARG, "get_limits: null ctx");
+  int rc = check_limit_fields("get_limits", nfields, fields);
+  if (rc) return rc;
+  if (!values) return fail(MPCEKF_E_ARG, "get_limits: null values");
+  const size_t n = (size_t)X->n;
+  for (int i = 0; i < nfields; ++i) {
+    if (X->percell) std::copy_n(X->h_lim.begin() + (size_t)fields[i] * n, n, values + (size_t)i * n);
+    else std::fill_n(values + (size_t)i * n, n, cfg_limit(X->cfg, fields[i]));
+  }
+  return MPCEKF_OK;
+}
+
+int mpcekf_clear_limits(mpcekf_ctx *X) {
+  if (!X) return fail(MPCEKF_E_ARG, "clear_limits: null ctx");
+  X->percell = false;  // the buffers stay: a graph captured per-cell names d_lim until the context goes
+  X->h_lim.clear();
   return MPCEKF_OK;
 }
 
@@ -1964,12 +2070,16 @@ static int mpc_step_ex_impl(mpcekf_ctx *X, const double *lin, const double *soc_
   io.jfin_out = J_fin ? djf : nullptr;
   io.normdu_out = norm_du ? dnd : nullptr;
   io.nviol_out = nviol ? dv : nullptr;
+  const double *lim = X->lim();
   if (X->wide) {
-    if ((rc = lerr(launch_mpc_wide(X->k, X->s, io, X->w, X->stream), "mpc_wide"))) return rc;
+    if ((rc = lerr(launch_mpc_wide(X->k, X->s, io, X->w, X->stream, lim), "mpc_wide"))) return rc;
     if ((rc = lerr(launch_hild_wide(X->k, X->s, io, X->w, X->stream), "hild_wide"))) return rc;
   } else if (X->sw != 7) {
-    if ((rc = lerr(launch_mpc_sw(X->sw, X->k, X->s, io, X->stream), "mpc_sw"))) return rc;
+    if ((rc = lerr(launch_mpc_sw(X->sw, X->k, X->s, io, X->stream, lim), "mpc_sw"))) return rc;
     if ((rc = lerr(launch_hild_sw(X->sw, X->k, X->s, io, X->stream), "hild_sw"))) return rc;
+  } else if (lim) {  // per-cell limits, every switch on: k_mpc_pc<7>, then k_cell's Hildreth pair
+    if ((rc = lerr(launch_mpc_sw(7, X->k, X->s, io, X->stream, lim), "mpc_sw"))) return rc;
+    if ((rc = lerr(launch_hild(X->k, X->s, io, X->stream), "hild"))) return rc;
   } else {
     if ((rc = lerr(launch_cell(X->r, X->k, X->s, io, X->stream), "cell"))) return rc;
     if ((rc = lerr(launch_hild(X->k, X->s, io, X->stream), "hild"))) return rc;
@@ -2008,8 +2118,8 @@ static int mpc_diag_impl(mpcekf_ctx *X, const double *lin, const double *uk_1, d
   else dl = X->d_slin;
   if (uk_1) HIPCHK(xf.in(du, uk_1, n * 8));
   else HIPCHK(hipMemcpyAsync(du, X->s.uk_1, n * 8, hipMemcpyDeviceToDevice, X->stream));
-  rc = X->wide ? launch_cl_diag_wide(X->k, X->n, dl, du, poles ? dp : nullptr, sv ? ds : nullptr, X->stream)
-               : launch_cl_diag(X->k, X->n, dl, du, poles ? dp : nullptr, sv ? ds : nullptr, X->stream);
+  rc = X->wide ? launch_cl_diag_wide(X->k, X->n, dl, du, poles ? dp : nullptr, sv ? ds : nullptr, X->stream, X->lim())
+               : launch_cl_diag(X->k, X->n, dl, du, poles ? dp : nullptr, sv ? ds : nullptr, X->stream, X->lim());
   if ((rc = lerr(rc, "cl_diag"))) return rc;
   if (poles) HIPCHK(xf.out(poles, dp, n * 2 * NA * 8));
   if (sv) HIPCHK(xf.out(sv, ds, n * NA * 8));

@@ -3867,8 +3867,11 @@ static int hild_lds_bytes(int block = 256) {  // 4 waves per 256-thread block; o
 size_t hildreth_any_scratch(int64_t n, int Nc, int ncon) { return (size_t)n * (size_t)(ncon * Nc + 2 * ncon); }
 
 int launch_cl_diag(const KCfg &c, int64_t n, const double *lin, const double *uk1, double *poles, double *sv,
-                   void *stream) {
+                   void *stream, const double *lim) {
   if (n == 0) return 0;
+  // per-cell limits: k_cl_diag_pc lives in mpcekf_switch.hip, so that this file's code object is
+  // the one a scalar context has always run
+  if (lim) return launch_cl_diag_pc(c, n, lin, uk1, poles, sv, stream, lim);
   hipLaunchKernelGGL((k_cl_diag<NP, NC>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, (hipStream_t)stream, c, n, lin,
                      uk1, poles, sv);
   return (int)hipGetLastError();

@@ -81,6 +81,10 @@ struct KCfg {
   int max_warn, max_hild, flags;
 };
 
+// mpcekf_set_limits: the per-cell MPC limits record, slot-major [NLIMK][n] (KCfg's eight
+// limit fields; mpcekf_mpc.hpp cfg_cell overlays them on a lane-local copy of the scalars)
+enum { LK_REF = 0, LK_U_MAX, LK_U_MIN, LK_DU_MIN, LK_DU_MAX, LK_V_MAX, LK_PHISE_MIN, LK_ZMAX, NLIMK };
+
 struct KState {
   int64_t n;
   double *bigx;   // [n][NM][6]
@@ -248,13 +252,20 @@ int wide_prob_doubles(int Np, int Nc);
 // GsocT*Gsoc + sigma_min cache for mpc_setup (rr = -Ts/(3600 Q), a = diag(A) of one model)
 int launch_wide_smin(const KWide &w, double rr, const double *a6, void *stream);
 // iterMPC setup from the linearisation records io.lin_in [n][35] and io.soc_k1_in [n]
-int launch_mpc_wide(const KCfg &c, const KState &s, const KIO &io, const KWide &w, void *stream);
+// lim (device [NLIMK][n], may be null): mpcekf_set_limits' record; non-null launches the
+// per-cell variant (k_mpc_wide_pc), null the kernel a scalar context has always launched
+int launch_mpc_wide(const KCfg &c, const KState &s, const KIO &io, const KWide &w, void *stream,
+                    const double *lim = nullptr);
 // iterMPC.m:53-60 poles / sv from this step's linearisation records and pre-step uk_1
 // (Np = 5 / Nc = 2 here, the wide horizons in mpcekf_wide.hip)
+// lim as launch_mpc_wide's (Ru reads du_max): non-null launches k_cl_diag_pc
 int launch_cl_diag(const KCfg &c, int64_t n, const double *lin, const double *uk1, double *poles, double *sv,
-                   void *stream);
+                   void *stream, const double *lim = nullptr);
 int launch_cl_diag_wide(const KCfg &c, int64_t n, const double *lin, const double *uk1, double *poles, double *sv,
-                        void *stream);
+                        void *stream, const double *lim = nullptr);
+// Np = 5 / Nc = 2 with per-cell limits (k_cl_diag_pc; mpcekf_switch.hip)
+int launch_cl_diag_pc(const KCfg &c, int64_t n, const double *lin, const double *uk1, double *poles, double *sv,
+                      void *stream, const double *lim);
 // hildreth.m (16-lane groups, exact lane-per-cell path for the rest) and iterMPC.m:75-95
 int launch_hild_wide(const KCfg &c, const KState &s, const KIO &io, const KWide &w, void *stream);
 // context-free predMat / constraintsMPC / hildreth at the wide horizons
@@ -267,7 +278,10 @@ int launch_constraints_wide(const KCfg &c, int Np, int Nc, int64_t n, const doub
 // on, is launch_cell / launch_hild / launch_constraints).
 // iterMPC.m:17-66 from the linearisation records io.lin_in [n][35] and io.soc_k1_in [n]:
 // the problem record and hflag, or the finished cell when no QP is needed
-int launch_mpc_sw(int sw, const KCfg &c, const KState &s, const KIO &io, void *stream);
+// lim (device [NLIMK][n], may be null): mpcekf_set_limits' record; non-null launches the
+// per-cell variant k_mpc_pc<sw>, which also takes sw = 7 (its problem record and hflag are
+// k_cell's, so launch_hild follows it there)
+int launch_mpc_sw(int sw, const KCfg &c, const KState &s, const KIO &io, void *stream, const double *lim = nullptr);
 // hildreth.m over the enabled rows (fast sweep + exact finisher) and iterMPC.m:68-95
 int launch_hild_sw(int sw, const KCfg &c, const KState &s, const KIO &io, void *stream);
 // compact M [n][nC][Nc], gamma [n][nC]

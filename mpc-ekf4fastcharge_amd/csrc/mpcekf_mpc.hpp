@@ -609,6 +609,26 @@ __host__ __device__ inline void closed_loop(const double a[6], const double Km[N
   CL[6 * NA + 6] = 1.0 - Km[6];
 }
 
+// ---------------------------------------------------------------------------
+// Per-cell limits (mpcekf_set_limits; runMPC.m:30-44 per cell)
+// ---------------------------------------------------------------------------
+// The cell's own KCfg: the context's scalars with the eight limit fields taken from the
+// record lim [NLIMK][n] -- slot-major, so each of the eight loads is coalesced over the wave
+// (64 B per cell in all).  The copy is lane-local; mpc_setup / constraints_s / mpc_core read
+// it where they read the kernel argument in a scalar context, their arithmetic untouched.
+__device__ __forceinline__ KCfg cfg_cell(const KCfg &cf, const double *lim, int64_t n, int64_t c) {
+  KCfg k = cf;
+  k.ref = lim[LK_REF * n + c];
+  k.u_max = lim[LK_U_MAX * n + c];
+  k.u_min = lim[LK_U_MIN * n + c];
+  k.du_min = lim[LK_DU_MIN * n + c];
+  k.du_max = lim[LK_DU_MAX * n + c];
+  k.v_max = lim[LK_V_MAX * n + c];
+  k.phise_min = lim[LK_PHISE_MIN * n + c];
+  k.zmax = lim[LK_ZMAX * n + c];
+  return k;
+}
+
 // per cell: lin [n][35] (this step's EKFmatsHandler record), uk1 [n] (uk_1 before the
 // step's iterMPC); poles [n][7][2] (re, im), sv [n][7] (either may be null)
 template <int NP, int NC>
@@ -616,24 +636,18 @@ __global__ void __launch_bounds__(64) k_cl_diag(const KCfg cf, int64_t n, const 
                                                 double *poles, double *sv) {
   const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= n) return;
-  Lin L;
-  lin_load(lin + c * 35, L);
-  double Km[NA], CL[NA * NA];
-  mpc_kmpc<NP, NC>(cf, L, uk1[c], Km);
-  closed_loop(L.a, Km, CL);
-  if (poles) {
-    double re[NA], im[NA];
-    eig::eigvals(NA, CL, re, im);
-    for (int i = 0; i < NA; ++i) {
-      poles[(c * NA + i) * 2] = re[i];
-      poles[(c * NA + i) * 2 + 1] = im[i];
-    }
-  }
-  if (sv) {
-    double s[NA];
-    eig::singvals(NA, CL, s);
-    for (int i = 0; i < NA; ++i) sv[c * NA + i] = s[i];
-  }
+#include "mpcekf_cl_diag.inc"
+}
+
+// k_cl_diag with the cell's own limits (Ru = ||F|| / (2 du_max sqrt(Nc)) - sigma_min, and F
+// through mpcData.ref), the same body
+template <int NP, int NC>
+__global__ void __launch_bounds__(64) k_cl_diag_pc(const KCfg cfs, int64_t n, const double *lin, const double *uk1,
+                                                   double *poles, double *sv, const double *lim) {
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= n) return;
+  const KCfg cf = cfg_cell(cfs, lim, n, c);
+#include "mpcekf_cl_diag.inc"
 }
 
 }  // namespace mk

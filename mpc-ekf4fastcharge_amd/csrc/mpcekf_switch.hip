@@ -8,6 +8,8 @@
 //                       problem record and hflag, or the finished cell when no QP is needed
 //   k_hild_sw<SW>       hildreth.m's fast rank-2 sweep over the enabled rows (hild_cell<SW>)
 //   k_hild_slow_sw<SW>  the exact-rule finisher of the lanes it flagged
+// A context with per-cell limits (mpcekf_set_limits) takes the same route under every mask, 7
+// included, with k_mpc_pc<SW> in k_mpc_sw's place: the same body on the cell's own limits.
 // SW is a template argument: a disabled row is absent from every unrolled row loop, so the
 // row number stays a constant of the loop (structural zeros, register-held constant rows,
 // the LDS prefetch ring) and no sum sees a term of a disabled block.  Arithmetic follows
@@ -32,62 +34,20 @@ __global__ void __launch_bounds__(256) k_mpc_sw(const KCfg cf, const KState s, c
   const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t n = s.n;
   if (c >= n) return;
-  const bool fused = io.mode & MODE_FUSED;
-  s.hflag[c] = 0;  // set again only if hildreth.m must run
-  if (s.status[c] & ST_ERROR) {  // the fused step's k_cell already wrote this cell's NaN outputs
-    if (!fused) {
-      const double NaN = __builtin_nan("");
-      if (io.uk_out) io.uk_out[c] = NaN;
-      if (io.nexec) io.nexec[c] = 0;
-      if (io.junc_out) io.junc_out[c] = NaN;
-      if (io.jfin_out) io.jfin_out[c] = NaN;
-      if (io.normdu_out) io.normdu_out[c] = NaN;
-      if (io.nviol_out) io.nviol_out[c] = 0;
-    }
-    return;
-  }
-  Lin L;
-  lin_load(io.lin_in + c * 35, L);
-  const double Zsoc = io.soc_k1_in[c];
-  double uk_1 = s.uk_1[c];
-  MpcOut o;
-  MpcSetup Pm;
-  const bool need = mpc_setup<NP, NC, SW>(cf, L, uk_1, Zsoc, Pm, o);
-  if (s.J_unc) s.J_unc[c] = o.J_unc;
-  if (io.junc_out) io.junc_out[c] = o.J_unc;
-  s.hflag[c] = need ? 1 : 0;
-  if (need) {  // hildreth.m runs in k_hild_sw; a disabled block's Hv / He / gamma fields are +0
-    double *pb = s.prob;
-#pragma unroll
-    for (int a = 0; a < NC; ++a) {
-      pb[(PB_F + a) * n + c] = Pm.F[a];
-#pragma unroll
-      for (int b = 0; b < NC; ++b) pb[(PB_E + a * NC + b) * n + c] = Pm.E[a][b];
-    }
-#pragma unroll
-    for (int i = 0; i < NP; ++i) {
-      pb[(PB_HV + i) * n + c] = Pm.Cn.Hv[i];
-      pb[(PB_HE + i) * n + c] = Pm.Cn.He[i];
-      pb[(PB_HS + i) * n + c] = Pm.Cn.Hs[i];
-      pb[(PB_ERR + i) * n + c] = Pm.e[i];
-    }
-#pragma unroll
-    for (int i = 0; i < NCON; ++i) pb[(PB_GAM + i) * n + c] = Pm.Cn.gam[i];
-    pb[PB_RU * n + c] = Pm.Ru;
-    pb[PB_UK1 * n + c] = uk_1;
-  } else {
-    o.nexec = 0;
-    mpc_finish<NP, NC, SW>(Pm.Cn, Pm.e, Pm.Ru, Pm.DU, uk_1, o);
-    s.uk_1[c] = uk_1;
-    if (s.J_fin) { s.J_fin[c] = o.J_fin; s.nviol[c] = o.nviol; }
-    cost_out(io, c, o.J_fin, o.nviol, norm_du<NC>(Pm.DU));
-    if (io.uk_out) io.uk_out[c] = o.uk;
-    if (io.nexec) io.nexec[c] = 0;
-    if (fused) {
-      s.uk[c] = o.uk;
-      if (io.u) io.u[c] = o.uk;
-    }
-  }
+#include "mpcekf_mpc_sw.inc"
+}
+
+// k_mpc_sw with the cell's own limits (mpcekf_set_limits): lim [NLIMK][n] overlaid on a
+// lane-local copy of the scalars (cfg_cell), the same body.  SW = 7 too: a per-cell context
+// with every switch on takes this split route, and its record / hflag are what k_cell hands
+// k_hild / k_hild_slow.
+template <int SW>
+__global__ void __launch_bounds__(256) k_mpc_pc(const KCfg cfs, const KState s, const KIO io, const double *lim) {
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t n = s.n;
+  if (c >= n) return;
+  const KCfg cf = cfg_cell(cfs, lim, n, c);
+#include "mpcekf_mpc_sw.inc"
 }
 
 template <int SW>
@@ -139,9 +99,16 @@ __global__ void __launch_bounds__(64) k_constraints_sw(const KCfg cf, int64_t n,
 // ---------------------------------------------------------------------------
 static int grid_for(int64_t n, int block) { return (int)((n + block - 1) / block); }
 
-// f(std::integral_constant<int, sw>) for sw = 0..6
-template <class F>
+// f(std::integral_constant<int, sw>) for sw = 0..6, and 7 where the caller has an all-on form
+// (ALL: the per-cell k_mpc_pc)
+template <bool ALL = false, class F>
 static int with_sw(int sw, F &&f) {
+  if constexpr (ALL) {
+    if (sw == 7) {
+      f(std::integral_constant<int, 7>{});
+      return 0;
+    }
+  }
   switch (sw) {
     case 0: f(std::integral_constant<int, 0>{}); return 0;
     case 1: f(std::integral_constant<int, 1>{}); return 0;
@@ -154,14 +121,30 @@ static int with_sw(int sw, F &&f) {
   }
 }
 
-int launch_mpc_sw(int sw, const KCfg &c, const KState &s, const KIO &io, void *stream) {
+int launch_mpc_sw(int sw, const KCfg &c, const KState &s, const KIO &io, void *stream, const double *lim) {
   if (s.n == 0) return 0;
   const int block = spread_block(s.n, 1, 256);
+  if (lim) {
+    if (with_sw<true>(sw, [&](auto m) {
+          hipLaunchKernelGGL(k_mpc_pc<decltype(m)::value>, dim3(grid_for(s.n, block)), dim3(block), 0,
+                             (hipStream_t)stream, c, s, io, lim);
+        }))
+      return -1;
+    return (int)hipGetLastError();
+  }
   if (with_sw(sw, [&](auto m) {
         hipLaunchKernelGGL(k_mpc_sw<decltype(m)::value>, dim3(grid_for(s.n, block)), dim3(block), 0,
                            (hipStream_t)stream, c, s, io);
       }))
     return -1;
+  return (int)hipGetLastError();
+}
+
+int launch_cl_diag_pc(const KCfg &c, int64_t n, const double *lin, const double *uk1, double *poles, double *sv,
+                      void *stream, const double *lim) {
+  if (n == 0) return 0;
+  hipLaunchKernelGGL((k_cl_diag_pc<NP, NC>), dim3(grid_for(n, 64)), dim3(64), 0, (hipStream_t)stream, c, n, lin, uk1,
+                     poles, sv, lim);
   return (int)hipGetLastError();
 }
 

@@ -360,6 +360,52 @@ class Context:
         """Replay repeated fused-call shapes from captured hipGraphs (mpcekf_set_graph)."""
         check(self.L.mpcekf_set_graph(self.h, int(bool(enable))))
 
+    # -- per-cell limits and targets (runMPC.m:30-44 per cell) ------------
+    LIMIT_FIELDS = _lib.LIMIT_FIELDS
+
+    @classmethod
+    def _limit_arrays(cls, n, fields):
+        """set_limits' keywords -> (int32 field ids, float64 [len, n] values); ValueError for
+        an unknown keyword, no keyword at all, or a value that is neither a scalar nor [n]."""
+        if not fields:
+            raise ValueError(f"set_limits: no field given (one of {cls.LIMIT_FIELDS})")
+        alias = {"targetSOC": "target_soc"}
+        ids, rows = [], []
+        for k, v in fields.items():
+            k = alias.get(k, k)
+            if k not in cls.LIMIT_FIELDS:
+                raise ValueError(f"set_limits: unknown field {k!r} (one of {cls.LIMIT_FIELDS})")
+            if cls.LIMIT_FIELDS.index(k) in ids:
+                raise ValueError(f"set_limits: field {k!r} given twice")
+            a = np.asarray(v, dtype=np.float64)
+            if a.ndim > 1 or (a.ndim == 1 and a.shape[0] != n):
+                raise ValueError(f"set_limits: {k} must be a scalar or a length-{n} array, got shape {a.shape}")
+            ids.append(cls.LIMIT_FIELDS.index(k))
+            rows.append(np.broadcast_to(a, (n,)))
+        return np.asarray(ids, dtype=np.int32), np.ascontiguousarray(np.stack(rows), dtype=np.float64)
+
+    def set_limits(self, **fields):
+        """mpcData.ref / mpcData.const of runMPC.m:30-44 per cell (mpcekf_set_limits): keywords
+        target_soc, Crate, u_max, du_min, du_max, v_max, phise_min, z_max, z_tol in make_config's
+        units, each a scalar (broadcast) or a length-ncells array.  A field not named keeps what
+        it had (the configuration's scalar, or an earlier set_limits).  Takes effect at the next
+        MPC stage, mid-charge included."""
+        ids, vals = self._limit_arrays(self.n, fields)   # ValueError before any library call
+        check(self.L.mpcekf_set_limits(self.h, int(ids.size), iptr(ids), dptr(vals)))
+
+    def get_limits(self):
+        """{field: [ncells]} of the limits in force (mpcekf_get_limits): what set_limits stored,
+        the configuration's scalar for a field never set."""
+        ids = np.arange(len(self.LIMIT_FIELDS), dtype=np.int32)
+        vals = np.empty((ids.size, self.n))
+        check(self.L.mpcekf_get_limits(self.h, int(ids.size), iptr(ids), dptr(vals)))
+        return {k: vals[i] for i, k in enumerate(self.LIMIT_FIELDS)}
+
+    def clear_limits(self):
+        """Back to the configuration's scalars and the launch sequence before the first
+        set_limits (mpcekf_clear_limits)."""
+        check(self.L.mpcekf_clear_limits(self.h))
+
     def set_timing(self, enable=True):
         """enable: True/1 = every step; N > 1 = sample every N-th step (less perturbation)."""
         check(self.L.mpcekf_set_timing(self.h, int(enable)))
@@ -692,14 +738,18 @@ def structured_M(Hv, He, Hs):
     return M
 
 
-def runMPC(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=None, obs=None):
+def runMPC(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=None, obs=None, limits=None):
     """runMPC.m:72-112 for a batch of cells; returns trajectories [nsteps, ncells].
     tc_traj [nsteps, ncells] (degC): a temperature profile (TC is the initial one).
-    obs: the plant's observables of every step as out["obs"] (Context.step's obs=)."""
+    obs: the plant's observables of every step as out["obs"] (Context.step's obs=).
+    limits: per-cell targets and limits, a dict of Context.set_limits' keywords (a protocol
+    sweep: runMPC.m:30-44 per cell), set after init_cells and before the first step."""
     SOC0 = np.atleast_1d(np.asarray(SOC0, dtype=np.float64))
     n = ncells or SOC0.shape[0]
     with Context(rom, n, cfg, device) as ctx:
         ctx.init_cells(SOC0, TC)
+        if limits:
+            ctx.set_limits(**limits)
         out = ctx.step(nsteps, tc=tc_traj, obs=obs)
         out["status"] = ctx.get_state()["status"]
         return out
