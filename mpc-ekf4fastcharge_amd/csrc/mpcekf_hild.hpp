@@ -24,18 +24,6 @@ constexpr int NCON = 4 * NC + 3 * NP;  // constraint rows (constraintsMPC.m)
 #ifndef MPCEKF_HILD_PF
 #define MPCEKF_HILD_PF 3
 #endif
-#ifndef MPCEKF_HILD_REGROWS  // k_hild: the constant rows' X / H_ii slots in registers
-#define MPCEKF_HILD_REGROWS 1
-#endif
-// k_hild finishes its slow lanes itself (no k_hild_slow launch).  Off: the exact-rule
-// path's registers moved the fast sweep's allocation (AGPRs 34 -> 242) and k_hild took
-// 89.5 instead of ~75 us, more than the ~5 us a k_hild_slow launch costs (r04g A/B)
-#ifndef MPCEKF_HILD_INLINE_SLOW
-#define MPCEKF_HILD_INLINE_SLOW 0
-#endif
-#ifndef MPCEKF_HILD_NEXTV  // k_hild: the next sweep's v accumulated in the row loop
-#define MPCEKF_HILD_NEXTV 1
-#endif
 
 using Cons = ConsT<NP, NC>;
 using MpcSetup = MpcSetupT<NP, NC>;
@@ -190,7 +178,7 @@ __device__ __forceinline__ void hild_unstage(const double2 *hl, XS &Xs) {
 // lane's LDS slots once per solve), so a sweep reads LDS for the 15 Toeplitz rows only.
 // At 4 waves per CU in the maxIter window the two ds_read_b128 per row were as long as
 // the row's dependent chain.
-constexpr int HILD_REG_ROWS = MPCEKF_HILD_REGROWS ? 4 * NC : 0;
+constexpr int HILD_REG_ROWS = 4 * NC;
 __device__ __forceinline__ double2 hx_r(const double2 *hl, const double2 xr3[3], int i) {
   if (i < HILD_REG_ROWS) {
     const double2 x = xr3[hslot(i)];
@@ -228,7 +216,7 @@ __device__ __forceinline__ void hild_v(const double2 *hl, const double2 xr3[3], 
 // (v0, v1): this sweep's start v in, the next sweep's out.  The next sweep's v is summed
 // row by row from lambda_i's final value of this sweep (row i is the last to change it),
 // the same fmas on the same operands in the same order as hild_v after the sweep, with the
-// X(:,i) the row already read (MPCEKF_HILD_NEXTV; 0: hild_v at every sweep start).
+// X(:,i) the row already read.
 // With a block switched off the loop runs over the compact stack ci = 0 .. nC - 1 (the
 // prefetch ring turns on ci); i = row_full(ci) is still a constant of the unrolled loop.
 template <int SW = SW_ALL>
@@ -238,7 +226,6 @@ __device__ __forceinline__ void sweep_fast(const Cons &Cn, const double2 *hl, co
   ConsM Mf{Cn};
   constexpr int NCS = NCON_SW<SW>;
   asm volatile("" ::: "memory");  // reload the LDS slots each sweep (no hoisting)
-  if (!MPCEKF_HILD_NEXTV) hild_v<SW>(hl, xr3, L, v0, v1);
   double u0 = 0.0, u1 = 0.0;
   asm volatile("" ::: "memory");
   // row i's slots are read MPCEKF_HILD_PF rows ahead: ds_read latency (~76 cycles idle,
@@ -273,16 +260,12 @@ __device__ __forceinline__ void sweep_fast(const Cons &Cn, const double2 *hl, co
     L[i] = nl;
     v0 = __builtin_fma(-xc.x, m, v0);   // fma(x, d, v) with d = -m: the same value
     v1 = __builtin_fma(-xc.y, m, v1);
-    if (MPCEKF_HILD_NEXTV) {
-      u0 = __builtin_fma(xc.x, nl, u0);
-      u1 = __builtin_fma(xc.y, nl, u1);
-    }
+    u0 = __builtin_fma(xc.x, nl, u0);
+    u1 = __builtin_fma(xc.y, nl, u1);
   }
   vfin = isfinite(v0) && isfinite(v1);
-  if (MPCEKF_HILD_NEXTV) {
-    v0 = u0;
-    v1 = u1;
-  }
+  v0 = u0;
+  v1 = u1;
 }
 
 // The exact form for lanes the fast form flagged: plain division, v recomputed from
@@ -577,16 +560,10 @@ __device__ __forceinline__ void hild_finish(const KState &s, const KIO &io, int6
   }
 }
 
-template <int SW = SW_ALL>
-__device__ __forceinline__ void hild_slow_cell(const KCfg &cf, const KState &s, const KIO &io, int64_t c);
-// out of line: the exact-rule path keeps its registers out of the fast sweep's allocation
-template <int SW = SW_ALL>
-__device__ __noinline__ void hild_slow_wave(const KCfg &cf, const KState &s, const KIO &io, int64_t c) {
-  hild_slow_cell<SW>(cf, s, io, c);
-}
-
 // hildreth.m + iterMPC.m:68-95, lane per cell: the fast solve (hild_fast).  Blocks of 256
-// lanes (hild_lane_lds); k_hild, or the end of k_cell in the fused step.  lambda keeps the
+// lanes (hild_lane_lds); k_hild.  A lane outside the fast form's domain is left to
+// k_hild_slow (hild_slow_cell), whose exact-rule path keeps its registers out of the fast
+// sweep's allocation (profiles/r04h_ab_inline_slow.txt).  lambda keeps the
 // all-on slots in s.lam; a disabled row's slot is neither read nor written (it stays 0).
 template <int SW = SW_ALL>
 __device__ __forceinline__ void hild_cell(const KCfg &cf, const KState &s, const KIO &io, int64_t c) {
@@ -608,21 +585,12 @@ __device__ __forceinline__ void hild_cell(const KCfg &cf, const KState &s, const
   extern __shared__ double2 hlds[];
   int nexec;
   const bool slow = hild_fast<SW>(Cn, E, lam, cf.max_hild, cf.hild_tol, K, !qp, hild_lane_lds(hlds), s.lam + c, n, nexec);
-  if (MPCEKF_HILD_INLINE_SLOW) {
-    // the rare wave with a lane outside the fast form's domain redoes that lane with the
-    // exact rules here (warm start still in s.lam), the wave's other lanes riding along on
-    // the dummy problem: no second kernel, whose launch cost ~4 us a step even when empty
-    if (qp && slow) s.hflag[c] = 2;
-    if (__any(slow)) hild_slow_wave<SW>(cf, s, io, c);
-    if (!qp || slow) return;
-  } else {
-    if (__any(slow) && (threadIdx.x & 63) == __builtin_amdgcn_readfirstlane(threadIdx.x & 63))
-      atomicAdd(s.hslow, 1);  // one add per wave: k_hild_slow has work
-    if (!qp) return;
-    if (slow) {  // k_hild_slow finishes it (warm start still in s.lam)
-      s.hflag[c] = 2;
-      return;
-    }
+  if (__any(slow) && (threadIdx.x & 63) == __builtin_amdgcn_readfirstlane(threadIdx.x & 63))
+    atomicAdd(s.hslow, 1);  // one add per wave: k_hild_slow has work
+  if (!qp) return;
+  if (slow) {  // k_hild_slow finishes it (warm start still in s.lam)
+    s.hflag[c] = 2;
+    return;
   }
   double Mtl[NC];
   hild_mtl<SW>(Cn, lam, Mtl);
@@ -631,7 +599,7 @@ __device__ __forceinline__ void hild_cell(const KCfg &cf, const KState &s, const
     if (ron<SW>(i)) s.lam[(size_t)i * n + c] = lam[i];  // iterMPC.m:68
   hild_finish<SW>(s, io, c, Cn, Mtl, nexec);
 }
-template <int SW>
+template <int SW = SW_ALL>
 __device__ __forceinline__ void hild_slow_cell(const KCfg &cf, const KState &s, const KIO &io, int64_t c) {
   if (c >= s.n) return;
   const bool slow = s.hflag[c] == 2;

@@ -1217,18 +1217,16 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
   if (!tr) tr = &none;
   const bool bounds = X->cfg.flags & MPCEKF_CF_BOUNDS;
   if (tr->zbk && !bounds) return fail(MPCEKF_E_ARG, "step_ex: a boundzk trajectory needs MPCEKF_CF_BOUNDS");
-  // boundzk in k_cell itself, or from its hand-off record in k_bounds (the lane-quad
-  // k_ekf4 path writes only the record; MB writes boundzk in k_cell)
+  // boundzk from k_cell's / k_ekf4's hand-off record in k_bounds (MB writes boundzk in
+  // k_cell, from its one 6x6 covariance)
   // per-cell limits (mpcekf_set_limits): the split route at every batch size, no k_ekf4 mapping
   const double *lim = X->lim();
   const bool quad = X->quad && !lim, split_cell = X->split_cell && !lim;
-  const bool bnd_kernel = bounds && !X->mb && (!cell_computes_bounds() || quad);
+  const bool bnd_kernel = bounds && !X->mb;
   // OB_step's simStep inside k_cell (KRom::cell_plant): no k_plant launch
   const bool plant_in_cell = X->r.cell_plant && !X->mb;  // k_cell, or k_ekf4's lane quad (quad_plant)
-  // hildreth.m at the end of k_cell (Np = 5, one k_cell per step): no k_hild launch
   // a constraint block off, or per-cell limits at Np = 5: the split route of mpcekf_switch.hip
   const bool switched = X->sw != 7 || (lim && !X->wide);
-  const bool hild_in_cell = cell_runs_hild() && !X->wide && !split_cell && !quad && !switched;
   const size_t n = (size_t)X->n, per = n * (size_t)nsteps, nzz = (size_t)X->nz + 2;
   // the output fields, their element size and elements per cell-step
   struct F {
@@ -1344,7 +1342,6 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
       io.lazy_t = t;
       io.plant = plant_in_cell;
       io.tc_in = plant_in_cell && dtc ? dtc + (size_t)k * n : nullptr;
-      io.hild = hild_in_cell;
       io.stamps = X->d_stamps;
       io.u = (double *)row(0, k);
       io.v = (double *)row(1, k);
@@ -1441,7 +1438,7 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
         if ((rc = lerr(launch_hild(X->k, X->s, iow, X->stream), "hild"))) return rc;
       } else if (switched) {
         if ((rc = lerr(launch_hild_sw(X->sw, X->k, X->s, iow, X->stream), "hild_sw"))) return rc;
-      } else if (!hild_in_cell && (rc = lerr(launch_hild(X->k, X->s, io, X->stream), "hild"))) {
+      } else if ((rc = lerr(launch_hild(X->k, X->s, io, X->stream), "hild"))) {
         return rc;
       }
       if (diag) {
@@ -1495,9 +1492,7 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
     for (int k = 0; k < nsteps; ++k)
       for (int j = 0; j < 5; ++j) {
         if ((k + 1) % X->timing_every != 0 && k != nsteps - 1) continue;
-        if ((j == 4 && !flushed[k]) || (j == 2 && !bnd_kernel) || (j == 0 && plant_in_cell && !nslots) ||
-            (j == 3 && hild_in_cell && !diag))
-          continue;
+        if ((j == 4 && !flushed[k]) || (j == 2 && !bnd_kernel) || (j == 0 && plant_in_cell && !nslots)) continue;
         float ms = 0;
         const int a = j == 3 ? hstart : e0[j], b = j == 3 ? 4 : e0[j] + 1;
         HIPCHK(hipEventElapsedTime(&ms, X->ev[(size_t)k * NEV + a], X->ev[(size_t)k * NEV + b]));
@@ -1923,7 +1918,7 @@ static int ekf_step_impl(mpcekf_ctx *X, const double *vk, const double *ik, cons
   io.ik_in = dik;
   io.zk = dzk;
   io.zbk = boundzk ? dzb : nullptr;
-  const bool bnd_kernel = boundzk && !X->mb && !cell_computes_bounds();
+  const bool bnd_kernel = boundzk && !X->mb;  // k_bounds from k_cell's record (MB: k_cell itself)
   io.bnd = bnd_kernel ? X->d_bnd : nullptr;
   io.xm_out = dxm;
   io.xg_out = dxg;

@@ -28,41 +28,6 @@
 namespace mk {
 
 
-// k_cell build options (A/B knobs; the defaults are the measured best):
-// MPCEKF_REC_ONCE: corners whose whole record (xhat and Sigma) is read with the first
-// read; the others read Sigma at their update.  1: corner 0's Sigma is what the gains
-// use first; 2..4 hold more Sigma in registers and spill (measured no faster).
-// MPCEKF_CELL_OUTLINE: the Jacobi symmetrisation as a call instead of inline.
-#ifndef MPCEKF_S_AHEAD  // k_cell: corner j+1's Sigma loaded before corner j's record store (§4.2)
-#define MPCEKF_S_AHEAD 1
-#endif
-#ifndef MPCEKF_RING_LATE  // k_cell: the plant's ring stores after the cell's last load (§4.2)
-#define MPCEKF_RING_LATE 1
-#endif
-#ifndef MPCEKF_PLANT_STORE_LATE  // k_cell: the plant's state stores after the cell's last load
-#define MPCEKF_PLANT_STORE_LATE 0
-#endif
-#ifndef MPCEKF_REC_ONCE
-#define MPCEKF_REC_ONCE 1
-#endif
-#ifndef MPCEKF_CELL_OUTLINE
-#define MPCEKF_CELL_OUTLINE false
-#endif
-// k_flush: the next cell's loads issued before this cell's replay
-#ifndef MPCEKF_FLUSH_PF
-#define MPCEKF_FLUSH_PF 1
-#endif
-#ifndef MPCEKF_FLUSH_COAL  // k_flush_coal (coalesced chunks, NM <= 64): measured slower, off
-#define MPCEKF_FLUSH_COAL 0
-#endif
-// v3 lookups without branches (NaN theta, Ea = 0 and dexp's special cases by selects): one
-// basic block per lookup, so neighbouring lookups' L2 loads can overlap; quintic k_cell 45.3k
-// -> 43.6k instructions, 1,084 -> 837 branches, same-box 155.3 / 148.0 -> 151.9 / 147.7 us
-// (profiles/r05h_ab_branchfree.txt)
-#ifndef MPCEKF_PL_BRANCHFREE
-#define MPCEKF_PL_BRANCHFREE 1
-#endif
-
 // Section timestamps of k_cell for profiling builds (-DMPCEKF_STAMPS); compiled out otherwise.
 #ifdef MPCEKF_STAMPS
 #define STAMP(i)                                                                          \
@@ -187,24 +152,15 @@ __device__ __forceinline__ int tab_interval(int n, double x, double &s) {
 }
 // one row: interval i's coefficients at c + i * istride
 __device__ __forceinline__ double tabp(const double *c, int n, double x, int istride) {
-#if !MPCEKF_PL_BRANCHFREE
-  if (x != x) return __builtin_nan("");
-#endif
   double s;
   const int i = tab_interval(n, x, s);  // a NaN x: interval 0 (fmax), the NaN selected below
   const double2 *p = reinterpret_cast<const double2 *>(c + (size_t)i * istride);
   const double v = horner6(p[0], p[1], p[2], s);
-  return (MPCEKF_PL_BRANCHFREE && x != x) ? __builtin_nan("") : v;
+  return x != x ? __builtin_nan("") : v;
 }
 // two adjacent rows of interval i (the T bracket): a from c + i * istride, b KPOLY after
 __device__ __forceinline__ void tabp2(const double *c, int n, double x, int istride, double &a, double &b,
                                       int ro = KPOLY) {
-#if !MPCEKF_PL_BRANCHFREE
-  if (x != x) {
-    a = b = __builtin_nan("");
-    return;
-  }
-#endif
   double s;
   const int i = tab_interval(n, x, s);
   const double2 *p = reinterpret_cast<const double2 *>(c + (size_t)i * istride);
@@ -212,7 +168,7 @@ __device__ __forceinline__ void tabp2(const double *c, int n, double x, int istr
   const double2 a01 = p[0], a23 = p[1], a45 = p[2], b01 = q[0], b23 = q[1], b45 = q[2];
   a = horner6(a01, a23, a45, s);
   b = horner6(b01, b23, b45, s);
-  if (MPCEKF_PL_BRANCHFREE && x != x) a = b = __builtin_nan("");
+  if (x != x) a = b = __builtin_nan("");
 }
 // ABI v4 rows on a function's own theta nodes (include/mpcekf.h node / node_p): the segment
 // k = #{j in 1..m-2 : x_j <= theta} (oracle node_poly) from the function's uniform bucket map
@@ -240,18 +196,11 @@ __device__ __forceinline__ void tabn2(const double *c, const double *map, int nu
 // Defined exp of the v3 Arrhenius factor (oracle/mpcekf_oracle.c orc_exp, rom.py dexp):
 // x = k ln2 + r, k = floor(x / ln2 + 1/2), fdlibm's rational form for exp(r); only
 // +, -, *, /, floor and ldexp, exact or correctly rounded on both sides.
-// MPCEKF_PL_BRANCHFREE: the special cases by selects (the in-range arithmetic unchanged), so
-// that a lookup is one basic block
+// The special cases by selects (the in-range arithmetic unchanged), so that a lookup is one
+// basic block and neighbouring lookups' L2 loads can overlap (profiles/r05h_ab_branchfree.txt)
 __device__ __forceinline__ double dexp(double x0) {
-#if MPCEKF_PL_BRANCHFREE
   const bool nan = x0 != x0, big = x0 > 709.782712893384, small = x0 < -745.1332191019412;
   const double x = (nan || big || small) ? 0.0 : x0;
-#else
-  const double x = x0;
-  if (x != x) return x;
-  if (x > 709.782712893384) return __builtin_inf();
-  if (x < -745.1332191019412) return 0.0;
-#endif
   const double k = floor(x * 1.44269504088896338700e+00 + 0.5);
   const double hi = x - k * dm::LN2_HI;
   const double lo = k * dm::LN2_LO;
@@ -262,12 +211,8 @@ __device__ __forceinline__ double dexp(double x0) {
                                  t * (6.61375632143793436117e-05 +
                                       t * (-1.65339022054652515390e-06 + t * 4.13813679705723846039e-08))));
   const double y = 1.0 - ((lo - (r * c) / (2.0 - c)) - hi);
-#if MPCEKF_PL_BRANCHFREE
   const double v = ldexp(y, (int)k);
   return nan ? x0 : big ? __builtin_inf() : small ? 0.0 : v;
-#else
-  return ldexp(y, (int)k);
-#endif
 }
 
 // Electrode tables (include/mpcekf.h mpcekf_electrode; host: build_rom).  In LDS: a
@@ -328,13 +273,9 @@ struct ETab {
       else
         tabn2(r->poly + off + j * jstr, r->poly + moff, nu, th, istr, a, c, ro);
       a = a + g * (c - a);
-#if MPCEKF_PL_BRANCHFREE
       // every function multiplied by its factor, dexp(+-0) = 1 exactly when Ea = 0 (a * 1 = a:
       // the oracle's unmultiplied value): no branch between neighbouring lookups' loads
       a = a * dexp(ear != 0.0 ? ear * xa : 0.0);
-#else
-      if (ear != 0.0) a = a * dexp(ear * xa);
-#endif
       return a;
     }
     const double *t = b + etab_header(nth) + ((fn * 2 + side) * nte + j) * nth;
@@ -1665,7 +1606,7 @@ __global__ void __launch_bounds__(256) k_flush(const KRom r, const KCfg cf, cons
     for (int e = 0; e < 6; ++e) cp[e] = cP[(size_t)mm * 6 + e];
     // software pipelined over the wave's cells: the next cell's rings, timestamps and
     // records are loaded while this cell replays, so every wave keeps a cell's 13.6 KB
-    // in flight (MPCEKF_FLUSH_PF = 0: load, replay, store in turn)
+    // in flight
     struct FCell {
       double hpl, hul, xe[REC], xp[6];
       int tse, tsp;
@@ -1692,14 +1633,10 @@ __global__ void __launch_bounds__(256) k_flush(const KRom r, const KCfg cf, cons
       }
     };
     FCell cur;
-    if (MPCEKF_FLUSH_PF && c_lo + w0 < c_hi) fload(c_lo + w0, cur);
+    if (c_lo + w0 < c_hi) fload(c_lo + w0, cur);
     for (int64_t c = c_lo + w0; c < c_hi; c += nw) {
       FCell nx;
-      if (MPCEKF_FLUSH_PF) {
-        if (c + nw < c_hi) fload(c + nw, nx);
-      } else {
-        fload(c, cur);
-      }
+      if (c + nw < c_hi) fload(c + nw, nx);
       const double hpl = cur.hpl, hul = cur.hul;
       const int tse = cur.tse, tsp = cur.tsp;
       double2 *re = reinterpret_cast<double2 *>(s.ekf + ((size_t)c * NM + mm) * REC);
@@ -1734,114 +1671,8 @@ __global__ void __launch_bounds__(256) k_flush(const KRom r, const KCfg cf, cons
         s.ts_ekf[c * NM + m] = new_ts;
         s.ts_plant[c * NM + m] = new_ts;
       }
-      if (MPCEKF_FLUSH_PF) cur = nx;
+      cur = nx;
     }
-  }
-}
-
-// k_flush_coal: k_flush with coalesced record traffic (NM <= 64).  A cell's EKF records
-// ([NM][20] doubles) and plant states ([NM][6]) are contiguous, and every element's update
-// is its own recurrence x <- fma(coef, x, input) over the steps its model skipped, so a wave
-// takes the cell's regions as consecutive 16-byte chunks, lane l chunk l + 64 q: each load
-// and store instruction moves one contiguous KB instead of 16 B at a 160-B stride per lane.
-// A chunk is two elements of one model (REC and 6 are even); its coefficients are at the
-// same offset of bulk_tab, its timestamp is the model's.  Same fmas, same order per element.
-// Bitwise-green but slower (645 vs 455 us per flush at configs[2], profiles/r03n_ab_flush_coal.txt):
-// 13 per-chunk timestamp gathers and a compare per chunk and step replace k_flush's two per
-// lane, and the per-lane 16-B stride was not what held k_flush back.  Off by default.
-constexpr int FC_QE = 10, FC_QP = 3;  // chunks per lane: 64 * 10 >= 64 * 20 / 2, 64 * 3 >= 64 * 6 / 2
-__global__ void __launch_bounds__(256) k_flush_coal(const KRom r, const KCfg cf, const KState s, const int t,
-                                                    const int new_ts, const int64_t c_lo, const int64_t c_hi) {
-  const int NM = r.NM;
-  const int lane = threadIdx.x & 63;
-  const int64_t nw = (int64_t)gridDim.x * (blockDim.x >> 6);
-  const int64_t w0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const double W = cf.SigmaW;
-  const bool mb = cf.flags & KF_MB;  // MB never time-updates the per-model EKF records
-  const int ne2 = NM * REC / 2, np2 = NM * 3;
-  const double *cC = r.bulk_tab, *cP = r.bulk_tab + (size_t)NM * REC;
-  // per-lane constants: the chunks' coefficients, models and element kinds
-  double2 ke[FC_QE], kp[FC_QP];
-  int me[FC_QE], mp[FC_QP];
-  bool xe0[FC_QE], xe1[FC_QE];  // element is an xhat entry (input priorI) or Sigma (input SigmaW)
-#pragma unroll
-  for (int q = 0; q < FC_QE; ++q) {
-    const int j = lane + 64 * q, jj = j < ne2 ? j : ne2 - 1;
-    ke[q] = reinterpret_cast<const double2 *>(cC)[jj];
-    me[q] = j < ne2 ? (2 * j) / REC : -1;
-    xe0[q] = (2 * jj) % REC < NX;
-    xe1[q] = (2 * jj + 1) % REC < NX;
-  }
-#pragma unroll
-  for (int q = 0; q < FC_QP; ++q) {
-    const int j = lane + 64 * q, jj = j < np2 ? j : np2 - 1;
-    kp[q] = reinterpret_cast<const double2 *>(cP)[jj];
-    mp[q] = j < np2 ? (2 * j) / 6 : -1;
-  }
-  struct FCell {
-    double hpl, hul;
-    double2 xe[FC_QE], xp[FC_QP];
-    int tse[FC_QE], tsp[FC_QP];
-  };
-  auto fload = [&](int64_t c, FCell &F) {
-    F.hpl = s.hist_p[(size_t)(lane & (LAZY_H - 1)) * s.n + c];
-    F.hul = s.hist_u[(size_t)(lane & (LAZY_H - 1)) * s.n + c];
-    const double2 *re = reinterpret_cast<const double2 *>(s.ekf + (size_t)c * NM * REC);
-    const double2 *rp = reinterpret_cast<const double2 *>(s.bigx + (size_t)c * NM * 6);
-#pragma unroll
-    for (int q = 0; q < FC_QE; ++q) {
-      const bool a = me[q] >= 0;
-      F.xe[q] = re[a ? lane + 64 * q : 0];
-      F.tse[q] = (a && !mb) ? s.ts_ekf[c * NM + me[q]] : t;
-    }
-#pragma unroll
-    for (int q = 0; q < FC_QP; ++q) {
-      const bool a = mp[q] >= 0;
-      F.xp[q] = rp[a ? lane + 64 * q : 0];
-      F.tsp[q] = a ? s.ts_plant[c * NM + mp[q]] : t;
-    }
-  };
-  FCell cur;
-  if (c_lo + w0 < c_hi) fload(c_lo + w0, cur);
-  for (int64_t c = c_lo + w0; c < c_hi; c += nw) {
-    FCell nx;
-    if (c + nw < c_hi) fload(c + nw, nx);
-    int kmin = t;
-#pragma unroll
-    for (int q = 0; q < FC_QE; ++q) kmin = min(kmin, cur.tse[q]);
-#pragma unroll
-    for (int q = 0; q < FC_QP; ++q) kmin = min(kmin, cur.tsp[q]);
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) kmin = min(kmin, __shfl_xor(kmin, o));
-    for (int k = kmin + 1; k <= t; ++k) {  // k is wave-uniform
-      const int sl = k & (LAZY_H - 1);
-      const double p = rl64(cur.hpl, sl), u = rl64(cur.hul, sl);
-#pragma unroll
-      for (int q = 0; q < FC_QE; ++q)
-        if (k > cur.tse[q]) {
-          cur.xe[q].x = __builtin_fma(ke[q].x, cur.xe[q].x, xe0[q] ? p : W);
-          cur.xe[q].y = __builtin_fma(ke[q].y, cur.xe[q].y, xe1[q] ? p : W);
-        }
-#pragma unroll
-      for (int q = 0; q < FC_QP; ++q)
-        if (k > cur.tsp[q]) {
-          cur.xp[q].x = __builtin_fma(kp[q].x, cur.xp[q].x, u);
-          cur.xp[q].y = __builtin_fma(kp[q].y, cur.xp[q].y, u);
-        }
-    }
-    double2 *re = reinterpret_cast<double2 *>(s.ekf + (size_t)c * NM * REC);
-    double2 *rp = reinterpret_cast<double2 *>(s.bigx + (size_t)c * NM * 6);
-#pragma unroll
-    for (int q = 0; q < FC_QE; ++q)
-      if (me[q] >= 0 && cur.tse[q] < t) re[lane + 64 * q] = cur.xe[q];
-#pragma unroll
-    for (int q = 0; q < FC_QP; ++q)
-      if (mp[q] >= 0 && cur.tsp[q] < t) rp[lane + 64 * q] = cur.xp[q];
-    if (lane < NM) {
-      s.ts_ekf[c * NM + lane] = new_ts;
-      s.ts_plant[c * NM + lane] = new_ts;
-    }
-    cur = nx;
   }
 }
 
@@ -1894,7 +1725,7 @@ __device__ __forceinline__ void ekf_catch_up4(const KState &s, const CellCtx &cc
     for (int i = 0; i < j; ++i) need[j] = need[j] && m[i] != m[j];
   }
   if (!(need[0] || need[1] || need[2] || need[3])) return;
-  // pt: step t's input (the ring's slot t, which k_cell may not have stored yet: MPCEKF_RING_LATE)
+  // pt: step t's input (the ring's slot t, which k_cell stores only after its last load)
   double x[4][NX], S[4][NPK];
 #pragma unroll
   for (int j = 0; j < 4; ++j)
@@ -2111,47 +1942,19 @@ __device__ __forceinline__ double qform(const double T[NPK], const double rw[NX]
   return q;
 }
 
-// The plant's per-cell stores, held for the caller to issue after its last load
-// (MPCEKF_PLANT_STORE_LATE): SOCn / SOCp and the advanced corner states.
-struct PlantOut {
-  double socn, socp;
-  double x[4][6];
-  int mm[4];
-  bool adv[4], on;
-};
-__device__ __forceinline__ void plant_store(const KRom &r, const KState &s, int64_t c, int lazy_t, const PlantOut &o) {
-  s.SOCn[c] = o.socn;
-  s.SOCp[c] = o.socp;
-  double *bx = s.bigx + (size_t)c * r.NM * 6;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    if (!o.adv[j]) continue;
-    store_corner(bx + (size_t)o.mm[j] * 6, o.x[j]);
-    s.ts_plant[c * r.NM + o.mm[j]] = lazy_t;
-  }
-}
 // OB_step's simStep (OB_step.m:188-357) for one cell at the start of k_cell's fused step:
 // the shared plant helpers, read from the cell blob (the plant's 9 role rows are the blob's
 // first C rows, D at nzp*5, diag(A) after them -- the integrator's a = 1 exactly, checked
 // by build_rom -- and the res0 column after the Sigma coefficients).  Returns Vcell; the
-// plant state, averages, ring inputs and timestamps are stored as k_plant4 stores them.
-// (ring_p / po: the ring input and the state stores handed back for the caller to issue
-// after its last load, MPCEKF_RING_LATE / MPCEKF_PLANT_STORE_LATE.)
+// plant state, averages and timestamps are stored as k_plant4 stores them; the ring inputs
+// of this step (Iapp and ring_p) are left for the caller to store after its last load.
 template <int NZ, bool PL>
 __device__ __forceinline__ double cell_plant(const KRom &r, const KState &s, const double *L, const double *tb,
                                              const double *Tp, const double *Zp, int64_t c, int lazy_t, double Iapp,
-                                             double tcs, int st, double *ring_p = nullptr, PlantOut *po = nullptr) {
+                                             double tcs, int st, double &ring_p) {
   constexpr int OA = NZ * NX + NZ, OR0 = NZ * NX + NZ + NX + NPK, OD = NZ * NX;
   const int stride = r.cell_stride;
-  if (lazy_t) {  // this step's inputs, for the deferred updates of every model
-    if (ring_p) {  // stored by the caller after its last load (MPCEKF_RING_LATE)
-      *ring_p = s.priorI[c];
-    } else {
-      const size_t slot = (size_t)(lazy_t % LAZY_H) * s.n + c;
-      s.hist_u[slot] = Iapp;
-      s.hist_p[slot] = s.priorI[c];
-    }
-  }
+  if (lazy_t) ring_p = s.priorI[c];  // this step's input, for the deferred updates of every model
   if (st & ST_ERROR) return __builtin_nan("");
   const double T = tcs + 273.15;  // OB_step.m:75
   const ETab et = etab<PL>(r, tb + r.cell_tab, T);
@@ -2194,18 +1997,6 @@ __device__ __forceinline__ double cell_plant(const KRom &r, const KState &s, con
 #pragma unroll
   for (int q = 0; q < NPLANT; ++q) yk[q] = blend4(y[0][q], y[1][q], y[2][q], y[3][q], aZ, aT);
   const double V = plant_vcell(r, et, yk, T, Iapp, negSOC, posSOC, SOC0n, SOC0p);
-  if (po) {  // the caller stores them after its last load
-    po->on = true;
-    po->socn = SOCnAvg;
-    po->socp = SOCpAvg;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      po->mm[j] = mm[j];
-      po->adv[j] = lazy_t && tsj[j] < lazy_t;
-      plant_advance<false>(L + mm[j] * stride + OA, xs[j], Iapp, po->x[j]);
-    }
-    return V;
-  }
   s.SOCn[c] = SOCnAvg;
   s.SOCp[c] = SOCpAvg;
   if (lazy_t) {  // advance the corners through step t in place
@@ -2221,88 +2012,6 @@ __device__ __forceinline__ double cell_plant(const KRom &r, const KState &s, con
   return V;
 }
 
-// boundzk (iterEKF.m:186-205; getChatZ iterEKF.m:523-602, diagonal only) inside k_cell,
-// lane per cell: for each corner j in order, its getChatV row and the 26 quadratic forms
-// row' * Sigma1 * row with Sigma of the first corner (iterEKF.m:192), summed over the
-// corners as ((((0 + q0) + q1) + q2) + q3) -- k_bounds' quad order, so the bits are
-// k_bounds'.  Off by default: on k_cell's one-wave-per-SIMD chain the forms took as long
-// as the lane-quad k_bounds at 4 waves per SIMD (r04g A/B: 2.48e8 vs 2.50e8), which also
-// saved nothing by skipping the hand-off record.
-#ifndef MPCEKF_CELL_BOUNDS
-#define MPCEKF_CELL_BOUNDS 0
-#endif
-bool cell_computes_bounds() { return MPCEKF_CELL_BOUNDS != 0; }
-template <int NZ>
-__device__ __forceinline__ void cell_bounds(const KRom &r, const CellCtx &cc, const XI &xi, const BoundK &b, double S0,
-                                            double *zo) {
-  double S1b[NPK];
-  load_S(cc.erec + (size_t)xi.m[0] * REC, S1b);  // the record k_cell just stored (or caught up)
-#pragma unroll
-  for (int k = 0; k < NX; ++k)
-#pragma unroll
-    for (int l = k + 1; l < NX; ++l) S1b[pk(k, l)] = 2 * S1b[pk(k, l)];
-  const bool ph0pp = rowf(r, R_PHISE0, G_PPHIS);
-  double ChV[4][NX], cph0[4][NX];
-  const double *Cm[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    Cm[j] = cc.L + xi.m[j] * cc.stride;
-    chat_row(r, b.K, Cm[j], xi.g[j], ChV[j]);
-#pragma unroll
-    for (int k = 0; k < NX; ++k) {
-      double v = xi.g[j] * Cm[j][R_PHISE0 * NX + k];
-      if (ph0pp) v = v + ChV[j][k];
-      cph0[j][k] = v;
-    }
-  }
-  // the constant-column term (c0 * S0) * c0 of each kind (C0_*), picked per row
-  const double cv1 = b.C0, cv2 = b.r0n, cv3 = b.r0p, cv4 = b.dUn * b.r0n, cv5 = b.dUp * b.r0p, cv6 = -b.dUn * b.r0n;
-#pragma unroll 1
-  for (int q = 0; q < r.nz; ++q) {  // one form at a time
-    const bool fpp = rowf(r, q, G_PPHIS), fph = rowf(r, q, G_PHIE);
-    double sz = 0.0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const double g = xi.g[j];
-      double row[NX];
-      if (fpp) {
-#pragma unroll
-        for (int k = 0; k < NX; ++k) row[k] = __builtin_fma(g, Cm[j][q * NX + k], ChV[j][k]);
-      } else {
-#pragma unroll
-        for (int k = 0; k < NX; ++k) row[k] = g * Cm[j][q * NX + k];
-      }
-      if (fph)
-#pragma unroll
-        for (int k = 0; k < NX; ++k) row[k] = row[k] - cph0[j][k];
-      sz = sz + qform(S1b, row);
-    }
-    const int kd = r.c0k[q];
-    const double cv = kd == 1 ? cv1 : kd == 2 ? cv2 : kd == 3 ? cv3 : kd == 4 ? cv4 : kd == 5 ? cv5 : kd == 6 ? cv6 : 0.0;
-    zo[r.perm[q]] = 3 * sqrt(sz + (cv * S0) * cv);
-  }
-  double sv = 0.0;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) sv = sv + qform(S1b, ChV[j]);
-  sv = sv + b.C0 * S0 * b.C0;
-  const double rr = -r.Ts / (3600 * r.Q);
-  zo[r.nz] = 3 * sqrt(sv);
-  zo[r.nz + 1] = 3 * sqrt(rr * S0 * rr);
-}
-
-// 1: k_cell's simStep after the EKF's first record reads are issued, so the plant's chain
-// overlaps their round trip; measured slower (r04i same-box A/B: k_cell 143 vs 134 us)
-#ifndef MPCEKF_CELL_PLANT_LATE
-#define MPCEKF_CELL_PLANT_LATE 0
-#endif
-// k_cell also runs hildreth.m (the fused step's k_hild) after a block barrier.  Off by
-// default: it needs the in-kernel slow path (MPCEKF_HILD_INLINE_SLOW), and k_cell + Hildreth
-// as one kernel measured 255.7 us against 161 + 89.5 as two (r04g A/B)
-#ifndef MPCEKF_CELL_HILD
-#define MPCEKF_CELL_HILD 0
-#endif
-// (with its slow lanes finished in the same kernel: MPCEKF_HILD_INLINE_SLOW)
-bool cell_runs_hild() { return MPCEKF_CELL_HILD != 0 && MPCEKF_HILD_INLINE_SLOW != 0; }
 template <int NZ, int PARTS, bool MB = false, bool GR = false, bool PL = false>
 __global__ void __launch_bounds__(256) k_cell(const KRom r, const KCfg cf, const KState s, const KIO io) {
   extern __shared__ double lds[];
@@ -2313,14 +2022,11 @@ __global__ void __launch_bounds__(256) k_cell(const KRom r, const KCfg cf, const
   const double *Tp = tb + r.cell_tab + r.cell_tablen;
   const double *Zp = Tp + MAXT;
   const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  // the plant's ring inputs for this step (MPCEKF_RING_LATE: stored after the cell's last
-  // load, below, so that no load of the step waits for their stores)
+  // the plant's ring inputs for this step (stored after the cell's last load, below, so
+  // that no load of the step waits for their stores)
   double ring_u = 0.0, ring_p = 0.0;
   bool ring_late = false;
-  PlantOut pout;  // MPCEKF_PLANT_STORE_LATE: the plant's stores, issued after body
-  pout.on = false;
-  // the per-cell work as a lambda: its early exits return here, so every lane of the block
-  // reaches the barrier of the fused Hildreth below
+  // the per-cell work as a lambda: its early exits return here, to the late ring stores
   auto body = [&]() {
   if (c >= s.n) return;
   const int nz = r.nz;
@@ -2375,23 +2081,22 @@ __global__ void __launch_bounds__(256) k_cell(const KRom r, const KCfg cf, const
   double ik = 0.0, vk = 0.0;
   double vplant = 0.0;
   bool planted = false;
-  // runMPC.m:85: [voltage, ...] = OB_step(uk, TC, cellState, ROM), first (with
-  // MPCEKF_CELL_PLANT_LATE once the EKF's first record reads are issued; every path below
-  // runs it before it returns)
+  // runMPC.m:85: [voltage, ...] = OB_step(uk, TC, cellState, ROM), first.  Only the first
+  // call does anything; the later ones are kept because without them the compiler orders
+  // the plant's replay fmas differently (same instructions, another schedule).
   auto run_plant = [&]() {
     if constexpr ((PARTS & P_EKF) && !MB) {
       if (fplant && !planted) {
         if (c == 0 && io.lazy_t) *s.hslow = 0;  // k_hild_slow of the previous step has finished
         ring_u = s.uk[c];
-        vplant = cell_plant<NZ, PL>(r, s, cc.L, tb, Tp, Zp, c, io.lazy_t, ring_u, Tc, st,
-                                    MPCEKF_RING_LATE ? &ring_p : nullptr, MPCEKF_PLANT_STORE_LATE ? &pout : nullptr);
-        ring_late = MPCEKF_RING_LATE && io.lazy_t;
+        vplant = cell_plant<NZ, PL>(r, s, cc.L, tb, Tp, Zp, c, io.lazy_t, ring_u, Tc, st, ring_p);
+        ring_late = io.lazy_t != 0;
         s.vk[c] = vplant;
         planted = true;
       }
     }
   };
-  if (!MPCEKF_CELL_PLANT_LATE) run_plant();
+  run_plant();
   if ((PARTS & P_EKF) && (io.mode & (MODE_EKF | MODE_FUSED))) {
     if (st & ST_ERROR) {
       run_plant();
@@ -2399,7 +2104,7 @@ __global__ void __launch_bounds__(256) k_cell(const KRom r, const KCfg cf, const
       return;
     }
     ik = fused ? s.uk[c] : io.ik_in[c];
-    vk = fused ? s.vk[c] : io.vk_in[c];  // the plant's Vcell replaces it once the plant has run
+    vk = fused ? s.vk[c] : io.vk_in[c];  // the plant's Vcell replaces it below
     int warn = s.warn[c];
     if (warn > cf.max_warn) {  // iterEKF.m:55-59
       run_plant();
@@ -2569,14 +2274,16 @@ __global__ void __launch_bounds__(256) k_cell(const KRom r, const KCfg cf, const
       dup[j] = false;
 #pragma unroll
       for (int i = 0; i < j; ++i) dup[j] = dup[j] || xi.m[i] == xi.m[j];
-      if (j < MPCEKF_REC_ONCE) load_rec(cc.erec + (size_t)xi.m[j] * REC, xr[j], Sr[j]);
+      // corner 0's Sigma is what the gains use first: its whole record is read here; the
+      // other corners read Sigma at their update (holding more spills: DESIGN.md 4.2)
+      if (j == 0) load_rec(cc.erec + (size_t)xi.m[j] * REC, xr[j], Sr[j]);
       else load_x(cc.erec + (size_t)xi.m[j] * REC, xr[j]);
       tsj[j] = t ? s.ts_ekf[c * r.NM + xi.m[j]] : 0;
     }
-    // step t's ring input: the plant stores this cell's priorI there (k_plant4, or cell_plant
-    // below, which may not have run yet)
+    // step t's ring input: the plant stores this cell's priorI there (k_plant4; cell_plant's
+    // is stored only after body)
     const double pt = t ? (fplant ? s.priorI[c] : s.hist_p[(size_t)(t % LAZY_H) * s.n + c]) : 0.0;
-    run_plant();  // the records above are in flight while the plant's chain runs
+    run_plant();
     if (planted) vk = vplant;
     if (t) {
 #pragma unroll
@@ -2636,15 +2343,13 @@ __global__ void __launch_bounds__(256) k_cell(const KRom r, const KCfg cf, const
     __builtin_amdgcn_sched_barrier(0);
     STAMP(5);
     double xu[4][NX];  // corner j's xhat after its update
-    // MPCEKF_S_AHEAD: corner j+1's Sigma is loaded before corner j's record is stored.  On
+    // Corner j+1's Sigma is loaded before corner j's record is stored.  On
     // gfx950 one counter (vmcnt) covers loads and stores in issue order, so a load issued
     // after a store cannot be waited for without waiting for the store as well; loaded one
     // corner ahead, the wait for Sigma_{j+1} no longer includes corner j's store.  A corner
     // that repeats an earlier model (dup) reads its record after that store, as before.
     double Sn[NPK];
-    auto s_ahead = [&](int j) {
-      return MPCEKF_S_AHEAD && j < 4 && j >= MPCEKF_REC_ONCE && !dup[j];
-    };
+    auto s_ahead = [&](int j) { return j >= 1 && j < 4 && !dup[j]; };
     if (s_ahead(1)) load_S(cc.erec + (size_t)xi.m[1] * REC, Sn);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -2655,18 +2360,16 @@ __global__ void __launch_bounds__(256) k_cell(const KRom r, const KCfg cf, const
       } else {
 #pragma unroll
         for (int k = 0; k < NX; ++k) xj[k] = xr[j][k];
-        if (j < MPCEKF_REC_ONCE) {
+        if (j == 0) {
 #pragma unroll
           for (int k = 0; k < NPK; ++k) Sj[k] = Sr[j][k];
-        } else if (s_ahead(j)) {
+        } else {  // loaded one corner ahead (s_ahead(j): j >= 1 and not a duplicate)
 #pragma unroll
           for (int k = 0; k < NPK; ++k) Sj[k] = Sn[k];
-        } else {
-          load_S(rec, Sj);
         }
         if (t && j > 0) replay_S(Sj, cc.L + xi.m[j] * cc.stride + NZ * NX + NZ, tsj[j], t, cf.SigmaW);
       }
-      meas_update_regs<MPCEKF_CELL_OUTLINE>(xj, Sj, Lg[j], St[j], res);
+      meas_update_regs<false>(xj, Sj, Lg[j], St[j], res);
       if (j + 1 < 4 && s_ahead(j + 1)) load_S(cc.erec + (size_t)xi.m[j + 1] * REC, Sn);
       store_rec(rec, xj, Sj);
       if (t) s.ts_ekf[c * r.NM + xi.m[j]] = t;
@@ -2738,9 +2441,6 @@ __global__ void __launch_bounds__(256) k_cell(const KRom r, const KCfg cf, const
 #pragma unroll
       for (int j = 0; j < 4; ++j) { io.xm_out[c * 4 + j] = xi.m[j]; io.xg_out[c * 4 + j] = xi.g[j]; }
     }
-    if (MPCEKF_CELL_BOUNDS && io.zbk && !io.bnd)
-      cell_bounds<NZ>(r, cc, xi, bound_k(r, cc, SOC0 - x0 * (r.Ts / (3600 * r.Q)), Z[R_TE1], Z[R_TH0], Z[R_TEE], Z[R_TH3]),
-                      S0, io.zbk + c * (nz + 2));
     }  // OB
   }
   if (!(PARTS & (P_MPC | P_LIN))) return;
@@ -2785,7 +2485,6 @@ __global__ void __launch_bounds__(256) k_cell(const KRom r, const KCfg cf, const
     return;
   }
 
-#ifndef PROBE_NO_MPC
   if (io.mode & (MODE_MPC | MODE_FUSED)) {
     if (!fused) {
       if (st & ST_ERROR) { fail_outputs(); return; }
@@ -2847,20 +2546,12 @@ __global__ void __launch_bounds__(256) k_cell(const KRom r, const KCfg cf, const
       }
     }
   }
-#endif
   };
   body();
-  if (MPCEKF_PLANT_STORE_LATE && pout.on) plant_store(r, s, c, io.lazy_t, pout);
   if (ring_late) {  // every path of body ran the plant; the ring's slot t is read by no load of this step
     const size_t slot = (size_t)(io.lazy_t % LAZY_H) * s.n + c;
     s.hist_u[slot] = ring_u;
     s.hist_p[slot] = ring_p;
-  }
-  if constexpr (MPCEKF_CELL_HILD && (PARTS & P_MPC) != 0) {
-    if (io.hild) {  // hildreth.m in the same kernel (no k_hild launch): the blob's LDS becomes the
-      __syncthreads();  // per-lane Hildreth slots once every wave of the block is done with it
-      if (c < s.n) hild_cell(cf, s, io, c);
-    }
   }
 }
 
@@ -3722,15 +3413,11 @@ int launch_flush(const KRom &r, const KCfg &c, const KState &s, int t, int new_t
   if (c_hi <= c_lo) return 0;
   static_assert((LAZY_H & (LAZY_H - 1)) == 0 && LAZY_H <= 64, "k_flush: ring slots live in lanes");
   // persistent waves striding over cells, as many as fit: 2 per SIMD with the pipelined
-  // loads (210 VGPRs), 3 without (150)
-  const int64_t wmax = MPCEKF_FLUSH_PF ? 2048 : 3072;
+  // loads (210 VGPRs)
+  const int64_t wmax = 2048;
   const int64_t waves = c_hi - c_lo < wmax ? c_hi - c_lo : wmax;
-  if (MPCEKF_FLUSH_COAL && r.NM <= 64)
-    hipLaunchKernelGGL(k_flush_coal, dim3((int)((waves + 3) / 4)), dim3(256), 0, (hipStream_t)stream, r, c, s, t,
-                       new_ts, c_lo, c_hi);
-  else
-    hipLaunchKernelGGL(k_flush, dim3((int)((waves + 3) / 4)), dim3(256), 0, (hipStream_t)stream, r, c, s, t, new_ts,
-                       c_lo, c_hi);
+  hipLaunchKernelGGL(k_flush, dim3((int)((waves + 3) / 4)), dim3(256), 0, (hipStream_t)stream, r, c, s, t, new_ts,
+                     c_lo, c_hi);
   return (int)hipGetLastError();
 }
 
@@ -3746,9 +3433,7 @@ int launch_bulk(const KRom &r, const KCfg &c, const KState &s, const double *iap
 template <int NZ, int PARTS, bool MB>
 static void launch_cell_t(const KRom &r, const KCfg &c, const KState &s, const KIO &io, hipStream_t st) {
   const int block = spread_block(s.n, 1, 256);
-  int lds = cell_lds_bytes(r);
-  const int hl = block / 64 * (int)HILD_LDS_PER_WAVE;
-  if (io.hild) lds = lds > hl ? lds : hl;  // the Hildreth slots
+  const int lds = cell_lds_bytes(r);
   with_gr_pl(r.rom_global, r.npoly, [&](auto gr, auto pl) {
     const auto kern = k_cell<NZ, PARTS, MB, decltype(gr)::value, decltype(pl)::value>;
     static bool attr = false;  // one per instantiation
@@ -3887,10 +3572,8 @@ int launch_hild(const KCfg &c, const KState &s, const KIO &io, void *stream) {
   const int block = spread_block(s.n, 1, 256);
   hipLaunchKernelGGL(k_hild, dim3(grid_for(s.n, block)), dim3(block), hild_lds_bytes(block), (hipStream_t)stream, c, s,
                      io);
-  if (!MPCEKF_HILD_INLINE_SLOW) {
-    const int gs = grid_for(s.n, 64) < 256 ? grid_for(s.n, 64) : 256;
-    hipLaunchKernelGGL(k_hild_slow, dim3(gs), dim3(64), HILD_LDS_PER_WAVE, (hipStream_t)stream, c, s, io);
-  }
+  const int gs = grid_for(s.n, 64) < 256 ? grid_for(s.n, 64) : 256;
+  hipLaunchKernelGGL(k_hild_slow, dim3(gs), dim3(64), HILD_LDS_PER_WAVE, (hipStream_t)stream, c, s, io);
   return (int)hipGetLastError();
 }
 

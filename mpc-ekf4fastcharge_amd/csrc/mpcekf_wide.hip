@@ -8,10 +8,10 @@
 //                                     violation test, streamed row by row (no M or
 //                                     gamma arrays live); finishes cells that need no QP
 //   k_hild_prep       lane per cell   hildreth.m:17-29: R = chol(E) (handed over), K =
-//                                     M*(E\F) + gamma (MPCEKF_WIDE_XPRO=0: also X(:,i) =
-//                                     E\M(i,:)' for the 80 distinct rows and H_ii)
-//   k_hild_wide       8-lane group    X and H_ii from R in its prologue (XPRO), then the
-//                     per cell        hildreth.m:32-42 sweeps: lane k holds v_k (and v_k+8)
+//                                     M*(E\F) + gamma
+//   k_hild_wide       8-lane group    X(:,i) = E\M(i,:)' for the 80 distinct rows and H_ii
+//                     per cell        from R in its prologue (X never goes through HBM), then the
+//                                     hildreth.m:32-42 sweeps: lane k holds v_k (and v_k+8)
 //                                     and column k of X in registers; row values are summed
 //                                     by a DPP butterfly (oracle hild_row_t)
 //   k_hild_wide_slow  lane per cell   the exact rules (inf/NaN rows, non-finite X or M,
@@ -31,15 +31,6 @@
 #endif
 #ifndef PREP_UNROLL
 #define PREP_UNROLL 1  // k_hild_prep's row loops (rows in flight per wave)
-#endif
-#ifndef MPCEKF_WIDE_SORT
-#define MPCEKF_WIDE_SORT 1
-#endif
-// 1: k_hild_wide forms X(:,i) = E\M(i,:)' and H_ii itself from chol(E) (k_hild_prep hands
-// over R, 55 doubles per cell, instead of writing X, 800, to HBM for k_hild_wide to read
-// back); 0: k_hild_prep writes X and H_ii
-#ifndef MPCEKF_WIDE_XPRO
-#define MPCEKF_WIDE_XPRO 1
 #endif
 #include <cmath>
 #include <cstdint>
@@ -81,7 +72,6 @@ struct W {
 // k_hild_sort's bins over last step's sweep count (0 .. maxIter)
 constexpr int SWEEP_BINS = 64;
 __device__ __forceinline__ int sweep_bin(int it, int maxIter) {
-  if (!MPCEKF_WIDE_SORT) return 0;
   const int m = maxIter > 0 ? maxIter : 1;
   const int t = it < 0 ? 0 : it > m ? m : it;
   return (int)(((long long)t * SWEEP_BINS) / (m + 1));
@@ -196,12 +186,10 @@ __device__ __forceinline__ void mrow_vec(int i, const double *Hb, double b[NC]) 
   }
 }
 
-// One row of k_hild_prep: K_i = M(i,:)*(E\F) + gamma_i, and for a distinct row X(:,u) =
-// E\M(i,:)' and H_ii (also stored for the negated copy at i + NC when dup)
+// One row of k_hild_prep: K_i = M(i,:)*(E\F) + gamma_i (X(:,i) and H_ii are k_hild_wide's)
 template <int NP, int NC>
-__device__ __forceinline__ void prep_row(const KWide &w, const double *pb, int64_t n, int64_t c, int i, bool neg,
-                                         int u, bool dup, const double R[NC][NC], const double y[NC],
-                                         const double b[NC], double gam, bool &fin, double *xt, bool act) {
+__device__ __forceinline__ void prep_row(const KWide &w, int64_t c, int i, const double y[NC], const double b[NC],
+                                         double gam, bool &fin, bool act) {
   using T = W<NP, NC>;
   constexpr int NCON = T::NCON;
   double kk = 0.0;
@@ -211,50 +199,22 @@ __device__ __forceinline__ void prep_row(const KWide &w, const double *pb, int64
     fin = fin && isfinite(b[k]);
   }
   if (act) w.K[(size_t)c * NCON + i] = kk + gam;
-  if (neg || MPCEKF_WIDE_XPRO) return;  // H_ii of -b equals that of b (stored with the b row)
-  double x[NC];
-  chol_apply<NC>(R, b, x);
-  double h = 0.0;
-  const int l = threadIdx.x;
-#pragma unroll
-  for (int k = 0; k < NC; ++k) {
-    h = h + b[k] * x[k];
-    fin = fin && isfinite(x[k]);
-    xt[l * (NC + 1) + k] = x[k];  // odd stride: fewer bank conflicts
-  }
-  if (act) {
-    w.hii[(size_t)c * NCON + i] = h;
-    if (dup) w.hii[(size_t)c * NCON + i + NC] = h;
-  }
-  // X(:, u) of the wave's 64 cells is one contiguous [64][NC] span of w.X: written back
-  // from the LDS tile as 64 consecutive doubles per store (lane-per-cell stores of x[k]
-  // hit 64 lines per instruction), only the active cells' entries
-  __syncthreads();  // one wave per block
-  const int64_t c0 = (int64_t)blockIdx.x * blockDim.x;
-  const uint64_t am = __ballot(act);
-#pragma unroll
-  for (int j = 0; j < NC; ++j) {
-    const int e = j * 64 + l, cl = e / NC;
-    if ((am >> cl) & 1) w.X[((size_t)u * n + c0) * NC + e] = xt[cl * (NC + 1) + e % NC];
-  }
-  __syncthreads();
 }
 
 // ---------------------------------------------------------------------------
 // k_hild_prep: hildreth.m:28-29 for the cells that run it (hflag == 1)
 // ---------------------------------------------------------------------------
-// hflag after: 1 = k_hild_wide, 2 = exact path with X/K/H_ii ready, 3 = exact path
-// that must build them (E not SPD: MATLAB's \ falls back to LU), 4 (XPRO) = exact path
-// that builds X/H_ii from the stored R (K ready).
+// hflag after: 1 = k_hild_wide, 3 = exact path that must build X/K/H_ii (E not SPD:
+// MATLAB's \ falls back to LU), 4 = exact path that builds X/H_ii from the stored R (K
+// ready).  (2, the exact path with X/K/H_ii ready, is never set by this chain.)
 template <int NP, int NC>
 __global__ void __launch_bounds__(64) k_hild_prep(const KState s, const KWide w) {
   using T = W<NP, NC>;
   constexpr int NCON = T::NCON;
-  __shared__ double xt[64 * (NC + 1)];  // the wave's X(:, u) tile (one wave per block)
   const int64_t n = s.n;
   const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   bool act = c < n && s.hflag[c] == 1;
-  if (!__ballot(act)) return;  // uniform: every lane of the wave takes part in the tile stores
+  if (!__ballot(act)) return;
   const int64_t cr = act ? c : (int64_t)blockIdx.x * blockDim.x;  // inactive lanes read a valid cell
   const double *pb = w.prob;
   double E[NC][NC], R[NC][NC], F[NC], y[NC];
@@ -263,7 +223,7 @@ __global__ void __launch_bounds__(64) k_hild_prep(const KState s, const KWide w)
     s.hflag[c] = 3;
     act = false;
   }
-  if (MPCEKF_WIDE_XPRO && act) {
+  if (act) {  // R for k_hild_wide's prologue: 55 doubles per cell instead of X's 800
     int e = 0;
 #pragma unroll
     for (int a = 0; a < NC; ++a)
@@ -288,8 +248,7 @@ __global__ void __launch_bounds__(64) k_hild_prep(const KState s, const KWide w)
     double b[NC];
 #pragma unroll
     for (int k = 0; k < NC; ++k) b[k] = mconst<NC>(i, k);
-    prep_row<NP, NC>(w, pb, n, cr, i, xneg<NC>(i), xslot<NP, NC>(i), i < NC || (i >= 2 * NC && i < 3 * NC), R, y, b,
-                     gi, fin, xt, act);
+    prep_row<NP, NC>(w, cr, i, y, b, gi, fin, act);
   }
   double hn = pb[T::HV * n + cr];
 #pragma unroll 1
@@ -309,12 +268,12 @@ __global__ void __launch_bounds__(64) k_hild_prep(const KState s, const KWide w)
       const double gi = gam;
       hn = pb[(T::HV + blk * NP + r + 1) * n + cr];  // HV + 3 NP is GAM: in the record
       gam = pb[(T::GAM + i + 1) * n + cr];          // GAM + NCON is ERR: in the record
-      prep_row<NP, NC>(w, pb, n, cr, i, false, i - 2 * NC, false, R, y, b, gi, fin, xt, act);
+      prep_row<NP, NC>(w, cr, i, y, b, gi, fin, act);
     }
   }
-  // a non-finite M entry (XPRO: X is checked by k_hild_wide): the exact path, which with
-  // XPRO builds X and H_ii from R first (hflag 4)
-  if (act && !fin) s.hflag[c] = MPCEKF_WIDE_XPRO ? 4 : 2;
+  // a non-finite M entry (X is checked by k_hild_wide): the exact path, which builds X and
+  // H_ii from R first (hflag 4)
+  if (act && !fin) s.hflag[c] = 4;
 }
 
 // ---------------------------------------------------------------------------
@@ -529,13 +488,12 @@ __global__ void __launch_bounds__(128, 1) k_hild_wide(const KCfg cf, const KStat
                     2 * (T::ZERO_LDS + T::GROUPS * T::CELL_LDS + T::WAVES * T::JUNK) * 8 <= 160 * 1024,
                 "two blocks per CU");
   for (int i = threadIdx.x; i < NCON; i += blockDim.x) zero[i] = 0.0;
-  if (MPCEKF_WIDE_XPRO && (int64_t)blockIdx.x * T::GROUPS >= w.q[0]) return;  // block-uniform: nothing listed
+  if ((int64_t)blockIdx.x * T::GROUPS >= w.q[0]) return;  // block-uniform: nothing listed
   const bool act = slot < w.q[0];            // k_hild_sort's count
   const int64_t c = act ? w.list[slot] : 0;  // cells in k_hild_bin<true>'s order
   bool ok = true;
   static_assert(NC <= LN + 2 && T::NX_ROWS % LN == 0, "columns >= 8 spread as pairs over 4 lane pairs");
   double X0[T::NX_ROWS], X1[T::NX_ROWS / 4];
-#if MPCEKF_WIDE_XPRO
   // hildreth.m:28's X(:,i) = E\M(i,:)' and H_ii = M(i,:)*X(:,i) for the group's cell, from
   // k_hild_prep's R = chol(E): lane k solves the distinct rows u = 8j + k (chol_apply, the
   // arithmetic k_hild_prep would use), and the group transposes each chunk of 8 solutions
@@ -596,26 +554,10 @@ __global__ void __launch_bounds__(128, 1) k_hild_wide(const KCfg cf, const KStat
       Kl[i] = w.K[(size_t)c * NCON + i];
     }
   }
-#else
-  if (act) {
-    for (int i = k; i < NCON; i += LN) {
-      const double li = s.lam[(size_t)i * n + c];
-      const double hii = w.hii[(size_t)c * NCON + i];
-      ok = ok && isfinite(li) && hild_rok(hii);
-      lam[i] = li;
-      Kl[i] = w.K[(size_t)c * NCON + i];
-      hr[i] = make_double2(hii, 1.0 / hii);
-    }
-    for (int j = k; j < 3 * HPW; j += LN) {
-      const int b = j / HPW, q = j % HPW;
-      hp[j] = q < NC - 1 ? 0.0 : w.prob[(T::HV + b * NP + q - (NC - 1)) * n + c];
-    }
-  }
-#endif
   __syncthreads();
   if (!act) return;
   const int gshift = LN * (g % (64 / LN));
-  constexpr int SLOW = MPCEKF_WIDE_XPRO ? 4 : 2;  // the exact path (4: it builds X / H_ii first)
+  constexpr int SLOW = 4;  // the exact path, which builds X / H_ii from R first
   if ((__ballot(!ok) >> gshift) & 0xFFull) {  // outside the fast form's domain
     if (k == 0) s.hflag[c] = SLOW;
     return;
@@ -631,15 +573,6 @@ __global__ void __launch_bounds__(128, 1) k_hild_wide(const KCfg cf, const KStat
   // exec-masked store splits the wave's control flow inside the row)
   double *lst = lam;
   if (k != 0) lst = lds + T::ZERO_LDS + T::GROUPS * T::CELL_LDS + (threadIdx.x >> 6) * T::JUNK + (threadIdx.x & 63);
-#if !MPCEKF_WIDE_XPRO
-#pragma unroll
-  for (int u = 0; u < T::NX_ROWS; ++u) X0[u] = k < NC ? w.X[((size_t)u * n + c) * NC + k] : 0.0;
-#pragma unroll
-  for (int sl = 0; sl < T::NX_ROWS / 4; ++sl) {
-    const int u = 4 * sl + (k >> 1), col = LN + (k & 1);
-    X1[sl] = col < NC ? w.X[((size_t)u * n + c) * NC + col] : 0.0;
-  }
-#endif
   // X(:, i) of constraint row i for lane k's two columns (the -Cu / -I rows negated)
   auto xrow = [&](int i, double &x0, double &x1) {
     const int u = xslot<NP, NC>(i);

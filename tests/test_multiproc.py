@@ -73,7 +73,7 @@ def test_bench_algorithmic_bytes():
     # from k_cell's hand-off record
     assert "plant" not in b and set(b) == {"flush", "cell", "hild", "bounds"}
     assert b["bounds"] == (14 + 15 + 4 + 28) * 8
-    # boundzk inside k_cell (MPCEKF_CELL_BOUNDS=1): no record, corner 1's Sigma + boundzk in k_cell
+    # boundzk inside k_cell (no longer built; bench.py still models it): no record, corner 1's Sigma + boundzk
     bc = bench.algorithmic_bytes_per_cell(63, 23, True, bounds_kernel=False)
     assert set(bc) == {"flush", "cell", "hild"} and bc["cell"] == b["cell"] - 14 * 8 + 15 * 8 + 28 * 8
     # Np = 20 / Nc = 10: k_hild_prep hands k_hild_wide chol(E) (55) and K (100), not X (800 per cell)
