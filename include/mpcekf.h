@@ -445,6 +445,70 @@ int mpcekf_get_limits(mpcekf_ctx *ctx, int32_t nfields, const int32_t *fields, d
  * mpcekf_set_limits; a no-op on a context that never set any. */
 int mpcekf_clear_limits(mpcekf_ctx *ctx);
 
+/* ---- per-cell charge summary along the fused loop (not part of the reference interface) ----
+ * What a protocol sweep reads back per cell -- time to a SOC, the smallest side-reaction
+ * overpotential, peak voltage and current, charge moved, solver effort -- accumulated on the
+ * device over any number of calls, instead of runMPC.m:55-69's per-step stores reduced on the
+ * host.  mpcekf_step_summary is mpcekf_step's fused loop (runMPC.m:84-111) with no trajectory
+ * output: the same launches and the same state, bit for bit; each step's u_store,
+ * voltage_store, SOC_store, phise_store and cost.nexec rows (and one slot of OB_step's obs)
+ * go to a window of MPCEKF_SUM_WIN rows on the device, folded into the record once per
+ * window and at the end of the call, so the call's device memory does not grow with nsteps.
+ *
+ * t counts the summary steps since mpcekf_summary_begin, from 1, across calls.  A step is
+ * counted for a cell when none of its u, v, soc, phise is NaN (a cell in error has NaN
+ * outputs from its failing step on).  Every value is a double; step indices and counts are
+ * exact integers.
+ *   SEEN        steps run since begin, counted or not
+ *   STEPS       counted steps
+ *   ERR_STEP    t of the first step not counted; 0: none
+ *   T_REACH     t of the first counted step with soc >= soc_reach[c]; 0: never, or no
+ *               threshold.  soc_reach is in mpcekf_traj.soc's unit: zk(end) (runMPC.m:109), the
+ *               EKF's SOC as a fraction 0..1 (SOC0 / 100 - x0 Ts / (3600 Q)) -- not the
+ *               percent of mpcekf_config.target_soc and mpcekf_init_cells
+ *   U_MIN, U_MIN_STEP, U_MAX            over counted steps of u_store (a charging current is
+ *                                       negative: U_MIN is the peak charging current)
+ *   V_MAX, V_MAX_STEP, V_MIN            voltage_store
+ *   PHISE_MIN, PHISE_MIN_STEP           phise_store, the EKF's estimate (runMPC.m:94-95)
+ *   U_LAST, V_LAST, SOC_LAST, PHISE_LAST   the last counted step's values
+ *   U_SUM       u added in step order, plain fp64 additions from +0 (Ah = -U_SUM Ts / 3600)
+ *   NEXEC_SUM, NEXEC_MAX, NSAT          cost.nexec over counted steps; NSAT: steps with
+ *                                       nexec >= max_hild
+ *   OBS_MIN, OBS_MIN_STEP, OBS_MAX, OBS_MAX_STEP   the plant's slot obs_slot over the steps
+ *               where it is not NaN (counted or not); NaN / 0 without a slot
+ * An extremum is replaced only on a strict < / >: the first occurrence wins, and -0 and +0 do
+ * not displace each other.  With no counted step the extrema (NEXEC_MAX too) and the _LAST
+ * fields are NaN, their step fields and the sums 0. */
+enum {
+  MPCEKF_SUM_SEEN = 0, MPCEKF_SUM_STEPS, MPCEKF_SUM_ERR_STEP, MPCEKF_SUM_T_REACH,
+  MPCEKF_SUM_U_MIN, MPCEKF_SUM_U_MIN_STEP, MPCEKF_SUM_U_MAX,
+  MPCEKF_SUM_V_MAX, MPCEKF_SUM_V_MAX_STEP, MPCEKF_SUM_V_MIN,
+  MPCEKF_SUM_PHISE_MIN, MPCEKF_SUM_PHISE_MIN_STEP,
+  MPCEKF_SUM_U_LAST, MPCEKF_SUM_V_LAST, MPCEKF_SUM_SOC_LAST, MPCEKF_SUM_PHISE_LAST,
+  MPCEKF_SUM_U_SUM, MPCEKF_SUM_NEXEC_SUM, MPCEKF_SUM_NEXEC_MAX, MPCEKF_SUM_NSAT,
+  MPCEKF_SUM_OBS_MIN, MPCEKF_SUM_OBS_MIN_STEP, MPCEKF_SUM_OBS_MAX, MPCEKF_SUM_OBS_MAX_STEP,
+  MPCEKF_NSUM
+};
+#define MPCEKF_SUM_WIN 64 /* steps per window: the rows of device scratch a summary call uses */
+/* Allocates the record (first call) and resets it; soc_reach [ncells] or NULL (no threshold:
+ * T_REACH stays 0); obs_slot: one slot of mpcekf_obs_layout's record (e.g. negPhise0, the
+ * plant's own plating margin), or -1 for none.  A second begin resets the record.  May be
+ * called before mpcekf_init_cells (which does not touch the record).  MPCEKF_E_ARG: a NULL
+ * ctx, obs_slot outside -1 .. nobs - 1. */
+int mpcekf_summary_begin(mpcekf_ctx *ctx, const double *soc_reach, int32_t obs_slot);
+/* nsteps fused steps (mpcekf_step's, tc_degC as there: host [nsteps][ncells] or NULL) folded
+ * into the record.  MPCEKF_E_STATE without a begin (or before mpcekf_init_cells);
+ * MPCEKF_E_ARG: nsteps < 0.  A refused call leaves the context and the record as they were.
+ * The kernel that folds a window is not one of mpcekf_set_timing's five slots. */
+int mpcekf_step_summary(mpcekf_ctx *ctx, int32_t nsteps, const double *tc_degC);
+/* values [nfields][ncells]: row i = field fields[i] (distinct MPCEKF_SUM_* ids).
+ * MPCEKF_E_STATE without a begin; MPCEKF_E_ARG: a NULL pointer, nfields outside
+ * 1..MPCEKF_NSUM, an unknown or repeated id. */
+int mpcekf_get_summary(mpcekf_ctx *ctx, int32_t nfields, const int32_t *fields, double *values);
+/* Frees the record and the window; the context then behaves as one that never began.  A
+ * no-op without a begin. */
+int mpcekf_summary_end(mpcekf_ctx *ctx);
+
 /* ---- device memory (not part of the reference interface) ----
  * Device buffers for outputs_on_device calls, allocated by the library's own HIP
  * runtime so a host process never holds a second one (a framework's bundled

@@ -51,6 +51,15 @@
  *   values            = mpcekf_mex('getlimits', h, idx)                mpcekf_get_limits
  *                       ncells x numel(idx): what 'setlimits' stored, else the cfg scalar
  *                       mpcekf_mex('clearlimits', h)                   mpcekf_clear_limits
+ *                       mpcekf_mex('summarybegin', h, reach, slot)     mpcekf_summary_begin
+ *                       reach: [] or ncells SOC thresholds (the unit of 'step's soc: a fraction
+ *                       0..1); slot: [] or 0 for none, else one 1-based slot of the obs record
+ *                       mpcekf_mex('stepsummary', h, nsteps, tc)       mpcekf_step_summary
+ *                       'step' without outputs, folded into the per-cell summary record
+ *   s                 = mpcekf_mex('getsummary', h)                    mpcekf_get_summary
+ *                       struct of ncells x 1 column vectors, one per MPCEKF_SUM_* field
+ *                       (seen, steps, err_step, t_reach, u_min, ...; include/mpcekf.h)
+ *                       mpcekf_mex('summaryend', h)                    mpcekf_summary_end
  * Per-cell vectors are 1 x ncells or ncells x 1; zk / zbk are (nz+2) x ncells, xm / xg
  * 4 x ncells (xm: 0-based model index t*nZ+z), lin 35 x ncells -- MATLAB's column-major
  * k x ncells is the library's cell-major [ncells][k], so no copy is made for them.
@@ -365,7 +374,7 @@ static void gateway(mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
   static const char *const with_handle[] = {"destroy", "init", "step", "plant", "ekf", "linearize", "mpc",
                                             "graph", "mpcdiag", "get_state", "set_state", "scalars", "linfields",
                                             "plantobs", "obsslots", "obslayout", "stepobs", "setlimits", "getlimits",
-                                            "clearlimits"};
+                                            "clearlimits", "summarybegin", "stepsummary", "getsummary", "summaryend"};
   int known = 0;
   for (size_t i = 0; i < sizeof with_handle / sizeof *with_handle; ++i) known = known || !strcmp(cmd, with_handle[i]);
   if (!known) mexErrMsgIdAndTxt("mpcekf:arg", "unknown command %s", cmd);
@@ -411,6 +420,31 @@ static void gateway(mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
     }
     if (setlim && (!mxIsDouble(prhs[3]) || mxIsComplex(prhs[3])))
       mexErrMsgIdAndTxt("mpcekf:arg", "setlimits: values: expected a real double ncells x %zu array", nlimf);
+  }
+  /* the summary commands likewise: output count, argument classes, a slot that is no 1-based
+     integer (0 / []: none), an nsteps that is no non-negative integer */
+  const int sumbegin = !strcmp(cmd, "summarybegin"), stepsum = !strcmp(cmd, "stepsummary");
+  int32_t sumslot = -1, sumsteps = 0;
+  if (sumbegin || stepsum || !strcmp(cmd, "summaryend")) {
+    if (g_nlhs > 0) mexErrMsgIdAndTxt("mpcekf:arg", "%s: no output", cmd);
+  }
+  if (!strcmp(cmd, "getsummary") && g_nlhs > 1) mexErrMsgIdAndTxt("mpcekf:arg", "getsummary: at most 1 output");
+  if (sumbegin) {
+    if (nrhs > 2 && !mxIsEmpty(prhs[2]) && (!mxIsDouble(prhs[2]) || mxIsComplex(prhs[2])))
+      mexErrMsgIdAndTxt("mpcekf:arg", "summarybegin: reach: expected [] or ncells real doubles");
+    if (nrhs > 3 && !mxIsEmpty(prhs[3])) {
+      const double sd = scalar(prhs[3], "summarybegin: slot");
+      if (!(sd >= 0 && sd <= 2147483647.0) || sd != (double)(int32_t)sd)
+        mexErrMsgIdAndTxt("mpcekf:arg", "summarybegin: slot = %g is not a slot 1..nobs (0 or []: none)", sd);
+      sumslot = (int32_t)sd - 1;
+    }
+  }
+  if (stepsum) {
+    need(nrhs, 3, "'stepsummary', h, nsteps[, tc]");
+    const double nsd = scalar(prhs[2], "nsteps");
+    if (!(nsd >= 0 && nsd <= 2147483647.0) || nsd != (double)(int32_t)nsd)
+      mexErrMsgIdAndTxt("mpcekf:arg", "nsteps: expected a non-negative integer");
+    sumsteps = (int32_t)nsd;
   }
   mpcekf_ctx *h = handle(prhs[1]);
   int64_t n = 0;
@@ -567,6 +601,35 @@ static void gateway(mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
     chk(mpcekf_get_limits(h, (int32_t)nlimf, limf, mxGetDoubles(plhs[0])));
   } else if (!strcmp(cmd, "clearlimits")) {
     chk(mpcekf_clear_limits(h));
+  } else if (sumbegin) {
+    int32_t off[MPCEKF_OBS_COUNT + 1];
+    chk(mpcekf_obs_layout(h, off));
+    if (sumslot >= off[MPCEKF_OBS_COUNT])
+      mexErrMsgIdAndTxt("mpcekf:arg", "summarybegin: slot = %d is not a slot 1..%d (0 or []: none)", (int)sumslot + 1,
+                        (int)off[MPCEKF_OBS_COUNT]);
+    chk(mpcekf_summary_begin(h, nrhs > 2 ? opt_vec(prhs[2], nc, "summarybegin: reach (ncells)") : NULL, sumslot));
+  } else if (stepsum) {
+    chk(mpcekf_step_summary(h, sumsteps, nrhs > 3 ? opt_vec(prhs[3], nc * (size_t)sumsteps, "tc (ncells x nsteps)") : NULL));
+  } else if (!strcmp(cmd, "getsummary")) {
+    static const char *const sum_names[MPCEKF_NSUM] = {
+        "seen", "steps", "err_step", "t_reach", "u_min", "u_min_step", "u_max", "v_max", "v_max_step", "v_min",
+        "phise_min", "phise_min_step", "u_last", "v_last", "soc_last", "phise_last", "u_sum", "nexec_sum",
+        "nexec_max", "nsat", "obs_min", "obs_min_step", "obs_max", "obs_max_step"};
+    mxArray *a[MPCEKF_NSUM];
+    int32_t ids[MPCEKF_NSUM];
+    /* [nfields][ncells]: one scratch block, then a column vector per field */
+    double *vals = (double *)mxMalloc((size_t)MPCEKF_NSUM * nc * sizeof(double) + 8);
+    for (int f = 0; f < MPCEKF_NSUM; ++f) ids[f] = f;
+    chk(mpcekf_get_summary(h, MPCEKF_NSUM, ids, vals));
+    plhs[0] = mxCreateStructMatrix(1, 1, MPCEKF_NSUM, (const char **)sum_names);
+    for (int f = 0; f < MPCEKF_NSUM; ++f) {
+      a[f] = dmat(nc, 1);
+      if (nc) memcpy(mxGetDoubles(a[f]), vals + (size_t)f * nc, nc * sizeof(double));
+      mxSetField(plhs[0], 0, sum_names[f], a[f]);
+    }
+    mxFree(vals);
+  } else if (!strcmp(cmd, "summaryend")) {
+    chk(mpcekf_summary_end(h));
   } else if (!strcmp(cmd, "mpcdiag")) {
     need(nrhs, 3, "'mpcdiag', h, lin[, uk_1]");
     plhs[0] = mxCreateDoubleMatrix(7, (mwSize)nc, mxCOMPLEX);  /* interleaved (re, im): [ncells][7][2] */

@@ -25,6 +25,11 @@ S_SOCNAVG, S_SOCPAVG, S_X0, S_SIGMAX0, S_PRIORI, S_UK_1, S_UK, S_VK = range(8)
 OBS_COUNT = 25   # MPCEKF_OBS_COUNT: the fields of OB_step's obs (rom.py OBS_FIELDS)
 # MPCEKF_LIM_*: the per-cell limit fields of mpcekf_set_limits, by mpcekf_config's field names
 LIMIT_FIELDS = ("target_soc", "Crate", "u_max", "du_min", "du_max", "v_max", "phise_min", "z_max", "z_tol")
+# MPCEKF_SUM_*: the fields of the per-cell charge summary (mpcekf_get_summary), in enum order
+SUMMARY_FIELDS = ("seen", "steps", "err_step", "t_reach", "u_min", "u_min_step", "u_max", "v_max", "v_max_step",
+                  "v_min", "phise_min", "phise_min_step", "u_last", "v_last", "soc_last", "phise_last", "u_sum",
+                  "nexec_sum", "nexec_max", "nsat", "obs_min", "obs_min_step", "obs_max", "obs_max_step")
+SUM_WIN = 64     # MPCEKF_SUM_WIN
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
@@ -86,6 +91,7 @@ EXPORTS = [
     "mpcekf_get_scalars", "mpcekf_lin_fields",
     "mpcekf_obs_layout", "mpcekf_plant_step_obs", "mpcekf_plant_obs_slots", "mpcekf_step_ex_obs",
     "mpcekf_set_limits", "mpcekf_get_limits", "mpcekf_clear_limits",
+    "mpcekf_summary_begin", "mpcekf_step_summary", "mpcekf_get_summary", "mpcekf_summary_end",
     # the _async stage twins (include/mpcekf.h)
     "mpcekf_plant_step_async", "mpcekf_ekf_step_async", "mpcekf_linearize_async", "mpcekf_lin_fields_async",
     "mpcekf_mpc_step_async", "mpcekf_mpc_step_ex_async", "mpcekf_mpc_diag_async", "mpcekf_get_scalars_async",
@@ -155,6 +161,10 @@ def load():
     L.mpcekf_set_limits.argtypes = [vp, C.c_int32, _ip, _dp]
     L.mpcekf_get_limits.argtypes = [vp, C.c_int32, _ip, _dp]
     L.mpcekf_clear_limits.argtypes = [vp]
+    L.mpcekf_summary_begin.argtypes = [vp, _dp, C.c_int32]
+    L.mpcekf_step_summary.argtypes = [vp, C.c_int32, vp]
+    L.mpcekf_get_summary.argtypes = [vp, C.c_int32, _ip, _dp]
+    L.mpcekf_summary_end.argtypes = [vp]
     for nm in ("plant_step", "ekf_step", "linearize", "lin_fields", "mpc_step", "mpc_step_ex", "mpc_diag",
                "get_scalars", "plant_step_obs", "plant_obs_slots"):   # the _async twins take the synchronous call's arguments
         getattr(L, f"mpcekf_{nm}_async").argtypes = getattr(L, f"mpcekf_{nm}").argtypes

@@ -25,6 +25,7 @@
 #include "../../include/mpcekf.h"
 #include "mpcekf_eig.hpp"
 #include "mpcekf_kernels.hpp"
+#include "mpcekf_summary.hpp"
 
 using namespace mk;
 namespace mk {
@@ -222,6 +223,14 @@ struct mpcekf_ctx {
   double *d_lim = nullptr;
   bool percell = false;
   const double *lim() const { return percell ? d_lim : nullptr; }
+  // mpcekf_summary_begin .. _end: the record [NSUM][n], the thresholds [n] and the window the
+  // fused step's output rows land in during mpcekf_step_summary, SUM_WIN rows of u, v, soc,
+  // phise (double) and nexec (int) in d_sum_ring, one obs slot's in d_sum_obs (allocated by the
+  // first begin that names a slot).  Their sizes depend on n alone, never on a call's nsteps.
+  double *d_sum = nullptr, *d_sum_reach = nullptr, *d_sum_obs = nullptr;
+  char *d_sum_ring = nullptr;
+  int32_t sum_slot = -1;
+  size_t sum_row() const { return (((size_t)SUM_WIN * (size_t)n * 8) + 255) & ~(size_t)255; }  // one field's rows
   double *d_uk1p = nullptr;                      // [n] uk_1 before the step (poles / sv)
   int flush_period = LAZY_H;      // steps between all-model flushes (<= LAZY_H)
   // rolling flush (MPCEKF_FLUSH_ROLL=1, off by default): step t flushes the cell slice
@@ -1095,7 +1104,8 @@ int mpcekf_ctx_destroy(mpcekf_ctx *X) {
                   X->d_zbk,       X->d_tmp,        X->s.bigx, X->s.ekf,   X->s.lam,   X->d_ts, X->d_hist, X->d_stamps, X->d_bnd, X->d_xm, X->d_xg,
                   X->w.prob, X->w.X, X->w.R, X->w.K, X->w.hii, X->w.it, X->w.smin, X->d_lin, X->d_zsoc, X->d_mb, X->d_uk1p,
                   X->w.q, X->w.list, X->w.hist, X->d_poly, X->d_szk, X->d_sxg, X->d_sxm, X->d_slin, X->d_sv, X->d_zslot,
-                  X->d_obs_blob, X->d_obs, X->d_obs_plan, X->d_lim};
+                  X->d_obs_blob, X->d_obs, X->d_obs_plan, X->d_lim, X->d_sum, X->d_sum_reach, X->d_sum_obs,
+                  X->d_sum_ring};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   for (auto &g : X->graphs) (void)hipGraphExecDestroy(g.exec);
@@ -1202,12 +1212,23 @@ static int lerr(int rc, const char *what) {
 // update) -> iterEKF measurement update -> EKFmatsHandler -> iterMPC.
 // nslots > 0 (mpcekf_step_ex_obs): k_obs_traj first in every step, its rows one more output
 // field; nslots == 0 is mpcekf_step_ex: the same launches, allocations and copies as ever.
+// sum (mpcekf_step_summary): no trajectory leaves the call; the u, v, soc, phise, nexec rows
+// (and the record's obs slot) of step k go to row k % SUM_WIN of the context's window, which
+// k_summary folds into the record every SUM_WIN steps and after the last.  The per-step
+// temperatures are uploaded a window at a time, so no device buffer of the call grows with
+// nsteps.
 static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const mpcekf_traj *tr,
-                     const int32_t *slots, int32_t nslots, double *obs, int32_t outputs_on_device) {
+                     const int32_t *slots, int32_t nslots, double *obs, int32_t outputs_on_device,
+                     bool sum = false) {
   if (X) X->stage_zk = X->stage_lin = X->stage_v = X->stage_obs = false;  // the stage route's device hand-offs are stale
   int rc = need_init(X);
   if (rc) return rc;
   if (nsteps < 0) return fail(MPCEKF_E_ARG, "nsteps < 0");
+  if (sum && X->sum_slot >= 0) {  // checked by mpcekf_summary_begin
+    slots = &X->sum_slot;
+    nslots = 1;
+    obs = X->d_sum_obs;
+  }
   if (nslots < 0 || (nslots && (!slots || !obs))) return fail(MPCEKF_E_ARG, "step_ex_obs: nslots < 0 or a null slots / obs");
   for (int i = 0; i < nslots; ++i)
     if (slots[i] < 0 || slots[i] >= X->ko.nobs)
@@ -1241,7 +1262,20 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
            {nslots ? obs : nullptr, 8, (size_t)nslots, nullptr}};  // [nsteps][nslots][ncells]
   constexpr int NF = sizeof(f) / sizeof(f[0]);
   const double *dtc = tc_degC;  // [nsteps][n] device copy of the per-step temperatures
-  if (outputs_on_device) {
+  // sum: rows of the window instead of rows of a trajectory, for outputs and temperatures alike
+  const size_t ring = sum ? (size_t)SUM_WIN : 0;
+  const bool tc_windows = sum && tc_degC && (size_t)nsteps > ring;  // uploaded window by window
+  if (sum) {
+    f[14].host = nullptr;  // the obs rows stay on the device
+    for (int i = 0; i < 5; ++i) f[i].dev = X->d_sum_ring + (size_t)i * X->sum_row();
+    f[14].dev = nslots ? (char *)obs : nullptr;
+    if (tc_degC) {
+      const size_t rows = std::min((size_t)nsteps, ring);
+      if ((rc = X->tmp(rows * n * 8 + 256))) return rc;
+      if (!tc_windows) HIPCHK(hipMemcpyAsync(X->d_tmp, tc_degC, per * 8, hipMemcpyHostToDevice, X->stream));
+      dtc = X->d_tmp;
+    }
+  } else if (outputs_on_device) {
     for (F &e : f) e.dev = (char *)e.host;
   } else {
     size_t need = tc_degC ? ((per * 8 + 255) & ~(size_t)255) : 0;
@@ -1256,7 +1290,10 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
     }
   }
   auto row = [&](int i, int k) -> char * {  // step k's [ncells][width] block of field i
-    return f[i].dev ? f[i].dev + (size_t)k * n * f[i].width * f[i].esz : nullptr;
+    return f[i].dev ? f[i].dev + (ring ? (size_t)k % ring : (size_t)k) * n * f[i].width * f[i].esz : nullptr;
+  };
+  auto tc_row = [&](int k) -> const double * {  // step k's temperatures
+    return dtc ? dtc + (ring ? (size_t)k % ring : (size_t)k) * n : nullptr;
   };
   // iterMPC.m:53-60 diagnostics: k_cl_diag after the step from its linearisation records
   // and the uk_1 the step's iterMPC used
@@ -1308,7 +1345,9 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
   // k_plant(t + 1) overwrites the ring slot of step t + 1 - LAZY_H only after the join.  The
   // last step flushes every cell on the step's stream (timestamps 0, as before).  Under graph
   // capture the slices stay on the step's stream (same bits, no overlap).
-  const bool capturing = X->graph && !X->timing && nsteps > 0;
+  // (a summary call that uploads its temperatures window by window is not captured: the
+  // uploads read the caller's array)
+  const bool capturing = X->graph && !X->timing && nsteps > 0 && !tc_windows;
   const bool roll = X->flush_roll;
   const bool fork = roll && X->fstream && !capturing;
   // k_bounds beside Hildreth (bounds_side); under graph capture it stays on the step's stream
@@ -1324,24 +1363,23 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
       const bool sample = X->timing && ((k + 1) % X->timing_every == 0 || k == nsteps - 1);
       hipEvent_t *E = sample ? &X->ev[(size_t)k * NEV] : nullptr;
       if (E) HIPCHK(hipEventRecord(E[0], X->stream));
+      if (tc_windows && (size_t)k % ring == 0)  // the window's temperatures, after the last window's kernels
+        HIPCHK(hipMemcpyAsync(X->d_tmp, tc_degC + (size_t)k * n, std::min(ring, (size_t)(nsteps - k)) * n * 8,
+                              hipMemcpyHostToDevice, X->stream));
       if (diag) HIPCHK(hipMemcpyAsync(X->d_uk1p, X->s.uk_1, n * 8, hipMemcpyDeviceToDevice, X->stream));
       if (nslots) {  // the plant's observables of step t, before anything advances the plant
         KObsSel ok = osel;
         ok.out = (double *)row(14, k);
-        if ((rc = lerr(launch_obs_traj(X->r, X->s, X->ko, ok, t, dtc ? dtc + (size_t)k * n : nullptr, X->stream),
-                       "obs_traj")))
-          return rc;
+        if ((rc = lerr(launch_obs_traj(X->r, X->s, X->ko, ok, t, tc_row(k), X->stream), "obs_traj"))) return rc;
       }
-      if (!plant_in_cell &&
-          (rc = lerr(launch_plant(X->r, X->s, X->s.uk, X->s.vk, t, dtc ? dtc + (size_t)k * n : nullptr, X->stream),
-                     "plant")))
+      if (!plant_in_cell && (rc = lerr(launch_plant(X->r, X->s, X->s.uk, X->s.vk, t, tc_row(k), X->stream), "plant")))
         return rc;
       if (E) HIPCHK(hipEventRecord(E[1], X->stream));
       KIO io{};
       io.mode = MODE_FUSED;
       io.lazy_t = t;
       io.plant = plant_in_cell;
-      io.tc_in = plant_in_cell && dtc ? dtc + (size_t)k * n : nullptr;
+      io.tc_in = plant_in_cell ? tc_row(k) : nullptr;
       io.stamps = X->d_stamps;
       io.u = (double *)row(0, k);
       io.v = (double *)row(1, k);
@@ -1458,6 +1496,21 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
         if (timed) HIPCHK(hipEventRecord(E[6], X->stream));
         flushed[k] = timed;
       }
+      if (sum && ((size_t)t % ring == 0 || t == nsteps)) {  // the window is full, or the call ends
+        KSum q{};
+        q.rec = X->d_sum;
+        q.reach = X->d_sum_reach;
+        q.u = (const double *)f[0].dev;
+        q.v = (const double *)f[1].dev;
+        q.soc = (const double *)f[2].dev;
+        q.phise = (const double *)f[3].dev;
+        q.nexec = (const int *)f[4].dev;
+        q.obs = (const double *)f[14].dev;
+        q.n = X->n;
+        q.nrows = (int)((size_t)k % ring) + 1;
+        q.max_hild = X->cfg.max_hild;
+        if ((rc = lerr(launch_summary(q, X->stream), "summary"))) return rc;
+      }
     }
     return MPCEKF_OK;
   };
@@ -1471,6 +1524,11 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
     key.push_back((uintptr_t)nslots);
     key.push_back((uintptr_t)lim);  // set / clear change the launch sequence: graphs of the other one are not replayed
     for (int i = 0; i < nslots; ++i) key.push_back((uintptr_t)slots[i]);
+    // the summary state: its launches are part of the graph (the window's rows are already
+    // among the output rows above); the record last, 0 for a call that is no summary call --
+    // mpcekf_summary_end retires the graphs that name one
+    key.push_back((uintptr_t)(sum ? X->d_sum_reach : nullptr));
+    key.push_back((uintptr_t)(sum ? X->d_sum : nullptr));
     if ((rc = X->graph_launch(key, run_steps))) return rc;
   } else if ((rc = run_steps())) {
     return rc;
@@ -1631,6 +1689,90 @@ int mpcekf_clear_limits(mpcekf_ctx *X) {
   if (!X) return fail(MPCEKF_E_ARG, "clear_limits: null ctx");
   X->percell = false;  // the buffers stay: a graph captured per-cell names d_lim until the context goes
   X->h_lim.clear();
+  return MPCEKF_OK;
+}
+
+// ---- per-cell charge summary along the fused loop (mpcekf_summary.hip) ----
+static_assert(NSUM == MPCEKF_NSUM && SUM_WIN == MPCEKF_SUM_WIN && SUM_SEEN == MPCEKF_SUM_SEEN &&
+                  SUM_T_REACH == MPCEKF_SUM_T_REACH && SUM_U_MAX == MPCEKF_SUM_U_MAX && SUM_V_MIN == MPCEKF_SUM_V_MIN &&
+                  SUM_PHISE_MIN_STEP == MPCEKF_SUM_PHISE_MIN_STEP && SUM_PHISE_LAST == MPCEKF_SUM_PHISE_LAST &&
+                  SUM_U_SUM == MPCEKF_SUM_U_SUM && SUM_NSAT == MPCEKF_SUM_NSAT && SUM_OBS_MIN == MPCEKF_SUM_OBS_MIN &&
+                  SUM_OBS_MAX_STEP == MPCEKF_SUM_OBS_MAX_STEP,
+              "mpcekf_summary.hpp's rows are include/mpcekf.h's MPCEKF_SUM_*");
+
+int mpcekf_summary_begin(mpcekf_ctx *X, const double *soc_reach, int32_t obs_slot) {
+  if (!X) return fail(MPCEKF_E_ARG, "summary_begin: null ctx");
+  if (obs_slot < -1 || obs_slot >= X->ko.nobs)
+    return fail(MPCEKF_E_ARG, "summary_begin: obs_slot %d outside -1..%d", obs_slot, X->ko.nobs - 1);
+  HIPCHK(hipSetDevice(X->device));
+  const size_t n = std::max<size_t>((size_t)X->n, 1);
+  int rc;
+  // every buffer before anything is stored: a failed allocation leaves the context as it was
+  double *rec = X->d_sum, *reach = X->d_sum_reach, *ob = X->d_sum_obs;
+  char *ringp = X->d_sum_ring;
+  if (!rec && (rc = dalloc(&rec, n * NSUM))) return rc;
+  if (!reach && (rc = dalloc(&reach, n))) return rc;
+  if (!ringp && (rc = dalloc(&ringp, 5 * X->sum_row() + 256))) return rc;
+  if (obs_slot >= 0 && !ob && (rc = dalloc(&ob, (size_t)SUM_WIN * n))) return rc;
+  X->d_sum = rec;
+  X->d_sum_reach = reach;
+  X->d_sum_ring = ringp;
+  X->d_sum_obs = ob;
+  X->sum_slot = obs_slot;
+  if (soc_reach && X->n)
+    HIPCHK(hipMemcpyAsync(reach, soc_reach, (size_t)X->n * 8, hipMemcpyHostToDevice, X->stream));
+  if ((rc = lerr(launch_summary_reset(rec, reach, !soc_reach, X->n, X->stream), "summary_reset"))) return rc;
+  HIPCHK(hipStreamSynchronize(X->stream));
+  return MPCEKF_OK;
+}
+
+int mpcekf_step_summary(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC) {
+  if (!X) return fail(MPCEKF_E_ARG, "step_summary: null ctx");
+  if (!X->d_sum) return fail(MPCEKF_E_STATE, "step_summary: call mpcekf_summary_begin first");
+  return step_impl(X, nsteps, tc_degC, nullptr, nullptr, 0, nullptr, 0, true);
+}
+
+int mpcekf_get_summary(mpcekf_ctx *X, int32_t nfields, const int32_t *fields, double *values) {
+  if (!X) return fail(MPCEKF_E_ARG, "get_summary: null ctx");
+  if (nfields < 1 || nfields > MPCEKF_NSUM)
+    return fail(MPCEKF_E_ARG, "get_summary: nfields = %d outside 1..%d", nfields, (int)MPCEKF_NSUM);
+  if (!fields) return fail(MPCEKF_E_ARG, "get_summary: null fields");
+  if (!values) return fail(MPCEKF_E_ARG, "get_summary: null values");
+  unsigned seen = 0;
+  for (int i = 0; i < nfields; ++i) {
+    if (fields[i] < 0 || fields[i] >= MPCEKF_NSUM)
+      return fail(MPCEKF_E_ARG, "get_summary: fields[%d] = %d is not a MPCEKF_SUM_* id (0..%d)", i, fields[i],
+                  (int)MPCEKF_NSUM - 1);
+    if (seen >> fields[i] & 1) return fail(MPCEKF_E_ARG, "get_summary: fields: id %d given twice", fields[i]);
+    seen |= 1u << fields[i];
+  }
+  if (!X->d_sum) return fail(MPCEKF_E_STATE, "get_summary: call mpcekf_summary_begin first");
+  HIPCHK(hipSetDevice(X->device));
+  const size_t n = (size_t)X->n;
+  for (int i = 0; i < nfields && n; ++i)
+    HIPCHK(hipMemcpyAsync(values + (size_t)i * n, X->d_sum + (size_t)fields[i] * n, n * 8, hipMemcpyDeviceToHost,
+                          X->stream));
+  HIPCHK(hipStreamSynchronize(X->stream));
+  return MPCEKF_OK;
+}
+
+int mpcekf_summary_end(mpcekf_ctx *X) {
+  if (!X) return fail(MPCEKF_E_ARG, "summary_end: null ctx");
+  if (!X->d_sum) return MPCEKF_OK;
+  HIPCHK(hipSetDevice(X->device));
+  HIPCHK(hipStreamSynchronize(X->stream));
+  // the graphs captured from summary calls name the buffers freed below
+  for (size_t i = X->graphs.size(); i-- > 0;)
+    if (X->graphs[i].key.back()) {
+      (void)hipGraphExecDestroy(X->graphs[i].exec);
+      X->graphs.erase(X->graphs.begin() + (std::ptrdiff_t)i);
+    }
+  void *ptrs[] = {X->d_sum, X->d_sum_reach, X->d_sum_obs, X->d_sum_ring};
+  for (void *p : ptrs)
+    if (p) (void)hipFree(p);
+  X->d_sum = X->d_sum_reach = X->d_sum_obs = nullptr;
+  X->d_sum_ring = nullptr;
+  X->sum_slot = -1;
   return MPCEKF_OK;
 }
 

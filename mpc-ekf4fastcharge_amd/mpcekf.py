@@ -25,7 +25,7 @@ from . import _lib
 from ._lib import LIN_SIZE, MpcekfError, check, dptr, iptr
 from .rom import EL_TABLES, OBS_FIELDS, ROM, TF_CODE
 
-__all__ = ["Context", "DeviceBuffer", "hip_runtimes", "tc_grid", "make_config", "predMat", "constraintsMPC", "constraint_rows", "hildreth", "runMPC", "MpcekfError",
+__all__ = ["Context", "DeviceBuffer", "hip_runtimes", "tc_grid", "make_config", "predMat", "constraintsMPC", "constraint_rows", "hildreth", "runMPC", "run_summary", "MpcekfError",
            "LIN_SIZE"]
 
 LIN_FIELDS = dict(A=slice(0, 6), Csoc=slice(6, 12), Dsoc=12, Cv=slice(13, 19), Dv=19,
@@ -406,6 +406,66 @@ class Context:
         set_limits (mpcekf_clear_limits)."""
         check(self.L.mpcekf_clear_limits(self.h))
 
+    # -- per-cell charge summary along the fused loop ---------------------
+    SUMMARY_FIELDS = _lib.SUMMARY_FIELDS
+
+    def _summary_args(self, reach, obs):
+        """summary_begin's arguments -> (float64 [n] thresholds or None, int32 slot or -1).  obs:
+        a scalar field name of OB_step's obs, or (vector field, index).  KeyError for a field
+        that is not one, ValueError for a bad shape or index: before any library call."""
+        r = None
+        if reach is not None:
+            a = np.asarray(reach, dtype=np.float64)
+            if a.ndim > 1 or (a.ndim == 1 and a.shape[0] != self.n):
+                raise ValueError(f"summary_begin: reach must be a scalar or a length-{self.n} array, got shape {a.shape}")
+            r = np.ascontiguousarray(np.broadcast_to(a, (self.n,)))
+        slot = -1
+        if obs is not None:
+            name, idx = (obs, None) if isinstance(obs, str) else tuple(obs)
+            lay = self.rom.obs_layout()
+            if name not in lay:
+                raise KeyError(f"summary_begin: unknown obs field {name!r} (one of {OBS_FIELDS})")
+            m = lay[name].stop - lay[name].start
+            if name in self._OBS_SCALARS:
+                if idx not in (None, 0):
+                    raise ValueError(f"summary_begin: obs field {name!r} is a scalar: no index {idx!r}")
+                idx = 0
+            elif idx is None or int(idx) != idx or not 0 <= int(idx) < m:
+                raise ValueError(f"summary_begin: obs field {name!r} has {m} entries: give (field, index), 0-based")
+            slot = lay[name].start + int(idx)
+        return r, slot
+
+    def summary_begin(self, reach=None, obs=None):
+        """Start (or reset) the per-cell charge summary (mpcekf_summary_begin).  ``reach``: the
+        SOC whose first crossing T_REACH records, a scalar or [ncells], in the unit of step()'s
+        ``soc`` (zk(end): a fraction 0..1), None for none.  ``obs``: one slot of the plant's
+        observables to track beside the EKF's outputs, e.g. "negPhise0" (the plant's own
+        plating margin) or ("Thetae", 1); None for none."""
+        r, slot = self._summary_args(reach, obs)   # KeyError / ValueError before any library call
+        check(self.L.mpcekf_summary_begin(self.h, dptr(r), int(slot)))
+
+    def step_summary(self, nsteps, tc=None):
+        """nsteps fused steps (step()'s, tc as there) accumulated into the summary record; no
+        trajectory is returned and none is kept (mpcekf_step_summary)."""
+        tcs = None if tc is None else tc_grid(tc, nsteps, self.n)
+        check(self.L.mpcekf_step_summary(self.h, int(nsteps), tcs.ctypes.data_as(C.c_void_p) if tcs is not None else None))
+
+    def get_summary(self, fields=None):
+        """{name: [ncells] float64} of the summary record (mpcekf_get_summary): ``fields`` names
+        of SUMMARY_FIELDS (default all).  Step indices and counts are exact integers."""
+        names = self.SUMMARY_FIELDS if fields is None else (fields,) if isinstance(fields, str) else tuple(fields)
+        for k in names:
+            if k not in self.SUMMARY_FIELDS:
+                raise KeyError(f"get_summary: unknown field {k!r} (one of {self.SUMMARY_FIELDS})")
+        ids = np.asarray([self.SUMMARY_FIELDS.index(k) for k in names], dtype=np.int32)
+        vals = np.empty((ids.size, self.n))
+        check(self.L.mpcekf_get_summary(self.h, int(ids.size), iptr(ids), dptr(vals)))
+        return {k: vals[i] for i, k in enumerate(names)}
+
+    def summary_end(self):
+        """Free the summary record and its window (mpcekf_summary_end)."""
+        check(self.L.mpcekf_summary_end(self.h))
+
     def set_timing(self, enable=True):
         """enable: True/1 = every step; N > 1 = sample every N-th step (less perturbation)."""
         check(self.L.mpcekf_set_timing(self.h, int(enable)))
@@ -751,6 +811,34 @@ def runMPC(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=None,
         if limits:
             ctx.set_limits(**limits)
         out = ctx.step(nsteps, tc=tc_traj, obs=obs)
+        out["status"] = ctx.get_state()["status"]
+        return out
+
+
+def run_summary(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=None, limits=None, reach=None,
+                obs=None, chunk=None):
+    """runMPC.m:72-112 for a batch of cells, read out as the per-cell charge summary instead of
+    trajectories: {field: [ncells]} of Context.get_summary plus "status".  limits: as runMPC's
+    (a protocol sweep); reach, obs: Context.summary_begin's; tc_traj [nsteps, ncells] (degC): a
+    temperature profile; chunk: steps per step_summary call (default all at once; with tc_traj
+    a chunk bounds the host array each call converts).  Neither host nor device memory grows
+    with nsteps."""
+    SOC0 = np.atleast_1d(np.asarray(SOC0, dtype=np.float64))
+    n = ncells or SOC0.shape[0]
+    nsteps = int(nsteps)
+    chunk = nsteps if not chunk else int(chunk)
+    if chunk < 0 or (chunk == 0 and nsteps):
+        raise ValueError(f"run_summary: chunk = {chunk}")
+    tcs = None if tc_traj is None else tc_grid(tc_traj, nsteps, n)
+    with Context(rom, n, cfg, device) as ctx:
+        ctx.init_cells(SOC0, TC)
+        if limits:
+            ctx.set_limits(**limits)
+        ctx.summary_begin(reach=reach, obs=obs)
+        for k in range(0, nsteps, max(chunk, 1)):
+            m = min(chunk, nsteps - k)
+            ctx.step_summary(m, tc=None if tcs is None else tcs[k:k + m])
+        out = ctx.get_summary()
         out["status"] = ctx.get_state()["status"]
         return out
 
