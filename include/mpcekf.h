@@ -509,6 +509,71 @@ int mpcekf_get_summary(mpcekf_ctx *ctx, int32_t nfields, const int32_t *fields, 
  * no-op without a begin. */
 int mpcekf_summary_end(mpcekf_ctx *ctx);
 
+/* ---- per-cell lumped thermal model along the fused loop (not part of the reference interface) ----
+ * runMPC.m:85-92 passes a temperature TC it is given.  With a model, the cell temperature is a
+ * state: after every fused step the library advances it on the device from the current the
+ * step applied and the voltage the plant answered with, and the next step (or the next stage
+ * call) reads it -- a charge with self-heating at the fused loop's speed.  Per cell, after
+ * fused step t (Ts = rom.Ts), every line one or more separately rounded fp64 operations in
+ * exactly this order (no contraction into fused multiply-adds, IEEE division):
+ *   i    = the current OB_step applied in step t: MPCEKF_S_UK as it stood before the step
+ *          (= u_store(t-1))
+ *   v    = voltage_store(t): the plant's Vcell of step t (MPCEKF_S_VK); NaN for a cell that
+ *          has MPCEKF_ST_ERROR after the step (its outputs are NaN from its failing step on)
+ *   z    = (SOCnAvg - theta0n) / (theta100n - theta0n)      cellState.SOCnAvg after the step
+ *          (MPCEKF_S_SOCNAVG); OB_step.m:228's cellSOC, the obs record's cellSOC of step t+1
+ *   zc   = z > 0 ? z : 0;   zc = zc < 1 ? zc : 1            (a NaN z gives 0)
+ *   s    = zc * (double)(nocv - 1);   j = min((int)s, nocv - 2);   f = s - (double)j
+ *   U    = ocv[j] + f * (ocv[j+1] - ocv[j])                 open-circuit voltage over z in [0, 1]
+ *   q    = i * (U - v)                                      W; charging: i < 0, v > U, q > 0
+ *   loss = (T - Tamb) / Rth                                 Rth = +inf: adiabatic (loss = 0)
+ *   Tn   = T + ((q - loss) * Ts) / Cth
+ *   T   <- Tn if isfinite(Tn) and Tn <= 100 (the rule every temperature argument passes);
+ *          otherwise T is held and NHELD counts the step
+ * T is the context's cell temperature (degC): what mpcekf_init_cells or a stage call's
+ * temperature argument set.  Stage calls do not advance the model; their temperature argument
+ * still sets T.  Entropic (reversible) heat is not modelled.
+ * The record, every value a double, counts and step indices exact integers:
+ *   T            the cell temperature now
+ *   T_MAX, T_MAX_STEP, T_MIN   over the temperatures the steps used (T before the update),
+ *                replaced only on a strict > / <; T_MAX_STEP counts the model's steps from 1
+ *                since begin, across calls.  NaN / 0 before the first step
+ *   HEAT_SUM     the finite q values added in step order, plain fp64 additions from +0
+ *                (energy in J = HEAT_SUM * Ts)
+ *   STEPS        steps whose T was advanced
+ *   NHELD        steps whose T was held */
+enum { MPCEKF_TH_CTH = 0 /* J/K */, MPCEKF_TH_RTH /* K/W, +inf allowed */, MPCEKF_TH_TAMB /* degC */, MPCEKF_NTH };
+enum {
+  MPCEKF_THR_T = 0, MPCEKF_THR_T_MAX, MPCEKF_THR_T_MAX_STEP, MPCEKF_THR_T_MIN, MPCEKF_THR_HEAT_SUM,
+  MPCEKF_THR_STEPS, MPCEKF_THR_NHELD, MPCEKF_NTHR
+};
+/* Gives the context a model: params [MPCEKF_NTH][ncells], the open-circuit voltage table ocv
+ * [nocv] on a uniform grid of cell SOC 0..1, t0_degC [ncells] the temperature to start from or
+ * NULL to keep the context's.  Allocates the model's device buffers (first call) and resets the
+ * record; a second begin replaces parameters and table and resets the record.  May be called
+ * before mpcekf_init_cells, which sets T as ever and does not touch the record.  From then on
+ * every fused call (mpcekf_step, _step_ex, _step_ex_obs, _step_summary, _step_ex_thermal)
+ * advances the model once per step and takes tc_degC == NULL only: with a tc_degC it returns
+ * MPCEKF_E_ARG and leaves the context and the record as they were.  The model's kernel is not
+ * one of mpcekf_set_timing's five slots.
+ * MPCEKF_E_ARG (nothing changed): a NULL ctx, params or ocv; a Cth that is not finite and > 0;
+ * an Rth that is not > 0 (+inf allowed); a Tamb or t0 that is not finite and <= 100; nocv < 2;
+ * a non-finite ocv entry. */
+int mpcekf_thermal_begin(mpcekf_ctx *ctx, const double *params, int32_t nocv, const double *ocv,
+                         const double *t0_degC);
+/* values [nfields][ncells]: row i = field fields[i] (distinct MPCEKF_THR_* ids).
+ * MPCEKF_E_STATE without a begin; MPCEKF_E_ARG: a NULL pointer, nfields outside
+ * 1..MPCEKF_NTHR, an unknown or repeated id. */
+int mpcekf_thermal_get(mpcekf_ctx *ctx, int32_t nfields, const int32_t *fields, double *values);
+/* Frees the model; T stays what it is and the context then behaves as one that never began
+ * (tc_degC == NULL keeps T).  A no-op without a begin. */
+int mpcekf_thermal_end(mpcekf_ctx *ctx);
+/* mpcekf_step_ex_obs on a thermal context plus the model's rows, [nsteps][ncells] (host, or
+ * device when outputs_on_device != 0), either may be NULL: temp[t] the temperature step t
+ * used, heat[t] its q (NaN for a cell in error).  MPCEKF_E_STATE without a begin. */
+int mpcekf_step_ex_thermal(mpcekf_ctx *ctx, int32_t nsteps, const mpcekf_traj *traj, const int32_t *slots,
+                           int32_t nslots, double *obs, double *temp, double *heat, int32_t outputs_on_device);
+
 /* ---- device memory (not part of the reference interface) ----
  * Device buffers for outputs_on_device calls, allocated by the library's own HIP
  * runtime so a host process never holds a second one (a framework's bundled

@@ -60,6 +60,19 @@
  *                       struct of ncells x 1 column vectors, one per MPCEKF_SUM_* field
  *                       (seen, steps, err_step, t_reach, u_min, ...; include/mpcekf.h)
  *                       mpcekf_mex('summaryend', h)                    mpcekf_summary_end
+ *                       mpcekf_mex('thermalbegin', h, params, ocv, t0) mpcekf_thermal_begin
+ *                       params: ncells x 3, columns Cth (J/K), Rth (K/W, Inf: adiabatic), Tamb
+ *                       (degC); ocv: the open-circuit voltage on a uniform cell-SOC grid 0..1
+ *                       (2 entries or more); t0: [] (keep) or ncells temperatures (degC).  From
+ *                       then on every 'step' / 'stepobs' / 'stepsummary' / 'stepthermal' advances
+ *                       each cell's temperature after every step and takes no tc
+ *   s                 = mpcekf_mex('thermalget', h)                    mpcekf_thermal_get
+ *                       struct of ncells x 1 column vectors: T, T_max, T_max_step, T_min,
+ *                       heat_sum, steps, nheld (MPCEKF_THR_*; include/mpcekf.h)
+ *                       mpcekf_mex('thermalend', h)                    mpcekf_thermal_end
+ *   [u,v,soc,phise,nexec,temp,heat] = mpcekf_mex('stepthermal', h, nsteps)   mpcekf_step_ex_thermal
+ *                       'step' on a context with a thermal model, plus the temperature each
+ *                       step used and the heat it generated (W), ncells x nsteps
  * Per-cell vectors are 1 x ncells or ncells x 1; zk / zbk are (nz+2) x ncells, xm / xg
  * 4 x ncells (xm: 0-based model index t*nZ+z), lin 35 x ncells -- MATLAB's column-major
  * k x ncells is the library's cell-major [ncells][k], so no copy is made for them.
@@ -374,7 +387,8 @@ static void gateway(mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
   static const char *const with_handle[] = {"destroy", "init", "step", "plant", "ekf", "linearize", "mpc",
                                             "graph", "mpcdiag", "get_state", "set_state", "scalars", "linfields",
                                             "plantobs", "obsslots", "obslayout", "stepobs", "setlimits", "getlimits",
-                                            "clearlimits", "summarybegin", "stepsummary", "getsummary", "summaryend"};
+                                            "clearlimits", "summarybegin", "stepsummary", "getsummary", "summaryend",
+                                            "thermalbegin", "thermalget", "thermalend", "stepthermal"};
   int known = 0;
   for (size_t i = 0; i < sizeof with_handle / sizeof *with_handle; ++i) known = known || !strcmp(cmd, with_handle[i]);
   if (!known) mexErrMsgIdAndTxt("mpcekf:arg", "unknown command %s", cmd);
@@ -445,6 +459,31 @@ static void gateway(mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
     if (!(nsd >= 0 && nsd <= 2147483647.0) || nsd != (double)(int32_t)nsd)
       mexErrMsgIdAndTxt("mpcekf:arg", "nsteps: expected a non-negative integer");
     sumsteps = (int32_t)nsd;
+  }
+  /* the thermal commands likewise: output count, argument classes, a table of 2 entries or
+     more, an nsteps that is no non-negative integer */
+  const int thbegin = !strcmp(cmd, "thermalbegin"), stepth = !strcmp(cmd, "stepthermal");
+  int32_t thsteps = 0;
+  if ((thbegin || !strcmp(cmd, "thermalend")) && g_nlhs > 0) mexErrMsgIdAndTxt("mpcekf:arg", "%s: no output", cmd);
+  if (!strcmp(cmd, "thermalget") && g_nlhs > 1) mexErrMsgIdAndTxt("mpcekf:arg", "thermalget: at most 1 output");
+  if (stepth && g_nlhs > 7)
+    mexErrMsgIdAndTxt("mpcekf:arg", "stepthermal: at most 7 outputs [u, v, soc, phise, nexec, temp, heat]");
+  if (thbegin) {
+    need(nrhs, 4, "'thermalbegin', h, params, ocv[, t0]");
+    if (!mxIsDouble(prhs[2]) || mxIsComplex(prhs[2]))
+      mexErrMsgIdAndTxt("mpcekf:arg", "thermalbegin: params: expected a real double ncells x %d array", (int)MPCEKF_NTH);
+    if (!mxIsDouble(prhs[3]) || mxIsComplex(prhs[3]) || mxGetNumberOfElements(prhs[3]) < 2 ||
+        mxGetNumberOfElements(prhs[3]) > 2147483647.0)
+      mexErrMsgIdAndTxt("mpcekf:arg", "thermalbegin: ocv: expected 2 or more real doubles");
+    if (nrhs > 4 && !mxIsEmpty(prhs[4]) && (!mxIsDouble(prhs[4]) || mxIsComplex(prhs[4])))
+      mexErrMsgIdAndTxt("mpcekf:arg", "thermalbegin: t0: expected [] or ncells real doubles");
+  }
+  if (stepth) {
+    need(nrhs, 3, "'stepthermal', h, nsteps");
+    const double nsd = scalar(prhs[2], "nsteps");
+    if (!(nsd >= 0 && nsd <= 2147483647.0) || nsd != (double)(int32_t)nsd)
+      mexErrMsgIdAndTxt("mpcekf:arg", "nsteps: expected a non-negative integer");
+    thsteps = (int32_t)nsd;
   }
   mpcekf_ctx *h = handle(prhs[1]);
   int64_t n = 0;
@@ -630,6 +669,33 @@ static void gateway(mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
     mxFree(vals);
   } else if (!strcmp(cmd, "summaryend")) {
     chk(mpcekf_summary_end(h));
+  } else if (thbegin) {
+    /* ncells x 3 column-major is the library's [MPCEKF_NTH][ncells] as it stands */
+    chk(mpcekf_thermal_begin(h, dvec(prhs[2], nc * MPCEKF_NTH, "thermalbegin: params (ncells x 3)"),
+                             (int32_t)mxGetNumberOfElements(prhs[3]), mxGetDoubles(prhs[3]),
+                             nrhs > 4 ? opt_vec(prhs[4], nc, "thermalbegin: t0 (ncells)") : NULL));
+  } else if (!strcmp(cmd, "thermalget")) {
+    static const char *const th_names[MPCEKF_NTHR] = {"T", "T_max", "T_max_step", "T_min", "heat_sum", "steps", "nheld"};
+    int32_t ids[MPCEKF_NTHR];
+    double *vals = (double *)mxMalloc((size_t)MPCEKF_NTHR * nc * sizeof(double) + 8);
+    for (int f = 0; f < MPCEKF_NTHR; ++f) ids[f] = f;
+    chk(mpcekf_thermal_get(h, MPCEKF_NTHR, ids, vals));
+    plhs[0] = mxCreateStructMatrix(1, 1, MPCEKF_NTHR, (const char **)th_names);
+    for (int f = 0; f < MPCEKF_NTHR; ++f) {
+      mxArray *a = dmat(nc, 1);
+      if (nc) memcpy(mxGetDoubles(a), vals + (size_t)f * nc, nc * sizeof(double));
+      mxSetField(plhs[0], 0, th_names[f], a);
+    }
+    mxFree(vals);
+  } else if (!strcmp(cmd, "thermalend")) {
+    chk(mpcekf_thermal_end(h));
+  } else if (stepth) {
+    for (int i = 0; i < 7; ++i) plhs[i] = i == 4 ? imat(nc, (size_t)thsteps) : dmat(nc, (size_t)thsteps);
+    mpcekf_traj tr;
+    memset(&tr, 0, sizeof tr);
+    tr.u = mxGetDoubles(plhs[0]); tr.v = mxGetDoubles(plhs[1]); tr.soc = mxGetDoubles(plhs[2]);
+    tr.phise = mxGetDoubles(plhs[3]); tr.nexec = (int32_t *)mxGetData(plhs[4]);
+    chk(mpcekf_step_ex_thermal(h, thsteps, &tr, NULL, 0, NULL, mxGetDoubles(plhs[5]), mxGetDoubles(plhs[6]), 0));
   } else if (!strcmp(cmd, "mpcdiag")) {
     need(nrhs, 3, "'mpcdiag', h, lin[, uk_1]");
     plhs[0] = mxCreateDoubleMatrix(7, (mwSize)nc, mxCOMPLEX);  /* interleaved (re, im): [ncells][7][2] */

@@ -30,6 +30,9 @@ SUMMARY_FIELDS = ("seen", "steps", "err_step", "t_reach", "u_min", "u_min_step",
                   "v_min", "phise_min", "phise_min_step", "u_last", "v_last", "soc_last", "phise_last", "u_sum",
                   "nexec_sum", "nexec_max", "nsat", "obs_min", "obs_min_step", "obs_max", "obs_max_step")
 SUM_WIN = 64     # MPCEKF_SUM_WIN
+# MPCEKF_TH_* / MPCEKF_THR_*: the lumped thermal model's parameters and record (mpcekf_thermal_begin / _get)
+THERMAL_PARAMS = ("Cth", "Rth", "Tamb")
+THERMAL_FIELDS = ("T", "T_max", "T_max_step", "T_min", "heat_sum", "steps", "nheld")
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
@@ -92,6 +95,7 @@ EXPORTS = [
     "mpcekf_obs_layout", "mpcekf_plant_step_obs", "mpcekf_plant_obs_slots", "mpcekf_step_ex_obs",
     "mpcekf_set_limits", "mpcekf_get_limits", "mpcekf_clear_limits",
     "mpcekf_summary_begin", "mpcekf_step_summary", "mpcekf_get_summary", "mpcekf_summary_end",
+    "mpcekf_thermal_begin", "mpcekf_thermal_get", "mpcekf_thermal_end", "mpcekf_step_ex_thermal",
     # the _async stage twins (include/mpcekf.h)
     "mpcekf_plant_step_async", "mpcekf_ekf_step_async", "mpcekf_linearize_async", "mpcekf_lin_fields_async",
     "mpcekf_mpc_step_async", "mpcekf_mpc_step_ex_async", "mpcekf_mpc_diag_async", "mpcekf_get_scalars_async",
@@ -165,6 +169,10 @@ def load():
     L.mpcekf_step_summary.argtypes = [vp, C.c_int32, vp]
     L.mpcekf_get_summary.argtypes = [vp, C.c_int32, _ip, _dp]
     L.mpcekf_summary_end.argtypes = [vp]
+    L.mpcekf_thermal_begin.argtypes = [vp, _dp, C.c_int32, _dp, _dp]
+    L.mpcekf_thermal_get.argtypes = [vp, C.c_int32, _ip, _dp]
+    L.mpcekf_thermal_end.argtypes = [vp]
+    L.mpcekf_step_ex_thermal.argtypes = [vp, C.c_int32, C.POINTER(Traj), _ip, C.c_int32, vp, vp, vp, C.c_int32]
     for nm in ("plant_step", "ekf_step", "linearize", "lin_fields", "mpc_step", "mpc_step_ex", "mpc_diag",
                "get_scalars", "plant_step_obs", "plant_obs_slots"):   # the _async twins take the synchronous call's arguments
         getattr(L, f"mpcekf_{nm}_async").argtypes = getattr(L, f"mpcekf_{nm}").argtypes

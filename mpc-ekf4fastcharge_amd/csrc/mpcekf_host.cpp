@@ -26,6 +26,7 @@
 #include "mpcekf_eig.hpp"
 #include "mpcekf_kernels.hpp"
 #include "mpcekf_summary.hpp"
+#include "mpcekf_thermal.hpp"
 
 using namespace mk;
 namespace mk {
@@ -231,6 +232,11 @@ struct mpcekf_ctx {
   char *d_sum_ring = nullptr;
   int32_t sum_slot = -1;
   size_t sum_row() const { return (((size_t)SUM_WIN * (size_t)n * 8) + 255) & ~(size_t)255; }  // one field's rows
+  // mpcekf_thermal_begin .. _end: the parameters [NTH][n], the record [NTHR][n], the current
+  // the running step applied [n] and the OCV table [th_nocv].  d_th != nullptr: every fused
+  // step ends with k_thermal.
+  double *d_th = nullptr, *d_th_par = nullptr, *d_th_i = nullptr, *d_th_ocv = nullptr;
+  int32_t th_nocv = 0;
   double *d_uk1p = nullptr;                      // [n] uk_1 before the step (poles / sv)
   int flush_period = LAZY_H;      // steps between all-model flushes (<= LAZY_H)
   // rolling flush (MPCEKF_FLUSH_ROLL=1, off by default): step t flushes the cell slice
@@ -1105,7 +1111,7 @@ int mpcekf_ctx_destroy(mpcekf_ctx *X) {
                   X->w.prob, X->w.X, X->w.R, X->w.K, X->w.hii, X->w.it, X->w.smin, X->d_lin, X->d_zsoc, X->d_mb, X->d_uk1p,
                   X->w.q, X->w.list, X->w.hist, X->d_poly, X->d_szk, X->d_sxg, X->d_sxm, X->d_slin, X->d_sv, X->d_zslot,
                   X->d_obs_blob, X->d_obs, X->d_obs_plan, X->d_lim, X->d_sum, X->d_sum_reach, X->d_sum_obs,
-                  X->d_sum_ring};
+                  X->d_sum_ring, X->d_th, X->d_th_par, X->d_th_i, X->d_th_ocv};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   for (auto &g : X->graphs) (void)hipGraphExecDestroy(g.exec);
@@ -1217,13 +1223,20 @@ static int lerr(int rc, const char *what) {
 // k_summary folds into the record every SUM_WIN steps and after the last.  The per-step
 // temperatures are uploaded a window at a time, so no device buffer of the call grows with
 // nsteps.
+// A thermal context (mpcekf_thermal_begin): k_thermal last in every step advances s.Tc, which
+// the next step's kernels read (tc_in stays null); temp / heat (mpcekf_step_ex_thermal) are two
+// more [nsteps][ncells] output fields, written by k_thermal.
 static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const mpcekf_traj *tr,
                      const int32_t *slots, int32_t nslots, double *obs, int32_t outputs_on_device,
-                     bool sum = false) {
+                     bool sum = false, double *temp = nullptr, double *heat = nullptr) {
+  // a thermal context owns the temperature: refused before anything of the context changes
+  if (X && X->d_th && tc_degC)
+    return fail(MPCEKF_E_ARG, "step: tc_degC on a thermal context (mpcekf_thermal_begin): the model sets the temperature");
   if (X) X->stage_zk = X->stage_lin = X->stage_v = X->stage_obs = false;  // the stage route's device hand-offs are stale
   int rc = need_init(X);
   if (rc) return rc;
   if (nsteps < 0) return fail(MPCEKF_E_ARG, "nsteps < 0");
+  const bool thermal = X->d_th != nullptr;
   if (sum && X->sum_slot >= 0) {  // checked by mpcekf_summary_begin
     slots = &X->sum_slot;
     nslots = 1;
@@ -1259,7 +1272,8 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
            {tr->zk, 8, nzz, nullptr},    {tr->zbk, 8, nzz, nullptr},  {tr->J_unc, 8, 1, nullptr},
            {tr->J_fin, 8, 1, nullptr},   {tr->norm_du, 8, 1, nullptr}, {tr->nviol, 4, 1, nullptr},
            {tr->poles, 8, 2 * NA, nullptr}, {tr->sv, 8, NA, nullptr},
-           {nslots ? obs : nullptr, 8, (size_t)nslots, nullptr}};  // [nsteps][nslots][ncells]
+           {nslots ? obs : nullptr, 8, (size_t)nslots, nullptr},  // [nsteps][nslots][ncells]
+           {temp, 8, 1, nullptr},        {heat, 8, 1, nullptr}};  // k_thermal's rows (a thermal context's only)
   constexpr int NF = sizeof(f) / sizeof(f[0]);
   const double *dtc = tc_degC;  // [nsteps][n] device copy of the per-step temperatures
   // sum: rows of the window instead of rows of a trajectory, for outputs and temperatures alike
@@ -1367,6 +1381,9 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
         HIPCHK(hipMemcpyAsync(X->d_tmp, tc_degC + (size_t)k * n, std::min(ring, (size_t)(nsteps - k)) * n * 8,
                               hipMemcpyHostToDevice, X->stream));
       if (diag) HIPCHK(hipMemcpyAsync(X->d_uk1p, X->s.uk_1, n * 8, hipMemcpyDeviceToDevice, X->stream));
+      // the current the call's first step applies, before a kernel overwrites s.uk; k_thermal
+      // carries it from step to step (mpcekf_thermal.hip)
+      if (thermal && k == 0) HIPCHK(hipMemcpyAsync(X->d_th_i, X->s.uk, n * 8, hipMemcpyDeviceToDevice, X->stream));
       if (nslots) {  // the plant's observables of step t, before anything advances the plant
         KObsSel ok = osel;
         ok.out = (double *)row(14, k);
@@ -1511,6 +1528,26 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
         q.max_hild = X->cfg.max_hild;
         if ((rc = lerr(launch_summary(q, X->stream), "summary"))) return rc;
       }
+      if (thermal) {  // last: after Hildreth stored the next command and the flush
+        KTherm q{};
+        q.Tc = X->s.Tc;
+        q.vk = X->s.vk;
+        q.SOCn = X->s.SOCn;
+        q.status = X->s.status;
+        q.uk = X->s.uk;
+        q.iapp = X->d_th_i;
+        q.par = X->d_th_par;
+        q.ocv = X->d_th_ocv;
+        q.rec = X->d_th;
+        q.temp = (double *)row(15, k);
+        q.heat = (double *)row(16, k);
+        q.n = X->n;
+        q.nocv = X->th_nocv;
+        q.th0n = X->r.th0n;
+        q.th100n = X->r.th100n;
+        q.Ts = X->r.Ts;
+        if ((rc = lerr(launch_thermal(q, X->stream), "thermal"))) return rc;
+      }
     }
     return MPCEKF_OK;
   };
@@ -1524,6 +1561,11 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
     key.push_back((uintptr_t)nslots);
     key.push_back((uintptr_t)lim);  // set / clear change the launch sequence: graphs of the other one are not replayed
     for (int i = 0; i < nslots; ++i) key.push_back((uintptr_t)slots[i]);
+    // the thermal state (its temp / heat rows are among the output rows above): third from the
+    // end, 0 on a context without a model -- mpcekf_thermal_end retires the graphs that name one
+    key.push_back((uintptr_t)X->d_th_ocv);
+    key.push_back((uintptr_t)X->th_nocv);
+    key.push_back((uintptr_t)X->d_th);
     // the summary state: its launches are part of the graph (the window's rows are already
     // among the output rows above); the record last, 0 for a call that is no summary call --
     // mpcekf_summary_end retires the graphs that name one
@@ -1774,6 +1816,124 @@ int mpcekf_summary_end(mpcekf_ctx *X) {
   X->d_sum_ring = nullptr;
   X->sum_slot = -1;
   return MPCEKF_OK;
+}
+
+// ---- per-cell lumped thermal model along the fused loop (mpcekf_thermal.hip) ----
+static_assert(NTH == MPCEKF_NTH && TH_CTH == MPCEKF_TH_CTH && TH_RTH == MPCEKF_TH_RTH && TH_TAMB == MPCEKF_TH_TAMB &&
+                  NTHR == MPCEKF_NTHR && THR_T == MPCEKF_THR_T && THR_T_MAX == MPCEKF_THR_T_MAX &&
+                  THR_T_MAX_STEP == MPCEKF_THR_T_MAX_STEP && THR_T_MIN == MPCEKF_THR_T_MIN &&
+                  THR_HEAT_SUM == MPCEKF_THR_HEAT_SUM && THR_STEPS == MPCEKF_THR_STEPS &&
+                  THR_NHELD == MPCEKF_THR_NHELD,
+              "mpcekf_thermal.hpp's rows are include/mpcekf.h's MPCEKF_TH_* / MPCEKF_THR_*");
+
+// the graphs captured on a thermal context launch k_thermal on the model's buffers: retired
+// before any of those buffers is freed
+static void retire_thermal_graphs(mpcekf_ctx *X) {
+  for (size_t i = X->graphs.size(); i-- > 0;)
+    if (X->graphs[i].key[X->graphs[i].key.size() - 3]) {
+      (void)hipGraphExecDestroy(X->graphs[i].exec);
+      X->graphs.erase(X->graphs.begin() + (std::ptrdiff_t)i);
+    }
+}
+
+int mpcekf_thermal_begin(mpcekf_ctx *X, const double *params, int32_t nocv, const double *ocv, const double *t0_degC) {
+  if (!X) return fail(MPCEKF_E_ARG, "thermal_begin: null ctx");
+  if (!params) return fail(MPCEKF_E_ARG, "thermal_begin: null params");
+  if (!ocv) return fail(MPCEKF_E_ARG, "thermal_begin: null ocv");
+  if (nocv < 2) return fail(MPCEKF_E_ARG, "thermal_begin: nocv = %d: the table needs 2 entries or more", nocv);
+  for (int i = 0; i < nocv; ++i)
+    if (!std::isfinite(ocv[i])) return fail(MPCEKF_E_ARG, "thermal_begin: ocv[%d] = %g is not finite", i, ocv[i]);
+  const size_t nc = (size_t)X->n;
+  for (size_t c = 0; c < nc; ++c) {
+    const double Cth = params[MPCEKF_TH_CTH * nc + c], Rth = params[MPCEKF_TH_RTH * nc + c];
+    if (!std::isfinite(Cth) || !(Cth > 0))
+      return fail(MPCEKF_E_ARG, "thermal_begin: Cth[%zu] = %g: must be finite and > 0 (J/K)", c, Cth);
+    if (!(Rth > 0)) return fail(MPCEKF_E_ARG, "thermal_begin: Rth[%zu] = %g: must be > 0 (K/W; +inf: adiabatic)", c, Rth);
+  }
+  // check_tc's rule, with the argument named
+  for (size_t c = 0; c < nc; ++c) {
+    const double Tamb = params[MPCEKF_TH_TAMB * nc + c];
+    if (!(Tamb <= 100) || !std::isfinite(Tamb))
+      return fail(MPCEKF_E_ARG, "thermal_begin: Tamb[%zu] = %g: must be finite and in degC (iterEKF.m:62)", c, Tamb);
+    if (t0_degC && (!(t0_degC[c] <= 100) || !std::isfinite(t0_degC[c])))
+      return fail(MPCEKF_E_ARG, "thermal_begin: t0[%zu] = %g: must be finite and in degC (iterEKF.m:62)", c, t0_degC[c]);
+  }
+  int rc;
+  HIPCHK(hipSetDevice(X->device));
+  const size_t n = std::max<size_t>(nc, 1);
+  // every buffer before anything is stored: a failed allocation leaves the context as it was
+  double *rec = X->d_th, *par = X->d_th_par, *ia = X->d_th_i, *tab = X->d_th_ocv;
+  const bool new_tab = !tab || X->th_nocv != nocv;
+  if (!rec && (rc = dalloc(&rec, n * NTHR))) return rc;
+  if (!par && (rc = dalloc(&par, n * NTH))) return rc;
+  if (!ia && (rc = dalloc(&ia, n))) return rc;
+  if (new_tab) {
+    double *t = nullptr;
+    if ((rc = dalloc(&t, (size_t)nocv))) return rc;
+    if (tab) {  // no launch in flight reads the old table, and no graph names it any more
+      HIPCHK(hipStreamSynchronize(X->stream));
+      retire_thermal_graphs(X);
+      (void)hipFree(tab);
+    }
+    tab = t;
+  }
+  X->d_th = rec;
+  X->d_th_par = par;
+  X->d_th_i = ia;
+  X->d_th_ocv = tab;
+  X->th_nocv = nocv;
+  if (nc) HIPCHK(hipMemcpyAsync(par, params, nc * NTH * 8, hipMemcpyHostToDevice, X->stream));
+  HIPCHK(hipMemcpyAsync(tab, ocv, (size_t)nocv * 8, hipMemcpyHostToDevice, X->stream));
+  if (nc && t0_degC) HIPCHK(hipMemcpyAsync(X->s.Tc, t0_degC, nc * 8, hipMemcpyHostToDevice, X->stream));
+  if ((rc = lerr(launch_thermal_reset(rec, X->n, X->stream), "thermal_reset"))) return rc;
+  HIPCHK(hipStreamSynchronize(X->stream));
+  return MPCEKF_OK;
+}
+
+int mpcekf_thermal_get(mpcekf_ctx *X, int32_t nfields, const int32_t *fields, double *values) {
+  if (!X) return fail(MPCEKF_E_ARG, "thermal_get: null ctx");
+  if (nfields < 1 || nfields > MPCEKF_NTHR)
+    return fail(MPCEKF_E_ARG, "thermal_get: nfields = %d outside 1..%d", nfields, (int)MPCEKF_NTHR);
+  if (!fields) return fail(MPCEKF_E_ARG, "thermal_get: null fields");
+  if (!values) return fail(MPCEKF_E_ARG, "thermal_get: null values");
+  unsigned seen = 0;
+  for (int i = 0; i < nfields; ++i) {
+    if (fields[i] < 0 || fields[i] >= MPCEKF_NTHR)
+      return fail(MPCEKF_E_ARG, "thermal_get: fields[%d] = %d is not a MPCEKF_THR_* id (0..%d)", i, fields[i],
+                  (int)MPCEKF_NTHR - 1);
+    if (seen >> fields[i] & 1) return fail(MPCEKF_E_ARG, "thermal_get: fields: id %d given twice", fields[i]);
+    seen |= 1u << fields[i];
+  }
+  if (!X->d_th) return fail(MPCEKF_E_STATE, "thermal_get: call mpcekf_thermal_begin first");
+  HIPCHK(hipSetDevice(X->device));
+  const size_t n = (size_t)X->n;
+  for (int i = 0; i < nfields && n; ++i) {
+    const double *src = fields[i] == MPCEKF_THR_T ? X->s.Tc : X->d_th + (size_t)fields[i] * n;
+    HIPCHK(hipMemcpyAsync(values + (size_t)i * n, src, n * 8, hipMemcpyDeviceToHost, X->stream));
+  }
+  HIPCHK(hipStreamSynchronize(X->stream));
+  return MPCEKF_OK;
+}
+
+int mpcekf_thermal_end(mpcekf_ctx *X) {
+  if (!X) return fail(MPCEKF_E_ARG, "thermal_end: null ctx");
+  if (!X->d_th) return MPCEKF_OK;
+  HIPCHK(hipSetDevice(X->device));
+  HIPCHK(hipStreamSynchronize(X->stream));
+  retire_thermal_graphs(X);
+  void *ptrs[] = {X->d_th, X->d_th_par, X->d_th_i, X->d_th_ocv};
+  for (void *p : ptrs)
+    if (p) (void)hipFree(p);
+  X->d_th = X->d_th_par = X->d_th_i = X->d_th_ocv = nullptr;
+  X->th_nocv = 0;
+  return MPCEKF_OK;
+}
+
+int mpcekf_step_ex_thermal(mpcekf_ctx *X, int32_t nsteps, const mpcekf_traj *tr, const int32_t *slots, int32_t nslots,
+                           double *obs, double *temp, double *heat, int32_t outputs_on_device) {
+  if (!X) return fail(MPCEKF_E_ARG, "step_ex_thermal: null ctx");
+  if (!X->d_th) return fail(MPCEKF_E_STATE, "step_ex_thermal: call mpcekf_thermal_begin first");
+  return step_impl(X, nsteps, nullptr, tr, slots, nslots, obs, outputs_on_device, false, temp, heat);
 }
 
 int mpcekf_set_timing(mpcekf_ctx *X, int32_t enable) {

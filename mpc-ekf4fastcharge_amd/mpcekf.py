@@ -25,7 +25,7 @@ from . import _lib
 from ._lib import LIN_SIZE, MpcekfError, check, dptr, iptr
 from .rom import EL_TABLES, OBS_FIELDS, ROM, TF_CODE
 
-__all__ = ["Context", "DeviceBuffer", "hip_runtimes", "tc_grid", "make_config", "predMat", "constraintsMPC", "constraint_rows", "hildreth", "runMPC", "run_summary", "MpcekfError",
+__all__ = ["Context", "DeviceBuffer", "hip_runtimes", "tc_grid", "make_config", "predMat", "constraintsMPC", "constraint_rows", "hildreth", "runMPC", "run_summary", "thermal_ocv", "MpcekfError",
            "LIN_SIZE"]
 
 LIN_FIELDS = dict(A=slice(0, 6), Csoc=slice(6, 12), Dsoc=12, Cv=slice(13, 19), Dv=19,
@@ -275,7 +275,7 @@ class Context:
                        norm_du=(np.float64, ()), nviol=(np.int32, ()), poles=(np.float64, (7, 2)),
                        sv=(np.float64, (7,)))
 
-    def step(self, nsteps, outputs=("u", "v", "soc", "phise", "nexec"), tc=None, obs=None):
+    def step(self, nsteps, outputs=("u", "v", "soc", "phise", "nexec"), tc=None, obs=None, thermal=None):
         """nsteps fused closed-loop steps (runMPC.m:83-112).  ``outputs`` names the per-step
         stores to return as [nsteps, ncells(, k)] arrays: u, v, soc, phise, nexec, and the
         diagnostics x (x_store), zk / zbk (zkEst / zkBound), J_unc, J_fin, norm_du, nviol
@@ -287,9 +287,18 @@ class Context:
         each step starts from; ``phise`` above is the EKF's estimate): True for every field,
         or a field name / tuple of names as OB_step(obs=...) takes them.  Adds out["obs"], a
         dict field -> [nsteps, ncells] (scalar fields) or [nsteps, ncells, len] (vector
-        fields); only the selected slots are computed and copied.  None: the call as it was."""
+        fields); only the selected slots are computed and copied.  None: the call as it was.
+        ``thermal``: on a context with a thermal model (thermal_begin), the model's per-step rows
+        to return as [nsteps, ncells] arrays: "temp" (the temperature each step used) and / or
+        "heat" (the heat it generated, W); mpcekf_step_ex_thermal.  None: the call as it was."""
         n = self.n
         fields, slots = self._obs_select(obs, "step")   # KeyError before any library call
+        th = () if thermal is None else (thermal,) if isinstance(thermal, str) else tuple(thermal)
+        for k in th:
+            if k not in ("temp", "heat"):
+                raise KeyError(f"step: unknown thermal row {k!r} (one of ('temp', 'heat'))")
+        if thermal is not None and tc is not None:
+            raise ValueError("step: thermal rows come from the model, which takes no tc")
         tcs = None if tc is None else tc_grid(tc, nsteps, n)
         out = {}
         tr = _lib.Traj()
@@ -301,15 +310,22 @@ class Context:
             out[k] = np.empty((nsteps, n) + tail, dtype=dt)
             setattr(tr, k, out[k].ctypes.data_as(C.c_void_p).value)
         tcp = tcs.ctypes.data_as(C.c_void_p) if tcs is not None else None
-        if fields is None:
+        rec = None if fields is None else np.empty((nsteps, slots.size, n))
+        if thermal is not None:
+            for k in th:
+                out[k] = np.empty((nsteps, n))
+            vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+            ns = 0 if fields is None else int(slots.size)
+            check(self.L.mpcekf_step_ex_thermal(self.h, int(nsteps), C.byref(tr), iptr(slots) if ns else None, ns,
+                                                vp(rec) if ns else None, vp(out.get("temp")), vp(out.get("heat")), 0))
+        elif fields is None:
             check(self.L.mpcekf_step_ex(self.h, int(nsteps), tcp, C.byref(tr), 0))
+        elif slots.size:
+            check(self.L.mpcekf_step_ex_obs(self.h, int(nsteps), tcp, C.byref(tr), iptr(slots), int(slots.size),
+                                            rec.ctypes.data_as(C.c_void_p), 0))
         else:
-            rec = np.empty((nsteps, slots.size, n))
-            if slots.size:
-                check(self.L.mpcekf_step_ex_obs(self.h, int(nsteps), tcp, C.byref(tr), iptr(slots), int(slots.size),
-                                                rec.ctypes.data_as(C.c_void_p), 0))
-            else:
-                check(self.L.mpcekf_step_ex(self.h, int(nsteps), tcp, C.byref(tr), 0))
+            check(self.L.mpcekf_step_ex(self.h, int(nsteps), tcp, C.byref(tr), 0))
+        if fields is not None:
             lay, pos, out["obs"] = self.rom.obs_layout(), 0, {}
             for k in fields:   # slot-major rows per step -> [nsteps, n] / [nsteps, n, len]
                 m = lay[k].stop - lay[k].start
@@ -465,6 +481,51 @@ class Context:
     def summary_end(self):
         """Free the summary record and its window (mpcekf_summary_end)."""
         check(self.L.mpcekf_summary_end(self.h))
+
+    # -- per-cell lumped thermal model along the fused loop ----------------
+    THERMAL_PARAMS = _lib.THERMAL_PARAMS
+    THERMAL_FIELDS = _lib.THERMAL_FIELDS
+
+    @staticmethod
+    def _per_cell(n, name, v, who="thermal_begin"):
+        """A scalar or a length-n array -> float64 [n]; ValueError for any other shape."""
+        a = np.asarray(v, dtype=np.float64)
+        if a.ndim > 1 or (a.ndim == 1 and a.shape[0] != n):
+            raise ValueError(f"{who}: {name} must be a scalar or a length-{n} array, got shape {a.shape}")
+        return np.broadcast_to(a, (n,))
+
+    def thermal_begin(self, Cth, Rth, Tamb, ocv, T0=None):
+        """Give the context a per-cell lumped thermal model (mpcekf_thermal_begin): heat capacity
+        ``Cth`` (J/K), thermal resistance to the ambient ``Rth`` (K/W, np.inf: adiabatic) and
+        ambient temperature ``Tamb`` (degC), each a scalar or [ncells]; ``ocv``: the open-circuit
+        voltage on a uniform grid of cell SOC 0..1 (see :func:`thermal_ocv`); ``T0`` (degC,
+        scalar or [ncells]): the temperature to start from, None keeps the cells' own.  From then
+        on every fused call advances each cell's temperature after every step (and takes no
+        ``tc``); a second call replaces the model and resets its record."""
+        n = self.n
+        par = np.ascontiguousarray(np.stack([self._per_cell(n, k, v) for k, v in
+                                             zip(self.THERMAL_PARAMS, (Cth, Rth, Tamb))]), dtype=np.float64)
+        tab = np.ascontiguousarray(ocv, dtype=np.float64)
+        if tab.ndim != 1:
+            raise ValueError(f"thermal_begin: ocv must be a 1-D table, got shape {tab.shape}")
+        t0 = None if T0 is None else np.ascontiguousarray(self._per_cell(n, "T0", T0))
+        check(self.L.mpcekf_thermal_begin(self.h, dptr(par), int(tab.size), dptr(tab), dptr(t0)))
+
+    def thermal_get(self, fields=None):
+        """{name: [ncells] float64} of the thermal record (mpcekf_thermal_get): ``fields`` names of
+        THERMAL_FIELDS (default all).  Step indices and counts are exact integers."""
+        names = self.THERMAL_FIELDS if fields is None else (fields,) if isinstance(fields, str) else tuple(fields)
+        for k in names:
+            if k not in self.THERMAL_FIELDS:
+                raise KeyError(f"thermal_get: unknown field {k!r} (one of {self.THERMAL_FIELDS})")
+        ids = np.asarray([self.THERMAL_FIELDS.index(k) for k in names], dtype=np.int32)
+        vals = np.empty((ids.size, self.n))
+        check(self.L.mpcekf_thermal_get(self.h, int(ids.size), iptr(ids), dptr(vals)))
+        return {k: vals[i] for i, k in enumerate(names)}
+
+    def thermal_end(self):
+        """Drop the thermal model (mpcekf_thermal_end): the cells keep their temperature."""
+        check(self.L.mpcekf_thermal_end(self.h))
 
     def set_timing(self, enable=True):
         """enable: True/1 = every step; N > 1 = sample every N-th step (less perturbation)."""
@@ -798,31 +859,49 @@ def structured_M(Hv, He, Hs):
     return M
 
 
-def runMPC(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=None, obs=None, limits=None):
+def thermal_ocv(rom, n=101, T_degC=25.0):
+    """The cell's open-circuit voltage on a uniform grid of n cell-SOC points 0..1 at T_degC, from
+    the ROM's own electrode handles: Uocp_pos(soc_pos(z, T), T) - Uocp_neg(soc_neg(z, T), T).
+    Host numpy only; the table Context.thermal_begin takes."""
+    T = float(T_degC) + 273.15
+    pos, neg = rom.fn("pos"), rom.fn("neg")   # scalar functions, as the reference's handles are called
+    return np.array([float(pos.Uocp(pos.soc(z, T), T)) - float(neg.Uocp(neg.soc(z, T), T))
+                     for z in np.linspace(0.0, 1.0, int(n)).tolist()], dtype=np.float64)
+
+
+def runMPC(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=None, obs=None, limits=None,
+           thermal=None):
     """runMPC.m:72-112 for a batch of cells; returns trajectories [nsteps, ncells].
     tc_traj [nsteps, ncells] (degC): a temperature profile (TC is the initial one).
     obs: the plant's observables of every step as out["obs"] (Context.step's obs=).
     limits: per-cell targets and limits, a dict of Context.set_limits' keywords (a protocol
-    sweep: runMPC.m:30-44 per cell), set after init_cells and before the first step."""
+    sweep: runMPC.m:30-44 per cell), set after init_cells and before the first step.
+    thermal: a dict of Context.thermal_begin's keywords (Cth, Rth, Tamb, ocv, T0): the cells
+    heat themselves (TC is the initial temperature; no tc_traj); adds out["temp"], out["heat"]
+    and out["thermal"], the model's record."""
     SOC0 = np.atleast_1d(np.asarray(SOC0, dtype=np.float64))
     n = ncells or SOC0.shape[0]
     with Context(rom, n, cfg, device) as ctx:
         ctx.init_cells(SOC0, TC)
         if limits:
             ctx.set_limits(**limits)
-        out = ctx.step(nsteps, tc=tc_traj, obs=obs)
+        if thermal:
+            ctx.thermal_begin(**thermal)
+        out = ctx.step(nsteps, tc=tc_traj, obs=obs, thermal=("temp", "heat") if thermal else None)
+        if thermal:
+            out["thermal"] = ctx.thermal_get()
         out["status"] = ctx.get_state()["status"]
         return out
 
 
 def run_summary(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=None, limits=None, reach=None,
-                obs=None, chunk=None):
+                obs=None, chunk=None, thermal=None):
     """runMPC.m:72-112 for a batch of cells, read out as the per-cell charge summary instead of
     trajectories: {field: [ncells]} of Context.get_summary plus "status".  limits: as runMPC's
     (a protocol sweep); reach, obs: Context.summary_begin's; tc_traj [nsteps, ncells] (degC): a
     temperature profile; chunk: steps per step_summary call (default all at once; with tc_traj
     a chunk bounds the host array each call converts).  Neither host nor device memory grows
-    with nsteps."""
+    with nsteps.  thermal: as runMPC's (no tc_traj); adds "thermal", the model's record."""
     SOC0 = np.atleast_1d(np.asarray(SOC0, dtype=np.float64))
     n = ncells or SOC0.shape[0]
     nsteps = int(nsteps)
@@ -834,11 +913,15 @@ def run_summary(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=
         ctx.init_cells(SOC0, TC)
         if limits:
             ctx.set_limits(**limits)
+        if thermal:
+            ctx.thermal_begin(**thermal)
         ctx.summary_begin(reach=reach, obs=obs)
         for k in range(0, nsteps, max(chunk, 1)):
             m = min(chunk, nsteps - k)
             ctx.step_summary(m, tc=None if tcs is None else tcs[k:k + m])
         out = ctx.get_summary()
+        if thermal:
+            out["thermal"] = ctx.thermal_get()
         out["status"] = ctx.get_state()["status"]
         return out
 
