@@ -211,6 +211,16 @@ struct mpcekf_ctx {
   int ekf4_block = 256;       // k_ekf4 launch bound (MPCEKF_EKF4_BLOCK=512 / 1024: 256 / 128 VGPRs)
   int *d_ts = nullptr;        // deferred time update: ts_ekf, ts_plant [n][NM]
   double *d_hist = nullptr;   // input rings hist_p, hist_u [LAZY_H][n]
+  // the corner window (KState::hot_*): d_hot [4][REC][n] doubles, d_hot_i the
+  // tags and timestamps [2][4][n].  Allocated for 'OB' contexts whose fused step runs iterEKF in
+  // the lane-per-cell k_cell with the whole-batch flush (MPCEKF_HOT_CORNERS=0 turns it off);
+  // null otherwise, and the kernels then do what they did without one
+  double *d_hot = nullptr;
+  int *d_hot_i = nullptr;
+  int hot_clear() {  // every slot empty (context creation, init_cells, set_state)
+    if (d_hot_i) HIPCHK(hipMemsetAsync(d_hot_i, 0xFF, (size_t)n * 4 * sizeof(int), stream));
+    return MPCEKF_OK;
+  }
   long long *d_stamps = nullptr;  // profiling builds: k_cell section stamps
   // wide horizons (Np = 20, Nc = 10; mpcekf_wide.hip): k_cell hands the linearisation over
   bool wide = false;
@@ -1060,6 +1070,29 @@ int mpcekf_ctx_create(const mpcekf_rom *rom, const mpcekf_config *cfg, int devic
   s.hist_p = X->d_hist; s.hist_u = X->d_hist + n * LAZY_H;
   s.mb = X->d_mb;
   s.stamps = X->d_stamps;
+  {
+    // MPCEKF_HOT_CORNERS=0/1: the corner window off / on where eligible (default on).  The
+    // quad route's k_ekf4 and the MB filter do not know it, and the rolling flush runs its
+    // slices beside k_bounds, which reads the window.  An allocation that fails leaves the
+    // context without a window, not without a context.
+    bool hot = true;
+    if (const char *e = std::getenv("MPCEKF_HOT_CORNERS")) hot = std::atoi(e) != 0;
+    if (hot && !X->mb && !X->quad && !X->flush_roll && n > 0) {
+      if (hipMalloc((void **)&X->d_hot, n * 4 * REC * sizeof(double)) != hipSuccess ||
+          hipMalloc((void **)&X->d_hot_i, n * 8 * sizeof(int)) != hipSuccess) {
+        (void)hipGetLastError();
+        if (X->d_hot) (void)hipFree(X->d_hot);
+        if (X->d_hot_i) (void)hipFree(X->d_hot_i);
+        X->d_hot = nullptr;
+        X->d_hot_i = nullptr;
+      } else {
+        s.hot_rec = X->d_hot;
+        s.hot_m = X->d_hot_i;
+        s.hot_ts = X->d_hot_i + n * 4;
+        if ((rc = X->hot_clear())) { mpcekf_ctx_destroy(X); return rc; }
+      }
+    }
+  }
   // rows the current launch sequence does not write (k_plant's 12..19 when the plant runs
   // inside k_cell) read back as zero, never as stale allocation contents
   if (X->d_stamps) HIPCHK(hipMemset(X->d_stamps, 0, (size_t)n * NSTAMPS * sizeof(long long)));
@@ -1111,7 +1144,7 @@ int mpcekf_ctx_destroy(mpcekf_ctx *X) {
                   X->w.prob, X->w.X, X->w.R, X->w.K, X->w.hii, X->w.it, X->w.smin, X->d_lin, X->d_zsoc, X->d_mb, X->d_uk1p,
                   X->w.q, X->w.list, X->w.hist, X->d_poly, X->d_szk, X->d_sxg, X->d_sxm, X->d_slin, X->d_sv, X->d_zslot,
                   X->d_obs_blob, X->d_obs, X->d_obs_plan, X->d_lim, X->d_sum, X->d_sum_reach, X->d_sum_obs,
-                  X->d_sum_ring, X->d_th, X->d_th_par, X->d_th_i, X->d_th_ocv};
+                  X->d_sum_ring, X->d_th, X->d_th_par, X->d_th_i, X->d_th_ocv, X->d_hot, X->d_hot_i};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   for (auto &g : X->graphs) (void)hipGraphExecDestroy(g.exec);
@@ -1188,6 +1221,7 @@ int mpcekf_init_cells(mpcekf_ctx *X, const double *soc0_pct, const double *tc_de
   HIPCHK(hipMemsetAsync(X->s.lam, 0, n * X->ncon_dev * 8, X->stream));
   HIPCHK(hipMemsetAsync(X->d_int, 0, n * 4 * sizeof(int), X->stream));
   HIPCHK(hipMemsetAsync(X->d_ts, 0, n * X->NM * 2 * sizeof(int), X->stream));  // every model current
+  if ((rc0 = X->hot_clear())) return rc0;  // and every record in s.ekf
   int rc = launch_init_state(X->n, X->NM, X->s.ekf, X->s.bigx, X->cfg.SigmaX0, X->stream);
   if (rc) return fail(MPCEKF_E_HIP, "init kernel: %s", hipGetErrorString((hipError_t)rc));
   if (X->mb) {  // initKF.m:47-48,111-112: xhat = 0, SigmaX = SigmaX0 (6x6)
@@ -1560,6 +1594,7 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
     key.push_back((uintptr_t)osel.plan);  // a regrown plan buffer retires the graphs that named the old one
     key.push_back((uintptr_t)nslots);
     key.push_back((uintptr_t)lim);  // set / clear change the launch sequence: graphs of the other one are not replayed
+    key.push_back((uintptr_t)X->s.hot_rec);  // the corner window the captured kernels name (null: none)
     for (int i = 0; i < nslots; ++i) key.push_back((uintptr_t)slots[i]);
     // the thermal state (its temp / heat rows are among the output rows above): third from the
     // end, 0 on a context without a model -- mpcekf_thermal_end retires the graphs that name one
@@ -2665,6 +2700,7 @@ int mpcekf_set_state(mpcekf_ctx *X, const mpcekf_state *st) {
   const size_t n = (size_t)X->n, NM = (size_t)X->NM, nc = (size_t)X->ncon, ncd = (size_t)X->ncon_dev;
   if (st->bigX) HIPCHK(hipMemcpyAsync(X->s.bigx, st->bigX, n * NM * 6 * 8, hipMemcpyHostToDevice, X->stream));
   if (st->ekf) HIPCHK(hipMemcpyAsync(X->s.ekf, st->ekf, n * NM * REC * 8, hipMemcpyHostToDevice, X->stream));
+  if ((rc = X->hot_clear())) return rc;  // the corner window is empty between fused calls: it stays so
   if (st->mb && X->mb) HIPCHK(hipMemcpyAsync(X->d_mb, st->mb, n * MBREC * 8, hipMemcpyHostToDevice, X->stream));
   // scal and lambda are whole blocks (every slot given); warn and status share one block,
   // read back first when only one of them is given

@@ -388,18 +388,22 @@ __device__ __forceinline__ void get_xind(int nT, int nZ, const double *Tp, const
   xi.m[3] = iTu * nZ + iZu;
 }
 
-__device__ __forceinline__ void load_x(const double *rec, double x[NX]) {
+// A corner record as REC / 2 pairs of doubles, pair e at rec2[e * st]: st = 1 is the record in
+// s.ekf, st = n a slot of the corner window (KState::hot_rec).  The stride is a per-lane value
+// where a lane takes its record from either place; the loads and stores are the same 16-byte
+// ones in both.
+__device__ __forceinline__ void load_x(const double *rec, double x[NX], size_t st = 1) {
   const double2 *p = reinterpret_cast<const double2 *>(rec);
-  double2 a = p[0], b = p[1];
+  double2 a = p[0], b = p[st];
   x[0] = a.x; x[1] = a.y; x[2] = b.x; x[3] = b.y;
-  x[4] = rec[4];
+  x[4] = reinterpret_cast<const double *>(p + 2 * st)[0];
 }
-__device__ __forceinline__ void load_rec(const double *rec, double x[NX], double S[NPK]) {
+__device__ __forceinline__ void load_rec(const double *rec, double x[NX], double S[NPK], size_t st = 1) {
   const double2 *p = reinterpret_cast<const double2 *>(rec);
   double v[REC];
 #pragma unroll
   for (int i = 0; i < REC / 2; ++i) {
-    double2 t = p[i];
+    double2 t = p[i * st];
     v[2 * i] = t.x;
     v[2 * i + 1] = t.y;
   }
@@ -408,7 +412,7 @@ __device__ __forceinline__ void load_rec(const double *rec, double x[NX], double
 #pragma unroll
   for (int i = 0; i < NPK; ++i) S[i] = v[NX + i];
 }
-__device__ __forceinline__ void store_rec(double *rec, const double x[NX], const double S[NPK]) {
+__device__ __forceinline__ void store_rec(double *rec, const double x[NX], const double S[NPK], size_t st = 1) {
   double2 *p = reinterpret_cast<double2 *>(rec);
   double v[REC];
 #pragma unroll
@@ -416,17 +420,21 @@ __device__ __forceinline__ void store_rec(double *rec, const double x[NX], const
 #pragma unroll
   for (int i = 0; i < NPK; ++i) v[NX + i] = S[i];
 #pragma unroll
-  for (int i = 0; i < REC / 2; ++i) p[i] = make_double2(v[2 * i], v[2 * i + 1]);
+  for (int i = 0; i < REC / 2; ++i) p[i * st] = make_double2(v[2 * i], v[2 * i + 1]);
 }
-__device__ __forceinline__ void load_S(const double *rec, double S[NPK]) {
-  S[0] = rec[NX];
-  const double2 *p = reinterpret_cast<const double2 *>(rec + NX + 1);
+__device__ __forceinline__ void load_S(const double *rec, double S[NPK], size_t st = 1) {
+  const double2 *p = reinterpret_cast<const double2 *>(rec);
+  S[0] = reinterpret_cast<const double *>(p + 2 * st)[1];
 #pragma unroll
   for (int i = 0; i < 7; ++i) {
-    double2 t = p[i];
+    double2 t = p[(3 + i) * st];
     S[1 + 2 * i] = t.x;
     S[2 + 2 * i] = t.y;
   }
+}
+// slot j of cell c in the corner window, as a record pointer for the accessors above (st = n)
+__device__ __forceinline__ double *hot_slot(const KState &s, int j, int64_t c) {
+  return s.hot_rec + 2 * ((size_t)j * HOT_PAIRS * (size_t)s.n + (size_t)c);
 }
 
 // ---------------------------------------------------------------------------
@@ -1610,18 +1618,30 @@ __global__ void __launch_bounds__(256) k_flush(const KRom r, const KCfg cf, cons
     struct FCell {
       double hpl, hul, xe[REC], xp[6];
       int tse, tsp;
+      int slot;  // the corner-window slot that holds this lane's model, -1: its record is in s.ekf
     };
     auto fload = [&](int64_t c, FCell &F) {
       F.hpl = s.hist_p[(size_t)(lane & (LAZY_H - 1)) * s.n + c];
       F.hul = s.hist_u[(size_t)(lane & (LAZY_H - 1)) * s.n + c];
+      // the cell's four window tags (wave-uniform): the lane whose model a slot holds takes the
+      // record and timestamp from that slot
+      F.slot = -1;
+      if (s.hot_m) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (act && s.hot_m[(size_t)j * s.n + c] == m) F.slot = j;
+      }
+      const int *tp = F.slot >= 0 ? s.hot_ts + (size_t)F.slot * s.n + c : s.ts_ekf + c * NM + mm;
       // MB never time-updates the per-model EKF records (iterEKF.m:90-102)
-      F.tse = (act && !(cf.flags & KF_MB)) ? s.ts_ekf[c * NM + m] : t;
+      F.tse = (act && !(cf.flags & KF_MB)) ? *tp : t;
       F.tsp = act ? s.ts_plant[c * NM + m] : t;
-      const double2 *re = reinterpret_cast<const double2 *>(s.ekf + ((size_t)c * NM + mm) * REC);
+      const double2 *re = reinterpret_cast<const double2 *>(F.slot >= 0 ? hot_slot(s, F.slot, c)
+                                                                        : s.ekf + ((size_t)c * NM + mm) * REC);
+      const size_t rst = F.slot >= 0 ? (size_t)s.n : 1;
       const double2 *rp = reinterpret_cast<const double2 *>(s.bigx + ((size_t)c * NM + mm) * 6);
 #pragma unroll
       for (int e = 0; e < REC / 2; ++e) {
-        const double2 v = re[e];
+        const double2 v = re[e * rst];
         F.xe[2 * e] = v.x;
         F.xe[2 * e + 1] = v.y;
       }
@@ -1659,10 +1679,13 @@ __global__ void __launch_bounds__(256) k_flush(const KRom r, const KCfg cf, cons
           for (int e = 0; e < 6; ++e) xp[e] = __builtin_fma(cp[e], xp[e], u);
         }
       }
-      if (tse < t) {
+      // a record held in the corner window goes back to s.ekf even when it is current (the
+      // copy there is stale), and its slot is left empty
+      if (tse < t || cur.slot >= 0) {
 #pragma unroll
         for (int e = 0; e < REC / 2; ++e) re[e] = make_double2(xe[2 * e], xe[2 * e + 1]);
       }
+      if (cur.slot >= 0) s.hot_m[(size_t)cur.slot * s.n + c] = -1;
       if (tsp < t) {
 #pragma unroll
         for (int e = 0; e < 3; ++e) rp[e] = make_double2(xp[2 * e], xp[2 * e + 1]);
@@ -1711,12 +1734,13 @@ __device__ __forceinline__ void replay_S(double S[NPK], const double *a, int ts,
 
 template <int NZ>
 __device__ __forceinline__ void ekf_catch_up4(const KState &s, const CellCtx &cc, int NM, const int m[4], int64_t c,
-                                              int t, double W, double pt) {
+                                              int t, double W, double pt, const bool held[4]) {
   // all timestamps, then all lagging records, in flight together (latency, not bytes,
-  // is the cost here); a model named by several corners is advanced once
+  // is the cost here); a model named by several corners is advanced once.  held[j]: the
+  // model is current in the corner window (its s.ekf record and timestamp are stale)
   int ts[4];
 #pragma unroll
-  for (int j = 0; j < 4; ++j) ts[j] = s.ts_ekf[c * NM + m[j]];
+  for (int j = 0; j < 4; ++j) ts[j] = held[j] ? t : s.ts_ekf[c * NM + m[j]];
   bool need[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
@@ -2274,11 +2298,47 @@ __global__ void __launch_bounds__(256) k_cell(const KRom r, const KCfg cf, const
       dup[j] = false;
 #pragma unroll
       for (int i = 0; i < j; ++i) dup[j] = dup[j] || xi.m[i] == xi.m[j];
+    }
+    // The corner window (KState::hot_*).  hot: this step's four records go to
+    // the window's slots 0..3 (a cell with a repeated corner keeps the record path).  hit: slot j
+    // already holds corner j's model for all four, so they are read from there as well.  A
+    // lane whose tags differ from its corners in any position first writes every held slot back
+    // to s.ekf / ts_ekf and reads its records there, as without a window (a model that moves
+    // from one slot to another at a set-point crossing goes through its record).  The loads and
+    // stores below are one code path: a per-lane base pointer and pair stride.
+    const size_t hn = (size_t)s.n;
+    const bool win = s.hot_m != nullptr && t != 0;
+    bool hot = false, hit = false;
+    if (win) {
+      int hm[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) hm[j] = s.hot_m[j * hn + c];
+      hot = !(dup[1] || dup[2] || dup[3]);
+      hit = hot && hm[0] == xi.m[0] && hm[1] == xi.m[1] && hm[2] == xi.m[2] && hm[3] == xi.m[3];
+      if (!hit) {
+#pragma unroll 1
+        for (int j = 0; j < 4; ++j) {
+          const int mh = s.hot_m[j * hn + c];
+          if (mh < 0) continue;
+          double xh[NX], Sh[NPK];
+          load_rec(hot_slot(s, j, c), xh, Sh, hn);
+          store_rec(cc.erec + (size_t)mh * REC, xh, Sh);
+          s.ts_ekf[c * r.NM + mh] = s.hot_ts[j * hn + c];
+          if (!hot) s.hot_m[j * hn + c] = -1;
+        }
+      }
+    }
+    const size_t rst = hit ? hn : 1;  // pair stride of the four records' loads
+    const size_t wst = hot ? hn : 1;  // and of their stores
+    auto rrec = [&](int j) -> const double * { return hit ? hot_slot(s, j, c) : cc.erec + (size_t)xi.m[j] * REC; };
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
       // corner 0's Sigma is what the gains use first: its whole record is read here; the
       // other corners read Sigma at their update (holding more spills: DESIGN.md 4.2)
-      if (j == 0) load_rec(cc.erec + (size_t)xi.m[j] * REC, xr[j], Sr[j]);
-      else load_x(cc.erec + (size_t)xi.m[j] * REC, xr[j]);
-      tsj[j] = t ? s.ts_ekf[c * r.NM + xi.m[j]] : 0;
+      if (j == 0) load_rec(rrec(j), xr[j], Sr[j], rst);
+      else load_x(rrec(j), xr[j], rst);
+      const int *tp = hit ? s.hot_ts + j * hn + c : s.ts_ekf + c * r.NM + xi.m[j];
+      tsj[j] = t ? *tp : 0;
     }
     // step t's ring input: the plant stores this cell's priorI there (k_plant4; cell_plant's
     // is stored only after body)
@@ -2350,10 +2410,10 @@ __global__ void __launch_bounds__(256) k_cell(const KRom r, const KCfg cf, const
     // that repeats an earlier model (dup) reads its record after that store, as before.
     double Sn[NPK];
     auto s_ahead = [&](int j) { return j >= 1 && j < 4 && !dup[j]; };
-    if (s_ahead(1)) load_S(cc.erec + (size_t)xi.m[1] * REC, Sn);
+    if (s_ahead(1)) load_S(rrec(1), Sn, rst);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      double *rec = cc.erec + (size_t)xi.m[j] * REC;
+      double *rec = cc.erec + (size_t)xi.m[j] * REC;  // a repeated corner's (dup: never in the window)
       double xj[NX], Sj[NPK];
       if (dup[j]) {
         load_rec(rec, xj, Sj);  // as the earlier update of this model left it
@@ -2370,9 +2430,14 @@ __global__ void __launch_bounds__(256) k_cell(const KRom r, const KCfg cf, const
         if (t && j > 0) replay_S(Sj, cc.L + xi.m[j] * cc.stride + NZ * NX + NZ, tsj[j], t, cf.SigmaW);
       }
       meas_update_regs<false>(xj, Sj, Lg[j], St[j], res);
-      if (j + 1 < 4 && s_ahead(j + 1)) load_S(cc.erec + (size_t)xi.m[j + 1] * REC, Sn);
-      store_rec(rec, xj, Sj);
-      if (t) s.ts_ekf[c * r.NM + xi.m[j]] = t;
+      if (j + 1 < 4 && s_ahead(j + 1)) load_S(rrec(j + 1), Sn, rst);
+      // to window slot j with tag m[j] and timestamp t (a hit rewrites no tag and touches no
+      // ts_ekf), or to the record
+      store_rec(hot ? hot_slot(s, j, c) : rec, xj, Sj, wst);
+      if (t) {
+        *(hot ? s.hot_ts + j * hn + c : s.ts_ekf + c * r.NM + xi.m[j]) = t;
+        if (hot && !hit) s.hot_m[j * hn + c] = xi.m[j];
+      }
 #pragma unroll
       for (int k = 0; k < NX; ++k) xu[j][k] = xj[k];
       __builtin_amdgcn_sched_barrier(0);
@@ -2390,9 +2455,29 @@ __global__ void __launch_bounds__(256) k_cell(const KRom r, const KCfg cf, const
     const bool same = m1[0] == xi.m[0] && m1[1] == xi.m[1] && m1[2] == xi.m[2] && m1[3] == xi.m[3] &&
                       !(dup[1] || dup[2] || dup[3]);
     if (!same) {
-      if (io.lazy_t) ekf_catch_up4<NZ>(s, cc, r.NM, xi.m, c, io.lazy_t, cf.SigmaW, pt);
+      // with the window, a corner that is one of the four just updated is current only there
+      // and in xu: it is taken from xu and never re-read from s.ekf; a new model is not in
+      // the window (its slots hold exactly m1) and goes through its record, as without one
+      bool held[4];
+      double xn[4][NX];
 #pragma unroll
-      for (int j = 0; j < 4; ++j) load_x(cc.erec + (size_t)xi.m[j] * REC, xu[j]);
+      for (int j = 0; j < 4; ++j) {
+        held[j] = false;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          if (hot && m1[i] == xi.m[j]) {
+            held[j] = true;
+#pragma unroll
+            for (int k = 0; k < NX; ++k) xn[j][k] = xu[i][k];
+          }
+      }
+      if (io.lazy_t) ekf_catch_up4<NZ>(s, cc, r.NM, xi.m, c, io.lazy_t, cf.SigmaW, pt, held);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if (!held[j]) load_x(cc.erec + (size_t)xi.m[j] * REC, xn[j]);
+#pragma unroll
+        for (int k = 0; k < NX; ++k) xu[j][k] = xn[j][k];
+      }
     }
     STAMP(7);
     vhat = get_vars<NZ>(r, cc, xi, ik, x0, SOC0, warn, st, Z, Zsoc, xu, 0, &kr2);
@@ -2464,7 +2549,21 @@ __global__ void __launch_bounds__(256) k_cell(const KRom r, const KCfg cf, const
 #pragma unroll
       for (int j = 0; j < 4; ++j) { xi.m[j] = io.xm_in[c * 4 + j]; xi.g[j] = io.xg_in[c * 4 + j]; }
     }
-    mats_handler<NZ>(r, cc, xi, zr, Zsoc, Tc + 273.15, L, MB ? s.x0[c] : 0.0, xmax, fused && (PARTS & P_EKF) && have_xmax,
+    if constexpr (!(PARTS & P_EKF) && !MB) {
+      // the fused step's second kernel: EKFmatsHandler's corner may be held in the corner
+      // window, where the iterEKF kernel left it (its s.ekf record is then stale)
+      if (fused && s.hot_m && io.lazy_t) {
+        int mx;
+        (void)corner_max(xi, &mx);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (!have_xmax && s.hot_m[(size_t)j * s.n + c] == mx) {
+            load_x(hot_slot(s, j, c), xmax, (size_t)s.n);
+            have_xmax = true;
+          }
+      }
+    }
+    mats_handler<NZ>(r, cc, xi, zr, Zsoc, Tc + 273.15, L, MB ? s.x0[c] : 0.0, xmax, fused && have_xmax,
                      fused && (PARTS & P_EKF) && have_kr2 ? &kr2 : nullptr);
     if (io.lin_out) lin_store(io.lin_out + c * 35, L);
     if (io.x_out)
@@ -2854,7 +2953,16 @@ __global__ void __launch_bounds__(BOUNDS_BLOCK) k_bounds(const KRom r, const KSt
   const double S0 = bd[BD_S0 * n + c];
   // SigmaX of the first corner for all four (iterEKF.m:191)
   double S1b[NPK];
-  load_S(s.ekf + ((size_t)c * r.NM + (valid ? (int)bd[BD_M * n + c] : 0)) * REC, S1b);
+  // from the corner window when a slot holds that model (the usual case: k_cell has just
+  // stored it there, and the read is coalesced across the wave's cells), else from its record
+  const int m0 = valid ? (int)bd[BD_M * n + c] : 0;
+  int hslot = -1;
+  if (s.hot_m) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      if (valid && s.hot_m[(size_t)i * n + c] == m0) hslot = i;
+  }
+  load_S(hslot >= 0 ? hot_slot(s, hslot, c) : s.ekf + ((size_t)c * r.NM + m0) * REC, S1b, hslot >= 0 ? (size_t)n : 1);
 #pragma unroll
   for (int k = 0; k < NX; ++k)
 #pragma unroll

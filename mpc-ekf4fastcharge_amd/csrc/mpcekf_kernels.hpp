@@ -109,7 +109,16 @@ struct KState {
   int *ts_ekf, *ts_plant;    // [n][NM]
   double *hist_p, *hist_u;   // [LAZY_H][n] priorI (EKF) and Iapp (plant) of step t at slot t % LAZY_H
   long long *stamps;         // [NSTAMPS][n] section clocks (-DMPCEKF_STAMPS builds only, else null)
+  // the corner window (fused loop only, between flushes; all null: no window):
+  // each cell's four active EKF records slot-major, so that a wave reads and writes them as
+  // whole 1-KB transactions.  Model m's record and timestamp are in slot j iff hot_m[j][c] == m;
+  // its copy in ekf / ts_ekf is then stale.  k_flush leaves every slot empty.
+  double *hot_rec;           // [4][REC / 2][n] pairs of doubles (element e of slot j: pair e / 2)
+  int *hot_m, *hot_ts;       // [4][n] the model a slot holds (-1: empty) and its timestamp
 };
+// a record in the corner window: HOT_PAIRS double2 per slot, pair e of slot j of cell c at
+// hot_rec2[(j * HOT_PAIRS + e) * n + c]
+constexpr int HOT_PAIRS = REC / 2;
 
 // mpcekf_plant_step_obs: the obs blob, the record and where each permuted row goes.
 // Blob: per model nz rows of OBS_ROW doubles [C 5][res0][D][0] in the permuted row order
