@@ -217,8 +217,14 @@ struct mpcekf_ctx {
   // null otherwise, and the kernels then do what they did without one
   double *d_hot = nullptr;
   int *d_hot_i = nullptr;
-  int hot_clear() {  // every slot empty (context creation, init_cells, set_state)
+  // the plant window (KState::hotp_*): d_hotp [4][6][n] doubles, d_hotp_i its tags and timestamps
+  // [2][4][n].  For the contexts that may have a corner window, when the plant runs inside k_cell
+  // (KRom::cell_plant); MPCEKF_HOT_PLANT=0 turns it off on its own
+  double *d_hotp = nullptr;
+  int *d_hotp_i = nullptr;
+  int hot_clear() {  // every slot of both windows empty (context creation, init_cells, set_state)
     if (d_hot_i) HIPCHK(hipMemsetAsync(d_hot_i, 0xFF, (size_t)n * 4 * sizeof(int), stream));
+    if (d_hotp_i) HIPCHK(hipMemsetAsync(d_hotp_i, 0xFF, (size_t)n * 4 * sizeof(int), stream));
     return MPCEKF_OK;
   }
   long long *d_stamps = nullptr;  // profiling builds: k_cell section stamps
@@ -1089,9 +1095,27 @@ int mpcekf_ctx_create(const mpcekf_rom *rom, const mpcekf_config *cfg, int devic
         s.hot_rec = X->d_hot;
         s.hot_m = X->d_hot_i;
         s.hot_ts = X->d_hot_i + n * 4;
-        if ((rc = X->hot_clear())) { mpcekf_ctx_destroy(X); return rc; }
       }
     }
+    // MPCEKF_HOT_PLANT=0/1: the plant window, for the same contexts when cell_plant runs the
+    // plant in k_cell (a ROM whose plant stays in k_plant4 gets none)
+    bool hotp = true;
+    if (const char *e = std::getenv("MPCEKF_HOT_PLANT")) hotp = std::atoi(e) != 0;
+    if (hotp && !X->mb && !X->quad && !X->flush_roll && X->r.cell_plant && n > 0) {
+      if (hipMalloc((void **)&X->d_hotp, n * 4 * 6 * sizeof(double)) != hipSuccess ||
+          hipMalloc((void **)&X->d_hotp_i, n * 8 * sizeof(int)) != hipSuccess) {
+        (void)hipGetLastError();
+        if (X->d_hotp) (void)hipFree(X->d_hotp);
+        if (X->d_hotp_i) (void)hipFree(X->d_hotp_i);
+        X->d_hotp = nullptr;
+        X->d_hotp_i = nullptr;
+      } else {
+        s.hotp_x = X->d_hotp;
+        s.hotp_m = X->d_hotp_i;
+        s.hotp_ts = X->d_hotp_i + n * 4;
+      }
+    }
+    if ((rc = X->hot_clear())) { mpcekf_ctx_destroy(X); return rc; }
   }
   // rows the current launch sequence does not write (k_plant's 12..19 when the plant runs
   // inside k_cell) read back as zero, never as stale allocation contents
@@ -1144,7 +1168,7 @@ int mpcekf_ctx_destroy(mpcekf_ctx *X) {
                   X->w.prob, X->w.X, X->w.R, X->w.K, X->w.hii, X->w.it, X->w.smin, X->d_lin, X->d_zsoc, X->d_mb, X->d_uk1p,
                   X->w.q, X->w.list, X->w.hist, X->d_poly, X->d_szk, X->d_sxg, X->d_sxm, X->d_slin, X->d_sv, X->d_zslot,
                   X->d_obs_blob, X->d_obs, X->d_obs_plan, X->d_lim, X->d_sum, X->d_sum_reach, X->d_sum_obs,
-                  X->d_sum_ring, X->d_th, X->d_th_par, X->d_th_i, X->d_th_ocv, X->d_hot, X->d_hot_i};
+                  X->d_sum_ring, X->d_th, X->d_th_par, X->d_th_i, X->d_th_ocv, X->d_hot, X->d_hot_i, X->d_hotp, X->d_hotp_i};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   for (auto &g : X->graphs) (void)hipGraphExecDestroy(g.exec);
@@ -1595,6 +1619,7 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
     key.push_back((uintptr_t)nslots);
     key.push_back((uintptr_t)lim);  // set / clear change the launch sequence: graphs of the other one are not replayed
     key.push_back((uintptr_t)X->s.hot_rec);  // the corner window the captured kernels name (null: none)
+    key.push_back((uintptr_t)X->s.hotp_x);   // and the plant window
     for (int i = 0; i < nslots; ++i) key.push_back((uintptr_t)slots[i]);
     // the thermal state (its temp / heat rows are among the output rows above): third from the
     // end, 0 on a context without a model -- mpcekf_thermal_end retires the graphs that name one
@@ -2700,7 +2725,7 @@ int mpcekf_set_state(mpcekf_ctx *X, const mpcekf_state *st) {
   const size_t n = (size_t)X->n, NM = (size_t)X->NM, nc = (size_t)X->ncon, ncd = (size_t)X->ncon_dev;
   if (st->bigX) HIPCHK(hipMemcpyAsync(X->s.bigx, st->bigX, n * NM * 6 * 8, hipMemcpyHostToDevice, X->stream));
   if (st->ekf) HIPCHK(hipMemcpyAsync(X->s.ekf, st->ekf, n * NM * REC * 8, hipMemcpyHostToDevice, X->stream));
-  if ((rc = X->hot_clear())) return rc;  // the corner window is empty between fused calls: it stays so
+  if ((rc = X->hot_clear())) return rc;  // both windows are empty between fused calls: they stay so
   if (st->mb && X->mb) HIPCHK(hipMemcpyAsync(X->d_mb, st->mb, n * MBREC * 8, hipMemcpyHostToDevice, X->stream));
   // scal and lambda are whole blocks (every slot given); warn and status share one block,
   // read back first when only one of them is given

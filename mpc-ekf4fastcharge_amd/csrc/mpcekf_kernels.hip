@@ -1161,17 +1161,30 @@ __device__ __forceinline__ void plant_weights(const double *Tp, const double *Zp
   if (Zu != Zl) aZ = (cellSOC - Zl) / (Zu - Zl);
   if (Tu != Tl) aT = (T - Tl) / (Tu - Tl);
 }
-// a corner's 6 states (48 B of bigx)
-__device__ __forceinline__ void load_corner(const double *bx, double xs[6]) {
+// a corner's 6 states as three pairs, pair e at bx2[e * st]: st = 1 is the 48 B of bigx, st = n
+// a slot of the plant window (KState::hotp_x); the same 16-byte loads and stores in both
+__device__ __forceinline__ void load_corner(const double *bx, double xs[6], size_t st = 1) {
   const double2 *p = reinterpret_cast<const double2 *>(bx);
-  const double2 q0 = p[0], q1 = p[1], q2 = p[2];
+  const double2 q0 = p[0], q1 = p[st], q2 = p[2 * st];
   xs[0] = q0.x; xs[1] = q0.y; xs[2] = q1.x; xs[3] = q1.y; xs[4] = q2.x; xs[5] = q2.y;
 }
-__device__ __forceinline__ void store_corner(double *bx, const double x[6]) {
+__device__ __forceinline__ void store_corner(double *bx, const double x[6], size_t st = 1) {
   double2 *p = reinterpret_cast<double2 *>(bx);
   p[0] = make_double2(x[0], x[1]);
-  p[1] = make_double2(x[2], x[3]);
-  p[2] = make_double2(x[4], x[5]);
+  p[st] = make_double2(x[2], x[3]);
+  p[2 * st] = make_double2(x[4], x[5]);
+}
+// slot j of cell c in the plant window, as a state pointer for the two above (st = n)
+__device__ __forceinline__ double *hotp_slot(const KState &s, int j, int64_t c) {
+  return s.hotp_x + 2 * ((size_t)j * HOTP_PAIRS * (size_t)s.n + (size_t)c);
+}
+// the plant-window slot that holds model m of cell c (-1: none, its state is in bigx)
+__device__ __forceinline__ int hotp_find(const KState &s, int64_t c, int m) {
+  int slot = -1;
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    if (s.hotp_m[(size_t)i * s.n + c] == m) slot = i;
+  return slot;
 }
 // SOCnAvg / SOCpAvg through this step (OB_step.m:212-219)
 __device__ __forceinline__ void plant_soc_step(const KRom &r, const ETab &et, double SOC0n, double SOC0p, double Iapp,
@@ -1394,8 +1407,12 @@ __device__ __forceinline__ void obs_cell(const KRom &r, const KState &s, const K
   k.cellSOC = (k.negSOC - r.th0n) / (r.th100n - r.th0n);  // OB_step.m:228
   const PlantCorners pc = plant_corners(r, ob.Tp, ob.Zp, k.cellSOC, T);
   k.mj = corner_model(r, pc, j);
-  load_corner(s.bigx + ((size_t)c * r.NM + k.mj) * 6, k.xs);
-  if (tsj) *tsj = s.ts_plant[c * r.NM + k.mj];
+  // along the fused loop (tsj: k_obs_traj) the corner may be held in the plant window, where
+  // k_cell's cell_plant left it at step t - 1; the stage route never meets a held slot
+  const int slot = tsj && s.hotp_m ? hotp_find(s, c, k.mj) : -1;
+  load_corner(slot >= 0 ? hotp_slot(s, slot, c) : s.bigx + ((size_t)c * r.NM + k.mj) * 6, k.xs,
+              slot >= 0 ? (size_t)s.n : 1);
+  if (tsj) *tsj = *(slot >= 0 ? s.hotp_ts + (size_t)slot * s.n + c : s.ts_plant + c * r.NM + k.mj);
   plant_weights(ob.Tp, ob.Zp, pc, k.cellSOC, T, k.aZ, k.aT);
   k.B = ob.L + (size_t)k.mj * o.stride;
 }
@@ -1618,45 +1635,64 @@ __global__ void __launch_bounds__(256) k_flush(const KRom r, const KCfg cf, cons
     struct FCell {
       double hpl, hul, xe[REC], xp[6];
       int tse, tsp;
-      int slot;  // the corner-window slot that holds this lane's model, -1: its record is in s.ekf
+      int slot;   // the corner-window slot that holds this lane's model, -1: its record is in s.ekf
+      int pslot;  // the plant-window slot that holds it, -1: its plant state is in s.bigx
     };
-    auto fload = [&](int64_t c, FCell &F) {
+    // the cell's eight window tags in one load (lanes 0..3 the corner window's, 4..7 the plant
+    // window's; -1 where there is no window), taken one cell ahead of the records: the slot, and
+    // with it the address of every record load, then depends on no load of the same stage
+    const int *tags = lane < 4 ? s.hot_m : s.hotp_m;
+    auto ftag = [&](int64_t c) -> int { return lane < 8 && tags ? tags[(size_t)(lane & 3) * s.n + c] : -1; };
+    auto fload = [&](int64_t c, FCell &F, const int tag) {
       F.hpl = s.hist_p[(size_t)(lane & (LAZY_H - 1)) * s.n + c];
       F.hul = s.hist_u[(size_t)(lane & (LAZY_H - 1)) * s.n + c];
-      // the cell's four window tags (wave-uniform): the lane whose model a slot holds takes the
-      // record and timestamp from that slot
+      // the tags handed round by readlane: the lane whose model a slot holds takes the record (the
+      // plant state) and its timestamp from that slot
       F.slot = -1;
-      if (s.hot_m) {
+      F.pslot = -1;
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if (act && s.hot_m[(size_t)j * s.n + c] == m) F.slot = j;
+      for (int j = 0; j < 4; ++j) {
+        if (act && __builtin_amdgcn_readlane(tag, j) == m) F.slot = j;
+        if (act && __builtin_amdgcn_readlane(tag, 4 + j) == m) F.pslot = j;
       }
       const int *tp = F.slot >= 0 ? s.hot_ts + (size_t)F.slot * s.n + c : s.ts_ekf + c * NM + mm;
+      const int *tq = F.pslot >= 0 ? s.hotp_ts + (size_t)F.pslot * s.n + c : s.ts_plant + c * NM + mm;
       // MB never time-updates the per-model EKF records (iterEKF.m:90-102)
       F.tse = (act && !(cf.flags & KF_MB)) ? *tp : t;
-      F.tsp = act ? s.ts_plant[c * NM + m] : t;
+      F.tsp = act ? *tq : t;
+      // one code path for record and slot: a per-lane pointer that steps by the pair stride (1 on
+      // a record, n in a window), an add per pair and no per-lane multiply
       const double2 *re = reinterpret_cast<const double2 *>(F.slot >= 0 ? hot_slot(s, F.slot, c)
                                                                         : s.ekf + ((size_t)c * NM + mm) * REC);
-      const size_t rst = F.slot >= 0 ? (size_t)s.n : 1;
-      const double2 *rp = reinterpret_cast<const double2 *>(s.bigx + ((size_t)c * NM + mm) * 6);
+      const double2 *rp = reinterpret_cast<const double2 *>(F.pslot >= 0 ? hotp_slot(s, F.pslot, c)
+                                                                         : s.bigx + ((size_t)c * NM + mm) * 6);
+      const size_t rst = F.slot >= 0 ? (size_t)s.n : 1, pst = F.pslot >= 0 ? (size_t)s.n : 1;
 #pragma unroll
-      for (int e = 0; e < REC / 2; ++e) {
-        const double2 v = re[e * rst];
+      for (int e = 0; e < REC / 2; ++e, re += rst) {
+        const double2 v = *re;
         F.xe[2 * e] = v.x;
         F.xe[2 * e + 1] = v.y;
       }
 #pragma unroll
-      for (int e = 0; e < 3; ++e) {
-        const double2 v = rp[e];
+      for (int e = 0; e < 3; ++e, rp += pst) {
+        const double2 v = *rp;
         F.xp[2 * e] = v.x;
         F.xp[2 * e + 1] = v.y;
       }
     };
     FCell cur;
-    if (c_lo + w0 < c_hi) fload(c_lo + w0, cur);
+    int tagn = -1;  // the tags of the cell the next fload takes
+    if (c_lo + w0 < c_hi) {
+      fload(c_lo + w0, cur, ftag(c_lo + w0));
+      if (c_lo + w0 + nw < c_hi) tagn = ftag(c_lo + w0 + nw);
+    }
     for (int64_t c = c_lo + w0; c < c_hi; c += nw) {
       FCell nx;
-      if (c + nw < c_hi) fload(c + nw, nx);
+      if (c + nw < c_hi) {
+        const int tag = tagn;
+        if (c + 2 * nw < c_hi) tagn = ftag(c + 2 * nw);
+        fload(c + nw, nx, tag);
+      }
       const double hpl = cur.hpl, hul = cur.hul;
       const int tse = cur.tse, tsp = cur.tsp;
       double2 *re = reinterpret_cast<double2 *>(s.ekf + ((size_t)c * NM + mm) * REC);
@@ -1686,7 +1722,9 @@ __global__ void __launch_bounds__(256) k_flush(const KRom r, const KCfg cf, cons
         for (int e = 0; e < REC / 2; ++e) re[e] = make_double2(xe[2 * e], xe[2 * e + 1]);
       }
       if (cur.slot >= 0) s.hot_m[(size_t)cur.slot * s.n + c] = -1;
-      if (tsp < t) {
+      // the same for a plant state held in the plant window
+      if (cur.pslot >= 0) s.hotp_m[(size_t)cur.pslot * s.n + c] = -1;
+      if (tsp < t || cur.pslot >= 0) {
 #pragma unroll
         for (int e = 0; e < 3; ++e) rp[e] = make_double2(xp[2 * e], xp[2 * e + 1]);
       }
@@ -1990,13 +2028,42 @@ __device__ __forceinline__ double cell_plant(const KRom &r, const KState &s, con
   int mm[4];
   corner_models(r, pc, mm);
   double *bx = s.bigx + (size_t)c * r.NM * 6;
+  // The plant window (KState::hotp_*), as k_cell's corner window for the EKF
+  // records.  hot: this step's four states go to slots 0..3 (a cell with a repeated corner keeps
+  // the record path).  hit: slot j already holds corner j's model for all four, so they are read
+  // from there as well.  Any other lane first writes every held slot back to bigx / ts_plant and
+  // reads its states there (a model that moves between slots at a crossing goes through its
+  // record).  One code path below: a per-lane base pointer and pair stride.
+  const size_t hn = (size_t)s.n;
+  bool hot = false, hit = false;
+  if (s.hotp_m != nullptr && lazy_t != 0) {
+    int hm[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) hm[j] = s.hotp_m[j * hn + c];
+    hot = pc.iZu != pc.iZl && pc.iTu != pc.iTl;  // four distinct models
+    hit = hot && hm[0] == mm[0] && hm[1] == mm[1] && hm[2] == mm[2] && hm[3] == mm[3];
+    if (!hit) {
+#pragma unroll 1
+      for (int j = 0; j < 4; ++j) {
+        const int mh = s.hotp_m[j * hn + c];
+        if (mh < 0) continue;
+        double xh[6];
+        load_corner(hotp_slot(s, j, c), xh, hn);
+        store_corner(bx + (size_t)mh * 6, xh);
+        s.ts_plant[c * r.NM + mh] = s.hotp_ts[j * hn + c];
+        if (!hot) s.hotp_m[j * hn + c] = -1;
+      }
+    }
+  }
+  const size_t rst = hit ? hn : 1;  // pair stride of the four states' loads
+  const size_t wst = hot ? hn : 1;  // and of their stores
   // the 4 corner states as of step t-1: all loads before any store (duplicate corners)
   double xs[4][6];
   int tsj[4] = {0, 0, 0, 0};
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    load_corner(bx + (size_t)mm[j] * 6, xs[j]);
-    if (lazy_t) tsj[j] = s.ts_plant[c * r.NM + mm[j]];
+    load_corner(hit ? hotp_slot(s, j, c) : bx + (size_t)mm[j] * 6, xs[j], rst);
+    if (lazy_t) tsj[j] = *(hit ? s.hotp_ts + j * hn + c : s.ts_plant + c * r.NM + mm[j]);
   }
   // the per-cell scalar chain while the corner gathers are in flight
   plant_soc_step(r, et, SOC0n, SOC0p, Iapp, SOCnAvg, SOCpAvg);
@@ -2026,11 +2093,19 @@ __device__ __forceinline__ double cell_plant(const KRom &r, const KState &s, con
   if (lazy_t) {  // advance the corners through step t in place
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      if (tsj[j] >= lazy_t) continue;
+      if (tsj[j] >= lazy_t) {
+        // nothing to store: a slot that did not hold this corner stays empty (its state is in
+        // bigx, where the lane read it), one that did keeps what it holds
+        if (hot && !hit) s.hotp_m[j * hn + c] = -1;
+        continue;
+      }
       double x[6];
       plant_advance<false>(L + mm[j] * stride + OA, xs[j], Iapp, x);
-      store_corner(bx + (size_t)mm[j] * 6, x);
-      s.ts_plant[c * r.NM + mm[j]] = lazy_t;
+      // to window slot j with tag mm[j] and timestamp lazy_t (a hit rewrites no tag and touches
+      // no ts_plant), or to the record
+      store_corner(hot ? hotp_slot(s, j, c) : bx + (size_t)mm[j] * 6, x, wst);
+      *(hot ? s.hotp_ts + j * hn + c : s.ts_plant + c * r.NM + mm[j]) = lazy_t;
+      if (hot && !hit) s.hotp_m[j * hn + c] = mm[j];
     }
   }
   return V;

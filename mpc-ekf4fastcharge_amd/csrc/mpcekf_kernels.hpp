@@ -115,10 +115,18 @@ struct KState {
   // its copy in ekf / ts_ekf is then stale.  k_flush leaves every slot empty.
   double *hot_rec;           // [4][REC / 2][n] pairs of doubles (element e of slot j: pair e / 2)
   int *hot_m, *hot_ts;       // [4][n] the model a slot holds (-1: empty) and its timestamp
+  // the plant window (the same for the plant's four corner states, with tags of its own: the
+  // plant takes its corners from the true SOC and T, the EKF from the estimate; all null: no
+  // window).  Model m's plant state and timestamp are in slot j iff hotp_m[j][c] == m; its
+  // copy in bigx / ts_plant is then stale.  k_flush leaves every slot empty.
+  double *hotp_x;            // [4][3][n] pairs of doubles (pair e of slot j: states 2 e, 2 e + 1)
+  int *hotp_m, *hotp_ts;     // [4][n] the model a slot holds (-1: empty) and its timestamp
 };
 // a record in the corner window: HOT_PAIRS double2 per slot, pair e of slot j of cell c at
 // hot_rec2[(j * HOT_PAIRS + e) * n + c]
 constexpr int HOT_PAIRS = REC / 2;
+// a state in the plant window: pair e of slot j of cell c at hotp_x2[(j * HOTP_PAIRS + e) * n + c]
+constexpr int HOTP_PAIRS = 3;
 
 // mpcekf_plant_step_obs: the obs blob, the record and where each permuted row goes.
 // Blob: per model nz rows of OBS_ROW doubles [C 5][res0][D][0] in the permuted row order
