@@ -574,6 +574,58 @@ int mpcekf_thermal_end(mpcekf_ctx *ctx);
 int mpcekf_step_ex_thermal(mpcekf_ctx *ctx, int32_t nsteps, const mpcekf_traj *traj, const int32_t *slots,
                            int32_t nslots, double *obs, double *temp, double *heat, int32_t outputs_on_device);
 
+/* ---- the MPC limits scheduled over the model's temperature (not part of the reference interface) ----
+ * runMPC.m:30-44 sets the controller's limits once.  A battery management system derates them
+ * over temperature: the allowed C-rate falls as the cell warms, the plating margin rises when it
+ * is cold.  A schedule is a set of tables of limit fields over a uniform temperature grid,
+ * evaluated per cell on the device in every fused step, so the limits the MPC stage reads follow
+ * the temperature the thermal model computes -- inside one fused call, graph replay and
+ * mpcekf_step_summary included.  It goes through the existing current, voltage and eta blocks of
+ * constraintsMPC.m and changes no QP structure; there is no T_max row in the stack.
+ *
+ * fields[nfields]: distinct ids among MPCEKF_LIM_CRATE, _U_MAX, _DU_MIN, _DU_MAX, _V_MAX,
+ * _PHISE_MIN (the fields whose kernel slot is one number; TARGET_SOC, Z_MAX, Z_TOL cannot be
+ * scheduled).  tables [nsets][nfields][ntab] in mpcekf_config's units: entry k of a table is the
+ * field's value at T_lo + k (T_hi - T_lo) / (ntab - 1) degC.  set_of_cell [ncells] gives each
+ * cell its table set 0..nsets-1 (one batch sweeps several derating maps); NULL: set 0.
+ *
+ * For every fused step t and every cell, the MPC stage of step t reads, for each scheduled field,
+ * the table value at the temperature step t used: temp[t] of mpcekf_step_ex_thermal, the cell
+ * temperature as the step finds it -- the first step of a call after mpcekf_init_cells, after a
+ * mpcekf_thermal_begin with t0, or after a stage call's temperature argument included.  Fields not
+ * scheduled keep what mpcekf_set_limits stored, or the configuration's scalar.  Per cell and
+ * field, every line one or more separately rounded fp64 operations in exactly this order (no
+ * contraction, IEEE division), the shape of the model's open-circuit voltage lookup:
+ *   x   = (T - T_lo) / (T_hi - T_lo)
+ *   xc  = x > 0 ? x : 0;   xc = xc < 1 ? xc : 1             (a NaN x gives 0)
+ *   s   = xc * (double)(ntab - 1);   j = min((int)s, ntab - 2);   f = s - (double)j
+ *   val = tab[j] + f * (tab[j+1] - tab[j])
+ * The kernels' slot is formed from val by the expression the scalar configuration goes through
+ * (u_min = -Q * val for CRATE, val itself for the others), so a table constant at the
+ * configuration's value feeds the MPC kernels the scalar's bits.
+ *
+ * Needs a model: MPCEKF_E_STATE before mpcekf_thermal_begin.  Setting a schedule moves the
+ * context to the per-cell launch sequence if it is not there already, and
+ * evaluates the schedule once at the temperatures as they stand.  A second call replaces the
+ * schedule (fields of the first that the second does not name go back to their mpcekf_set_limits
+ * / configuration values); captured graphs stay valid.  While a schedule is active,
+ * mpcekf_get_limits returns for a scheduled field the value in force after the last evaluation
+ * (after a fused call: what its last step used); mpcekf_set_limits naming a scheduled field
+ * returns MPCEKF_E_ARG and mpcekf_clear_limits returns MPCEKF_E_STATE, both changing nothing.
+ * The stage route (mpcekf_mpc_step(_ex), mpcekf_mpc_diag) does not evaluate the schedule, as it
+ * does not advance the model: it reads the values of the last evaluation.  The schedule's kernels
+ * are not among mpcekf_set_timing's five slots.
+ * MPCEKF_E_ARG (nothing changed): a NULL ctx, fields or tables; nfields outside 1..6; a repeated
+ * id or one that cannot be scheduled; ntab < 2; T_lo or T_hi not finite, or T_hi <= T_lo; a
+ * non-finite table entry; nsets < 1; a set_of_cell entry outside 0..nsets-1 (the message names
+ * the cell). */
+int mpcekf_thermal_schedule(mpcekf_ctx *ctx, int32_t nfields, const int32_t *fields, int32_t ntab, double T_lo_degC,
+                            double T_hi_degC, int32_t nsets, const double *tables, const int32_t *set_of_cell);
+/* Ends the schedule: its fields go back to what mpcekf_set_limits or the configuration last gave
+ * them, and the launch sequence stays per-cell only if a mpcekf_set_limits is still in force.
+ * mpcekf_thermal_end does the same implicitly.  A no-op without a schedule. */
+int mpcekf_thermal_schedule_end(mpcekf_ctx *ctx);
+
 /* ---- device memory (not part of the reference interface) ----
  * Device buffers for outputs_on_device calls, allocated by the library's own HIP
  * runtime so a host process never holds a second one (a framework's bundled

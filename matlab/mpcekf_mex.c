@@ -73,6 +73,14 @@
  *   [u,v,soc,phise,nexec,temp,heat] = mpcekf_mex('stepthermal', h, nsteps)   mpcekf_step_ex_thermal
  *                       'step' on a context with a thermal model, plus the temperature each
  *                       step used and the heat it generated (W), ncells x nsteps
+ *                       mpcekf_mex('thermalschedule', h, idx, T_lo, T_hi, tables, sets)   mpcekf_thermal_schedule
+ *                       MPC limits that follow the model's temperature.  idx: 1-based field numbers
+ *                       as in 'setlimits', each once, among 2 Crate, 3 u_max, 4 du_min, 5 du_max,
+ *                       6 v_max, 7 phise_min; T_lo < T_hi: the uniform grid's ends (degC); tables:
+ *                       ntab x numel(idx) x nsets (or ntab x numel(idx)*nsets), ntab >= 2, column
+ *                       (j, s) = field idx(j) of derating map s over the grid; sets: [] (map 1) or
+ *                       ncells 1-based map numbers.  'getlimits' then returns the values in force
+ *                       mpcekf_mex('thermalscheduleend', h)            mpcekf_thermal_schedule_end
  * Per-cell vectors are 1 x ncells or ncells x 1; zk / zbk are (nz+2) x ncells, xm / xg
  * 4 x ncells (xm: 0-based model index t*nZ+z), lin 35 x ncells -- MATLAB's column-major
  * k x ncells is the library's cell-major [ncells][k], so no copy is made for them.
@@ -388,7 +396,8 @@ static void gateway(mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
                                             "graph", "mpcdiag", "get_state", "set_state", "scalars", "linfields",
                                             "plantobs", "obsslots", "obslayout", "stepobs", "setlimits", "getlimits",
                                             "clearlimits", "summarybegin", "stepsummary", "getsummary", "summaryend",
-                                            "thermalbegin", "thermalget", "thermalend", "stepthermal"};
+                                            "thermalbegin", "thermalget", "thermalend", "stepthermal",
+                                            "thermalschedule", "thermalscheduleend"};
   int known = 0;
   for (size_t i = 0; i < sizeof with_handle / sizeof *with_handle; ++i) known = known || !strcmp(cmd, with_handle[i]);
   if (!known) mexErrMsgIdAndTxt("mpcekf:arg", "unknown command %s", cmd);
@@ -484,6 +493,48 @@ static void gateway(mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
     if (!(nsd >= 0 && nsd <= 2147483647.0) || nsd != (double)(int32_t)nsd)
       mexErrMsgIdAndTxt("mpcekf:arg", "nsteps: expected a non-negative integer");
     thsteps = (int32_t)nsd;
+  }
+  /* the schedule commands likewise: output count, field numbers among the schedulable ones,
+     each once, grid ends that are real scalars, tables of ntab >= 2 rows and a whole number of
+     maps, set numbers that are 1-based integers */
+  const int thsched = !strcmp(cmd, "thermalschedule");
+  int32_t schf[MPCEKF_NLIM];
+  size_t nschf = 0, schtab = 0, schsets = 0;
+  double sch_lo = 0, sch_hi = 0;
+  if ((thsched || !strcmp(cmd, "thermalscheduleend")) && g_nlhs > 0) mexErrMsgIdAndTxt("mpcekf:arg", "%s: no output", cmd);
+  if (thsched) {
+    need(nrhs, 6, "'thermalschedule', h, idx, T_lo, T_hi, tables[, sets]");
+    nschf = mxGetNumberOfElements(prhs[2]);
+    if (nschf < 1 || nschf > 6) mexErrMsgIdAndTxt("mpcekf:arg", "thermalschedule: idx: expected 1..6 field numbers");
+    const double *idx = dvec(prhs[2], nschf, "idx");
+    unsigned seen = 0;
+    for (size_t j = 0; j < nschf; ++j) {
+      if (!(idx[j] >= MPCEKF_LIM_CRATE + 1 && idx[j] <= MPCEKF_LIM_PHISE_MIN + 1) || idx[j] != (double)(int)idx[j])
+        mexErrMsgIdAndTxt("mpcekf:arg", "thermalschedule: idx(%zu) = %g is not a field that can be scheduled (%d..%d)", j + 1,
+                          idx[j], (int)MPCEKF_LIM_CRATE + 1, (int)MPCEKF_LIM_PHISE_MIN + 1);
+      schf[j] = (int32_t)idx[j] - 1;
+      if (seen >> schf[j] & 1) mexErrMsgIdAndTxt("mpcekf:arg", "thermalschedule: idx(%zu) = %g is given twice", j + 1, idx[j]);
+      seen |= 1u << schf[j];
+    }
+    sch_lo = scalar(prhs[3], "thermalschedule: T_lo");
+    sch_hi = scalar(prhs[4], "thermalschedule: T_hi");
+    if (!mxIsDouble(prhs[5]) || mxIsComplex(prhs[5]) || mxIsEmpty(prhs[5]))
+      mexErrMsgIdAndTxt("mpcekf:arg", "thermalschedule: tables: expected a real double ntab x %zu x nsets array", nschf);
+    schtab = mxGetM(prhs[5]);
+    const size_t cols = mxGetNumberOfElements(prhs[5]) / schtab;
+    if (schtab < 2 || schtab > 2147483647.0 || cols % nschf != 0 || cols / nschf > 2147483647.0)
+      mexErrMsgIdAndTxt("mpcekf:arg", "thermalschedule: tables: %zu x %zu: expected ntab >= 2 rows and %zu columns per map",
+                        schtab, cols, nschf);
+    schsets = cols / nschf;
+    if (nrhs > 6 && !mxIsEmpty(prhs[6])) {
+      if (!mxIsDouble(prhs[6]) || mxIsComplex(prhs[6]))
+        mexErrMsgIdAndTxt("mpcekf:arg", "thermalschedule: sets: expected [] or ncells real doubles");
+      const size_t k = mxGetNumberOfElements(prhs[6]);
+      const double *sd = mxGetDoubles(prhs[6]);
+      for (size_t j = 0; j < k; ++j)
+        if (!(sd[j] >= 1 && sd[j] <= (double)schsets) || sd[j] != (double)(int32_t)sd[j])
+          mexErrMsgIdAndTxt("mpcekf:arg", "thermalschedule: sets(%zu) = %g is not a map 1..%zu", j + 1, sd[j], schsets);
+    }
   }
   mpcekf_ctx *h = handle(prhs[1]);
   int64_t n = 0;
@@ -696,6 +747,20 @@ static void gateway(mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
     tr.u = mxGetDoubles(plhs[0]); tr.v = mxGetDoubles(plhs[1]); tr.soc = mxGetDoubles(plhs[2]);
     tr.phise = mxGetDoubles(plhs[3]); tr.nexec = (int32_t *)mxGetData(plhs[4]);
     chk(mpcekf_step_ex_thermal(h, thsteps, &tr, NULL, 0, NULL, mxGetDoubles(plhs[5]), mxGetDoubles(plhs[6]), 0));
+  } else if (thsched) {
+    /* ntab x numel(idx) x nsets column-major is the library's [nsets][nfields][ntab] as it stands */
+    int32_t *set = NULL;
+    if (nrhs > 6 && !mxIsEmpty(prhs[6])) {
+      const double *sd = dvec(prhs[6], nc, "thermalschedule: sets (ncells)");
+      set = (int32_t *)mxMalloc(nc * sizeof(int32_t) + 8);
+      for (size_t c = 0; c < nc; ++c) set[c] = (int32_t)sd[c] - 1;
+    }
+    const int rc = mpcekf_thermal_schedule(h, (int32_t)nschf, schf, (int32_t)schtab, sch_lo, sch_hi, (int32_t)schsets,
+                                           mxGetDoubles(prhs[5]), set);
+    if (set) mxFree(set);
+    chk(rc);
+  } else if (!strcmp(cmd, "thermalscheduleend")) {
+    chk(mpcekf_thermal_schedule_end(h));
   } else if (!strcmp(cmd, "mpcdiag")) {
     need(nrhs, 3, "'mpcdiag', h, lin[, uk_1]");
     plhs[0] = mxCreateDoubleMatrix(7, (mwSize)nc, mxCOMPLEX);  /* interleaved (re, im): [ncells][7][2] */

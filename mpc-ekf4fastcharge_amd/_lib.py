@@ -32,6 +32,8 @@ SUMMARY_FIELDS = ("seen", "steps", "err_step", "t_reach", "u_min", "u_min_step",
 SUM_WIN = 64     # MPCEKF_SUM_WIN
 # MPCEKF_TH_* / MPCEKF_THR_*: the lumped thermal model's parameters and record (mpcekf_thermal_begin / _get)
 THERMAL_PARAMS = ("Cth", "Rth", "Tamb")
+# the limit fields mpcekf_thermal_schedule takes (the ones whose kernel slot is one number)
+SCHEDULE_FIELDS = ("Crate", "u_max", "du_min", "du_max", "v_max", "phise_min")
 THERMAL_FIELDS = ("T", "T_max", "T_max_step", "T_min", "heat_sum", "steps", "nheld")
 
 _dp = C.POINTER(C.c_double)
@@ -96,6 +98,7 @@ EXPORTS = [
     "mpcekf_set_limits", "mpcekf_get_limits", "mpcekf_clear_limits",
     "mpcekf_summary_begin", "mpcekf_step_summary", "mpcekf_get_summary", "mpcekf_summary_end",
     "mpcekf_thermal_begin", "mpcekf_thermal_get", "mpcekf_thermal_end", "mpcekf_step_ex_thermal",
+    "mpcekf_thermal_schedule", "mpcekf_thermal_schedule_end",
     # the _async stage twins (include/mpcekf.h)
     "mpcekf_plant_step_async", "mpcekf_ekf_step_async", "mpcekf_linearize_async", "mpcekf_lin_fields_async",
     "mpcekf_mpc_step_async", "mpcekf_mpc_step_ex_async", "mpcekf_mpc_diag_async", "mpcekf_get_scalars_async",
@@ -172,6 +175,8 @@ def load():
     L.mpcekf_thermal_begin.argtypes = [vp, _dp, C.c_int32, _dp, _dp]
     L.mpcekf_thermal_get.argtypes = [vp, C.c_int32, _ip, _dp]
     L.mpcekf_thermal_end.argtypes = [vp]
+    L.mpcekf_thermal_schedule.argtypes = [vp, C.c_int32, _ip, C.c_int32, C.c_double, C.c_double, C.c_int32, _dp, _ip]
+    L.mpcekf_thermal_schedule_end.argtypes = [vp]
     L.mpcekf_step_ex_thermal.argtypes = [vp, C.c_int32, C.POINTER(Traj), _ip, C.c_int32, vp, vp, vp, C.c_int32]
     for nm in ("plant_step", "ekf_step", "linearize", "lin_fields", "mpc_step", "mpc_step_ex", "mpc_diag",
                "get_scalars", "plant_step_obs", "plant_obs_slots"):   # the _async twins take the synchronous call's arguments

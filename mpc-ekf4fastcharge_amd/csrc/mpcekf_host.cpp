@@ -27,6 +27,7 @@
 #include "mpcekf_kernels.hpp"
 #include "mpcekf_summary.hpp"
 #include "mpcekf_thermal.hpp"
+#include "mpcekf_thermal_sched.hpp"
 
 using namespace mk;
 namespace mk {
@@ -236,9 +237,11 @@ struct mpcekf_ctx {
   // units (what mpcekf_get_limits returns; empty until the first set), d_lim [NLIMK][n] the
   // kernels' record, allocated by the first set and kept to the end (a captured graph may name
   // it).  percell: the MPC stages launch the per-cell kernel variants
+  // lim_set: a mpcekf_set_limits is in force; a temperature schedule (sched, below) keeps the
+  // context on the per-cell sequence too: percell = lim_set || sched
   std::vector<double> h_lim;
   double *d_lim = nullptr;
-  bool percell = false;
+  bool percell = false, lim_set = false;
   const double *lim() const { return percell ? d_lim : nullptr; }
   // mpcekf_summary_begin .. _end: the record [NSUM][n], the thresholds [n] and the window the
   // fused step's output rows land in during mpcekf_step_summary, SUM_WIN rows of u, v, soc,
@@ -253,6 +256,33 @@ struct mpcekf_ctx {
   // step ends with k_thermal.
   double *d_th = nullptr, *d_th_par = nullptr, *d_th_i = nullptr, *d_th_ocv = nullptr;
   int32_t th_nocv = 0;
+  // mpcekf_thermal_schedule .. _schedule_end: the header, each cell's table set [n] and the
+  // values in force [SCHED_MAXF][n] are allocated once; the tables [nsets][nf][ntab] grow on
+  // demand (sch_cap doubles).  sched: every fused call evaluates the schedule (h_sch: the
+  // header's host copy, row i of d_sch_val = field h_sch_field[i])
+  SchedHdr *d_sch_hdr = nullptr;
+  double *d_sch_tab = nullptr, *d_sch_val = nullptr;
+  int *d_sch_set = nullptr;
+  size_t sch_cap = 0;
+  bool sched = false;
+  SchedHdr h_sch{};
+  int32_t h_sch_field[SCHED_MAXF] = {};
+  int sched_row(int field) const {  // the row of a scheduled field, -1: not scheduled
+    for (int i = 0; sched && i < h_sch.nf; ++i)
+      if (h_sch_field[i] == field) return i;
+    return -1;
+  }
+  KSched ksched() const {
+    KSched g{};
+    g.hdr = d_sch_hdr;
+    g.tab = d_sch_tab;
+    g.set = d_sch_set;
+    g.Tc = s.Tc;
+    g.lim = d_lim;
+    g.val = d_sch_val;
+    g.n = n;
+    return g;
+  }
   double *d_uk1p = nullptr;                      // [n] uk_1 before the step (poles / sv)
   int flush_period = LAZY_H;      // steps between all-model flushes (<= LAZY_H)
   // rolling flush (MPCEKF_FLUSH_ROLL=1, off by default): step t flushes the cell slice
@@ -1167,7 +1197,7 @@ int mpcekf_ctx_destroy(mpcekf_ctx *X) {
                   X->d_zbk,       X->d_tmp,        X->s.bigx, X->s.ekf,   X->s.lam,   X->d_ts, X->d_hist, X->d_stamps, X->d_bnd, X->d_xm, X->d_xg,
                   X->w.prob, X->w.X, X->w.R, X->w.K, X->w.hii, X->w.it, X->w.smin, X->d_lin, X->d_zsoc, X->d_mb, X->d_uk1p,
                   X->w.q, X->w.list, X->w.hist, X->d_poly, X->d_szk, X->d_sxg, X->d_sxm, X->d_slin, X->d_sv, X->d_zslot,
-                  X->d_obs_blob, X->d_obs, X->d_obs_plan, X->d_lim, X->d_sum, X->d_sum_reach, X->d_sum_obs,
+                  X->d_obs_blob, X->d_obs, X->d_obs_plan, X->d_lim, X->d_sch_hdr, X->d_sch_tab, X->d_sch_val, X->d_sch_set, X->d_sum, X->d_sum_reach, X->d_sum_obs,
                   X->d_sum_ring, X->d_th, X->d_th_par, X->d_th_i, X->d_th_ocv, X->d_hot, X->d_hot_i, X->d_hotp, X->d_hotp_i};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
@@ -1427,7 +1457,12 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
   const int hstart = side ? 7 : 3;  // the event that opens the Hildreth interval
   const int P = X->flush_period;
   std::vector<char> flushed((size_t)nsteps, 0);
+  const bool sched = thermal && X->sched;
+  const KSched ksch = X->ksched();
   auto run_steps = [&]() -> int {
+    // the schedule at the temperature the call's first step finds (mpcekf_thermal_sched.hip);
+    // before the first timing event, so no slot of mpcekf_set_timing counts it
+    if (sched && nsteps > 0 && (rc = lerr(launch_sched(ksch, X->stream), "sched"))) return rc;
     for (int k = 0; k < nsteps; ++k) {
       const int t = k + 1;
       // sampled steps: every timing_every-th (k = every-1, 2 every-1, ...: with every dividing
@@ -1604,7 +1639,12 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
         q.th0n = X->r.th0n;
         q.th100n = X->r.th100n;
         q.Ts = X->r.Ts;
-        if ((rc = lerr(launch_thermal(q, X->stream), "thermal"))) return rc;
+        // a schedule: the next step's limits at the temperature this launch leaves
+        if (sched && k + 1 < nsteps) {
+          if ((rc = lerr(launch_thermal_sched(q, ksch, X->stream), "thermal_sched"))) return rc;
+        } else if ((rc = lerr(launch_thermal(q, X->stream), "thermal"))) {
+          return rc;
+        }
       }
     }
     return MPCEKF_OK;
@@ -1621,6 +1661,10 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
     key.push_back((uintptr_t)X->s.hot_rec);  // the corner window the captured kernels name (null: none)
     key.push_back((uintptr_t)X->s.hotp_x);   // and the plant window
     for (int i = 0; i < nslots; ++i) key.push_back((uintptr_t)slots[i]);
+    // the schedule's launches are part of the graph: its header (0 without a schedule) and its
+    // tables, which mpcekf_thermal_schedule may regrow
+    key.push_back((uintptr_t)(sched ? X->d_sch_hdr : nullptr));
+    key.push_back((uintptr_t)(sched ? X->d_sch_tab : nullptr));
     // the thermal state (its temp / heat rows are among the output rows above): third from the
     // end, 0 on a context without a model -- mpcekf_thermal_end retires the graphs that name one
     key.push_back((uintptr_t)X->d_th_ocv);
@@ -1734,14 +1778,10 @@ static int check_limit_fields(const char *who, int32_t nfields, const int32_t *f
   return MPCEKF_OK;
 }
 
-int mpcekf_set_limits(mpcekf_ctx *X, int32_t nfields, const int32_t *fields, const double *values) {
-  if (!X) return fail(MPCEKF_E_ARG, "set_limits: null ctx");
-  int rc = check_limit_fields("set_limits", nfields, fields);
-  if (rc) return rc;
-  if (!values) return fail(MPCEKF_E_ARG, "set_limits: null values");
-  // check_cfg puts no condition on the scalar form of any of these fields, so none is put on
-  // an element either (a negative du_max is a legitimate configuration)
-  HIPCHK(hipSetDevice(X->device));
+// The limits record's buffers and the host copy of the values (the configuration's scalars until
+// a set names a field): what the first mpcekf_set_limits or mpcekf_thermal_schedule needs.
+static int limits_bufs(mpcekf_ctx *X) {
+  int rc;
   const size_t n = (size_t)X->n;
   if (!X->d_lim && (rc = dalloc(&X->d_lim, std::max<size_t>(n, 1) * NLIMK))) return rc;
   // the split route's hand-off k_cell<P_EKF | P_LIN> -> k_mpc_pc (a switched or wide context has it)
@@ -1751,9 +1791,15 @@ int mpcekf_set_limits(mpcekf_ctx *X, int32_t nfields, const int32_t *fields, con
     X->h_lim.resize((size_t)MPCEKF_NLIM * n);
     for (int f = 0; f < MPCEKF_NLIM; ++f) std::fill_n(X->h_lim.begin() + (size_t)f * n, n, cfg_limit(X->cfg, f));
   }
-  for (int i = 0; i < nfields; ++i) std::copy_n(values + (size_t)i * n, n, X->h_lim.begin() + (size_t)fields[i] * n);
-  // the kernels' record by fill_kcfg's expressions: an array constant at the configuration's
-  // value gives the scalar's bits
+  return MPCEKF_OK;
+}
+
+// h_lim -> the kernels' record by fill_kcfg's expressions (an array constant at the
+// configuration's value gives the scalar's bits), then, with a schedule, its fields at every
+// cell's temperature as it stands.  Waits for the stream.
+static int limits_upload(mpcekf_ctx *X) {
+  int rc;
+  const size_t n = (size_t)X->n;
   std::vector<double> rec((size_t)NLIMK * n);
   const double *h = X->h_lim.data();
   const double Q = X->r.Q;
@@ -1769,8 +1815,28 @@ int mpcekf_set_limits(mpcekf_ctx *X, int32_t nfields, const int32_t *fields, con
   }
   // on the context's stream, after every launch already queued; the wait makes rec's lifetime safe
   if (n) HIPCHK(hipMemcpyAsync(X->d_lim, rec.data(), rec.size() * 8, hipMemcpyHostToDevice, X->stream));
+  if (X->sched && (rc = lerr(launch_sched(X->ksched(), X->stream), "sched"))) return rc;
   HIPCHK(hipStreamSynchronize(X->stream));
-  X->percell = true;
+  return MPCEKF_OK;
+}
+
+int mpcekf_set_limits(mpcekf_ctx *X, int32_t nfields, const int32_t *fields, const double *values) {
+  if (!X) return fail(MPCEKF_E_ARG, "set_limits: null ctx");
+  int rc = check_limit_fields("set_limits", nfields, fields);
+  if (rc) return rc;
+  if (!values) return fail(MPCEKF_E_ARG, "set_limits: null values");
+  for (int i = 0; i < nfields; ++i)
+    if (X->sched_row(fields[i]) >= 0)
+      return fail(MPCEKF_E_ARG, "set_limits: fields[%d] = %d is scheduled over temperature (mpcekf_thermal_schedule)", i,
+                  fields[i]);
+  // check_cfg puts no condition on the scalar form of any of these fields, so none is put on
+  // an element either (a negative du_max is a legitimate configuration)
+  HIPCHK(hipSetDevice(X->device));
+  const size_t n = (size_t)X->n;
+  if ((rc = limits_bufs(X))) return rc;
+  for (int i = 0; i < nfields; ++i) std::copy_n(values + (size_t)i * n, n, X->h_lim.begin() + (size_t)fields[i] * n);
+  if ((rc = limits_upload(X))) return rc;
+  X->percell = X->lim_set = true;
   return MPCEKF_OK;
 }
 
@@ -1780,16 +1846,28 @@ int mpcekf_get_limits(mpcekf_ctx *X, int32_t nfields, const int32_t *fields, dou
   if (rc) return rc;
   if (!values) return fail(MPCEKF_E_ARG, "get_limits: null values");
   const size_t n = (size_t)X->n;
+  bool wait = false;
   for (int i = 0; i < nfields; ++i) {
-    if (X->percell) std::copy_n(X->h_lim.begin() + (size_t)fields[i] * n, n, values + (size_t)i * n);
-    else std::fill_n(values + (size_t)i * n, n, cfg_limit(X->cfg, fields[i]));
+    const int row = X->sched_row(fields[i]);
+    if (row >= 0) {  // a scheduled field: the value of the last evaluation, kept on the device
+      if (!wait) HIPCHK(hipSetDevice(X->device));
+      if (n) HIPCHK(hipMemcpyAsync(values + (size_t)i * n, X->d_sch_val + (size_t)row * n, n * 8, hipMemcpyDeviceToHost, X->stream));
+      wait = true;
+    } else if (X->percell) {
+      std::copy_n(X->h_lim.begin() + (size_t)fields[i] * n, n, values + (size_t)i * n);
+    } else {
+      std::fill_n(values + (size_t)i * n, n, cfg_limit(X->cfg, fields[i]));
+    }
   }
+  if (wait) HIPCHK(hipStreamSynchronize(X->stream));
   return MPCEKF_OK;
 }
 
 int mpcekf_clear_limits(mpcekf_ctx *X) {
   if (!X) return fail(MPCEKF_E_ARG, "clear_limits: null ctx");
-  X->percell = false;  // the buffers stay: a graph captured per-cell names d_lim until the context goes
+  if (X->sched)
+    return fail(MPCEKF_E_STATE, "clear_limits: a temperature schedule is active (mpcekf_thermal_schedule_end first)");
+  X->percell = X->lim_set = false;  // the buffers stay: a graph captured per-cell names d_lim until the context goes
   X->h_lim.clear();
   return MPCEKF_OK;
 }
@@ -1978,6 +2056,8 @@ int mpcekf_thermal_get(mpcekf_ctx *X, int32_t nfields, const int32_t *fields, do
 int mpcekf_thermal_end(mpcekf_ctx *X) {
   if (!X) return fail(MPCEKF_E_ARG, "thermal_end: null ctx");
   if (!X->d_th) return MPCEKF_OK;
+  int rc = mpcekf_thermal_schedule_end(X);  // the scheduled fields back to set_limits' / the configuration's values
+  if (rc) return rc;
   HIPCHK(hipSetDevice(X->device));
   HIPCHK(hipStreamSynchronize(X->stream));
   retire_thermal_graphs(X);
@@ -1986,6 +2066,98 @@ int mpcekf_thermal_end(mpcekf_ctx *X) {
     if (p) (void)hipFree(p);
   X->d_th = X->d_th_par = X->d_th_i = X->d_th_ocv = nullptr;
   X->th_nocv = 0;
+  return MPCEKF_OK;
+}
+
+// ---- the MPC limits scheduled over the model's temperature (mpcekf_thermal_sched.hip) ----
+int mpcekf_thermal_schedule(mpcekf_ctx *X, int32_t nfields, const int32_t *fields, int32_t ntab, double T_lo_degC,
+                            double T_hi_degC, int32_t nsets, const double *tables, const int32_t *set_of_cell) {
+  if (!X) return fail(MPCEKF_E_ARG, "thermal_schedule: null ctx");
+  if (nfields < 1 || nfields > SCHED_MAXF)
+    return fail(MPCEKF_E_ARG, "thermal_schedule: nfields = %d outside 1..%d", nfields, (int)SCHED_MAXF);
+  if (!fields) return fail(MPCEKF_E_ARG, "thermal_schedule: null fields");
+  if (!tables) return fail(MPCEKF_E_ARG, "thermal_schedule: null tables");
+  SchedHdr h{};
+  unsigned seen = 0;
+  for (int i = 0; i < nfields; ++i) {
+    int slot;
+    switch (fields[i]) {
+      case MPCEKF_LIM_CRATE: slot = LK_U_MIN; break;
+      case MPCEKF_LIM_U_MAX: slot = LK_U_MAX; break;
+      case MPCEKF_LIM_DU_MIN: slot = LK_DU_MIN; break;
+      case MPCEKF_LIM_DU_MAX: slot = LK_DU_MAX; break;
+      case MPCEKF_LIM_V_MAX: slot = LK_V_MAX; break;
+      case MPCEKF_LIM_PHISE_MIN: slot = LK_PHISE_MIN; break;
+      default:
+        return fail(MPCEKF_E_ARG, "thermal_schedule: fields[%d] = %d cannot be scheduled (CRATE, U_MAX, DU_MIN, DU_MAX, "
+                    "V_MAX, PHISE_MIN can)", i, fields[i]);
+    }
+    if (seen >> fields[i] & 1) return fail(MPCEKF_E_ARG, "thermal_schedule: fields: id %d given twice", fields[i]);
+    seen |= 1u << fields[i];
+    h.slot[i] = slot;
+    h.crate[i] = fields[i] == MPCEKF_LIM_CRATE;
+  }
+  if (ntab < 2) return fail(MPCEKF_E_ARG, "thermal_schedule: ntab = %d: a table needs 2 entries or more", ntab);
+  if (!std::isfinite(T_lo_degC) || !std::isfinite(T_hi_degC) || !(T_hi_degC > T_lo_degC))
+    return fail(MPCEKF_E_ARG, "thermal_schedule: grid [%g, %g] degC: finite ends with T_hi > T_lo", T_lo_degC, T_hi_degC);
+  if (nsets < 1) return fail(MPCEKF_E_ARG, "thermal_schedule: nsets = %d: 1 or more", nsets);
+  const size_t ntabs = (size_t)nsets * (size_t)nfields * (size_t)ntab;
+  for (size_t i = 0; i < ntabs; ++i)
+    if (!std::isfinite(tables[i]))
+      return fail(MPCEKF_E_ARG, "thermal_schedule: tables[%zu] = %g is not finite (set %zu, field %zu, entry %zu)", i,
+                  tables[i], i / ((size_t)nfields * ntab), i / ntab % nfields, i % ntab);
+  const size_t nc = (size_t)X->n;
+  for (size_t c = 0; set_of_cell && c < nc; ++c)
+    if (set_of_cell[c] < 0 || set_of_cell[c] >= nsets)
+      return fail(MPCEKF_E_ARG, "thermal_schedule: set_of_cell[%zu] = %d outside 0..%d", c, set_of_cell[c], nsets - 1);
+  if (!X->d_th) return fail(MPCEKF_E_STATE, "thermal_schedule: call mpcekf_thermal_begin first");
+  int rc;
+  HIPCHK(hipSetDevice(X->device));
+  const size_t n = std::max<size_t>(nc, 1);
+  // every buffer before anything is stored: a failed allocation leaves the schedule as it was
+  if (!X->d_sch_hdr && (rc = dalloc(&X->d_sch_hdr, 1))) return rc;
+  if (!X->d_sch_set && (rc = dalloc(&X->d_sch_set, n))) return rc;
+  if (!X->d_sch_val && (rc = dalloc(&X->d_sch_val, n * SCHED_MAXF))) return rc;
+  if (X->sch_cap < ntabs) {
+    double *t = nullptr;
+    if ((rc = dalloc(&t, ntabs))) return rc;
+    if (X->d_sch_tab) {  // no launch in flight reads the old tables, and no graph names them any more
+      HIPCHK(hipStreamSynchronize(X->stream));
+      retire_thermal_graphs(X);
+      (void)hipFree(X->d_sch_tab);
+    }
+    X->d_sch_tab = t;
+    X->sch_cap = ntabs;
+  }
+  if ((rc = limits_bufs(X))) return rc;
+  h.T_lo = T_lo_degC;
+  h.T_hi = T_hi_degC;
+  h.Q = X->r.Q;
+  h.nf = nfields;
+  h.ntab = ntab;
+  h.nsets = nsets;
+  X->h_sch = h;
+  std::copy_n(fields, nfields, X->h_sch_field);
+  HIPCHK(hipMemcpyAsync(X->d_sch_hdr, &X->h_sch, sizeof(SchedHdr), hipMemcpyHostToDevice, X->stream));
+  HIPCHK(hipMemcpyAsync(X->d_sch_tab, tables, ntabs * 8, hipMemcpyHostToDevice, X->stream));
+  if (nc && set_of_cell) HIPCHK(hipMemcpyAsync(X->d_sch_set, set_of_cell, nc * 4, hipMemcpyHostToDevice, X->stream));
+  if (nc && !set_of_cell) HIPCHK(hipMemsetAsync(X->d_sch_set, 0, nc * 4, X->stream));
+  // the record from the values set_limits or the configuration gave (a replaced schedule's fields
+  // go back to them), then the new schedule's fields at the temperatures as they stand
+  X->sched = true;
+  X->percell = true;
+  return limits_upload(X);
+}
+
+int mpcekf_thermal_schedule_end(mpcekf_ctx *X) {
+  if (!X) return fail(MPCEKF_E_ARG, "thermal_schedule_end: null ctx");
+  if (!X->sched) return MPCEKF_OK;
+  HIPCHK(hipSetDevice(X->device));
+  X->sched = false;  // the buffers stay: a graph captured with the schedule names them until thermal_end
+  X->h_sch.nf = 0;
+  if (X->lim_set) return limits_upload(X);  // the scheduled fields back to what set_limits gave them
+  X->percell = false;
+  X->h_lim.clear();
   return MPCEKF_OK;
 }
 

@@ -524,8 +524,69 @@ class Context:
         return {k: vals[i] for i, k in enumerate(names)}
 
     def thermal_end(self):
-        """Drop the thermal model (mpcekf_thermal_end): the cells keep their temperature."""
+        """Drop the thermal model (mpcekf_thermal_end): the cells keep their temperature; a
+        schedule over it ends too."""
         check(self.L.mpcekf_thermal_end(self.h))
+
+    SCHEDULE_FIELDS = _lib.SCHEDULE_FIELDS
+
+    @classmethod
+    def _schedule_arrays(cls, n, T_lo, T_hi, sets, tables):
+        """thermal_schedule's arguments -> (int32 ids [nf], float64 tables [nsets][nf][ntab],
+        int32 set_of_cell [n] or None).  ValueError for an unknown, repeated or unschedulable
+        field, no field at all, tables of different shapes, a table that is neither [ntab] nor
+        [nsets][ntab], or a ``sets`` that is not a length-n integer array: before any library
+        call.  The values themselves (grid ends, finiteness, set indices) are the library's to
+        check."""
+        if not tables:
+            raise ValueError(f"thermal_schedule: no field given (one of {cls.SCHEDULE_FIELDS})")
+        ids, tabs = [], []
+        for k, v in tables.items():
+            if k not in cls.LIMIT_FIELDS and k != "targetSOC":
+                raise ValueError(f"thermal_schedule: unknown field {k!r} (one of {cls.SCHEDULE_FIELDS})")
+            if k not in cls.SCHEDULE_FIELDS:
+                raise ValueError(f"thermal_schedule: field {k!r} cannot be scheduled (one of {cls.SCHEDULE_FIELDS})")
+            a = np.asarray(v, dtype=np.float64)
+            if a.ndim not in (1, 2):
+                raise ValueError(f"thermal_schedule: {k} must be a [ntab] or [nsets][ntab] table, got shape {a.shape}")
+            ids.append(cls.LIMIT_FIELDS.index(k))
+            tabs.append(a)
+        two = [a for a in tabs if a.ndim == 2]
+        nsets = two[0].shape[0] if two else 1
+        ntab = tabs[0].shape[-1]
+        for k, a in zip(tables, tabs):
+            if a.shape[-1] != ntab or (a.ndim == 2 and a.shape[0] != nsets):
+                raise ValueError(f"thermal_schedule: {k} has shape {a.shape}: every table is [{ntab}] or [{nsets}][{ntab}] here")
+        if nsets < 1 or ntab < 1:
+            raise ValueError(f"thermal_schedule: empty tables ({nsets} sets of {ntab} entries)")
+        # [nf][nsets][ntab] -> [nsets][nf][ntab]; a [ntab] table serves every set
+        tab = np.stack([np.broadcast_to(a, (nsets, ntab)) for a in tabs]).transpose(1, 0, 2)
+        soc = None
+        if sets is not None:
+            soc = np.asarray(sets)
+            if soc.shape != (n,) or not np.issubdtype(soc.dtype, np.integer):
+                raise ValueError(f"thermal_schedule: sets must be a length-{n} integer array, got shape {soc.shape} "
+                                 f"of {soc.dtype}")
+            soc = np.ascontiguousarray(soc, dtype=np.int32)
+        return np.asarray(ids, dtype=np.int32), np.ascontiguousarray(tab, dtype=np.float64), soc
+
+    def thermal_schedule(self, T_lo, T_hi, sets=None, **tables):
+        """Schedule MPC limits over the thermal model's temperature (mpcekf_thermal_schedule):
+        each keyword is a limit field's name as in set_limits (Crate, u_max, du_min, du_max,
+        v_max, phise_min; make_config's units) with a table over the uniform grid ``T_lo`` ..
+        ``T_hi`` (degC), [ntab] or, for several derating maps in one batch, [nsets][ntab] with
+        ``sets`` [ncells] naming each cell's map (None: map 0).  From then on the MPC stage of
+        every fused step reads, per cell, the table value at the temperature the step used
+        (clamped to the grid's ends, linear between knots); get_limits returns the values in
+        force.  Needs thermal_begin; a second call replaces the schedule."""
+        ids, tab, soc = self._schedule_arrays(self.n, T_lo, T_hi, sets, tables)   # ValueError before any library call
+        check(self.L.mpcekf_thermal_schedule(self.h, int(ids.size), iptr(ids), int(tab.shape[2]), float(T_lo),
+                                             float(T_hi), int(tab.shape[0]), dptr(tab), iptr(soc)))
+
+    def thermal_schedule_end(self):
+        """End the schedule (mpcekf_thermal_schedule_end): its fields go back to what set_limits
+        or the configuration gave them."""
+        check(self.L.mpcekf_thermal_schedule_end(self.h))
 
     def set_timing(self, enable=True):
         """enable: True/1 = every step; N > 1 = sample every N-th step (less perturbation)."""
@@ -869,6 +930,16 @@ def thermal_ocv(rom, n=101, T_degC=25.0):
                      for z in np.linspace(0.0, 1.0, int(n)).tolist()], dtype=np.float64)
 
 
+def _thermal_begin(ctx, thermal):
+    """runMPC's / run_summary's thermal dict: thermal_begin's keywords, plus an optional
+    "schedule": a dict of thermal_schedule's (T_lo, T_hi, sets and the tables)."""
+    kw = dict(thermal)
+    sched = kw.pop("schedule", None)
+    ctx.thermal_begin(**kw)
+    if sched:
+        ctx.thermal_schedule(**sched)
+
+
 def runMPC(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=None, obs=None, limits=None,
            thermal=None):
     """runMPC.m:72-112 for a batch of cells; returns trajectories [nsteps, ncells].
@@ -878,7 +949,9 @@ def runMPC(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=None,
     sweep: runMPC.m:30-44 per cell), set after init_cells and before the first step.
     thermal: a dict of Context.thermal_begin's keywords (Cth, Rth, Tamb, ocv, T0): the cells
     heat themselves (TC is the initial temperature; no tc_traj); adds out["temp"], out["heat"]
-    and out["thermal"], the model's record."""
+    and out["thermal"], the model's record.  thermal["schedule"]: a dict of
+    Context.thermal_schedule's arguments (T_lo, T_hi, sets, the tables): limits that follow the
+    cells' temperature; adds out["limits"], the values in force at the last step."""
     SOC0 = np.atleast_1d(np.asarray(SOC0, dtype=np.float64))
     n = ncells or SOC0.shape[0]
     with Context(rom, n, cfg, device) as ctx:
@@ -886,10 +959,12 @@ def runMPC(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=None,
         if limits:
             ctx.set_limits(**limits)
         if thermal:
-            ctx.thermal_begin(**thermal)
+            _thermal_begin(ctx, thermal)
         out = ctx.step(nsteps, tc=tc_traj, obs=obs, thermal=("temp", "heat") if thermal else None)
         if thermal:
             out["thermal"] = ctx.thermal_get()
+            if thermal.get("schedule"):
+                out["limits"] = ctx.get_limits()
         out["status"] = ctx.get_state()["status"]
         return out
 
@@ -901,7 +976,8 @@ def run_summary(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=
     (a protocol sweep); reach, obs: Context.summary_begin's; tc_traj [nsteps, ncells] (degC): a
     temperature profile; chunk: steps per step_summary call (default all at once; with tc_traj
     a chunk bounds the host array each call converts).  Neither host nor device memory grows
-    with nsteps.  thermal: as runMPC's (no tc_traj); adds "thermal", the model's record."""
+    with nsteps.  thermal: as runMPC's, its "schedule" included (no tc_traj); adds "thermal", the
+    model's record."""
     SOC0 = np.atleast_1d(np.asarray(SOC0, dtype=np.float64))
     n = ncells or SOC0.shape[0]
     nsteps = int(nsteps)
@@ -914,7 +990,7 @@ def run_summary(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=
         if limits:
             ctx.set_limits(**limits)
         if thermal:
-            ctx.thermal_begin(**thermal)
+            _thermal_begin(ctx, thermal)
         ctx.summary_begin(reach=reach, obs=obs)
         for k in range(0, nsteps, max(chunk, 1)):
             m = min(chunk, nsteps - k)
