@@ -626,6 +626,68 @@ int mpcekf_thermal_schedule(mpcekf_ctx *ctx, int32_t nfields, const int32_t *fie
  * mpcekf_thermal_end does the same implicitly.  A no-op without a schedule. */
 int mpcekf_thermal_schedule_end(mpcekf_ctx *ctx);
 
+/* ---- series strings: one current per pack string along the fused loop (not part of the reference interface) ----
+ * Cells in series carry one current, and a charger can only apply what the weakest cell of the
+ * string accepts.  With a pack, the cells' controllers stay their own and the library couples
+ * their commands on the device, once per fused step, after the QP has produced them:
+ * - A context with a pack has ncells = nstrings * S.  String g is the cells [g*S, (g+1)*S).
+ * - After fused step t has produced each cell's command u_c, the kernel picks one cell per
+ *   string, the limiter.
+ *   - u_c is what Hildreth, or the unconstrained path, stored into s.uk (MPCEKF_S_UK).  Charging
+ *     current is negative, initMPC.m:66-67.
+ *   - The limiter is the cell with the largest u_c among the cells whose u_c is not NaN.
+ *   - Comparison is by value, so -0.0 == +0.0.  Ties go to the lowest in-string index.
+ * - The string current m_g is the limiter's u_c, bit for bit.  Every cell of the string whose own
+ *   command is not NaN gets s.uk <- m_g and s.uk_1 <- m_g (MPCEKF_S_UK, MPCEKF_S_UK_1).
+ * - A cell whose command is NaN (error, lock-out) is excluded.  It keeps its NaN, and its s.uk_1
+ *   is not touched.
+ * - A string with no non-NaN command writes nothing.  Its limiter is -1.
+ * - The u row of the step (trajectory, device buffer, summary window) holds the applied current
+ *   m_g for the cells that received it.  Excluded cells keep their NaN.
+ * - Because u holds the applied current, three things see it without further change:
+ *   - k_summary's peak current and charge moved (mpcekf_step_summary);
+ *   - the thermal model's carried current, which k_thermal reads from s.uk after this kernel;
+ *   - the next step's uk_1, and the uk_1 copy that k_cl_diag uses (poles / sv).
+ * - Per-cell record, [ncells] each, accumulated over any number of calls and reset by begin,
+ *   every value a double, counts exact integers:
+ *   - NLIM: the number of steps this cell was its string's limiter.
+ *   - STEPS: the number of steps this cell had a non-NaN command.
+ *   - HEADROOM: the sequential sum in step order of m_g - u_c, one rounded subtraction and one
+ *     rounded addition per step, from +0.  Only finite terms are added.  The unit is A*steps: the
+ *     charging current the cell would have taken but did not.
+ * - S = 1 is the identity.  Such a context runs the same bits as one without a pack (the record
+ *   still counts: NLIM = STEPS, HEADROOM sums zeros).
+ * The pack is a property of the context, like the thermal model: mpcekf_step, _step_ex,
+ * _step_ex_obs, _step_ex_thermal, _step_summary and _step_ex_pack all run the pack step, graph
+ * replay included.  The stage route (mpcekf_mpc_step(_ex)) is not coupled: a host loop over the
+ * stage calls sees every cell's own command, as it does not advance the thermal model either.
+ * The pack's kernel is not one of mpcekf_set_timing's five slots.
+ * Not modelled: parallel groups, balancing or bypass currents, strings of unequal length, heat
+ * conduction between neighbouring cells. */
+enum { MPCEKF_PK_NLIM = 0, MPCEKF_PK_STEPS, MPCEKF_PK_HEADROOM, MPCEKF_NPK };
+/* Makes the context a pack of ncells / series strings of `series` cells each, allocates the
+ * record (first call) and resets it; a second begin replaces the first and resets the record.
+ * May be called before mpcekf_init_cells.
+ * MPCEKF_E_ARG (nothing changed): a NULL ctx, series < 1, ncells % series != 0. */
+int mpcekf_pack_begin(mpcekf_ctx *ctx, int32_t series);
+/* values [nfields][ncells]: row i = field fields[i] (distinct MPCEKF_PK_* ids).
+ * MPCEKF_E_STATE without a begin; MPCEKF_E_ARG: a NULL pointer, nfields outside
+ * 1..MPCEKF_NPK, an unknown or repeated id. */
+int mpcekf_pack_get(mpcekf_ctx *ctx, int32_t nfields, const int32_t *fields, double *values);
+/* Frees the record; the cells keep their state and the context then behaves as one that never
+ * began.  A no-op without a begin. */
+int mpcekf_pack_end(mpcekf_ctx *ctx);
+/* mpcekf_step_ex_obs (and, on a thermal context, mpcekf_step_ex_thermal: temp / heat, which
+ * must be NULL without a model -- MPCEKF_E_STATE -- as tc_degC must be NULL with one) on a
+ * pack context plus the pack's rows (host, or device when outputs_on_device != 0), either may
+ * be NULL: ucmd [nsteps][ncells], each cell's own command before the reduction (traj->u holds
+ * the applied current); limiter [nsteps][ncells / series], each string's limiter as an
+ * in-string index, or -1.  MPCEKF_E_STATE without a begin; a refused call leaves the context
+ * and the record as they were. */
+int mpcekf_step_ex_pack(mpcekf_ctx *ctx, int32_t nsteps, const double *tc_degC, const mpcekf_traj *traj,
+                        const int32_t *slots, int32_t nslots, double *obs, double *temp, double *heat, double *ucmd,
+                        int32_t *limiter, int32_t outputs_on_device);
+
 /* ---- device memory (not part of the reference interface) ----
  * Device buffers for outputs_on_device calls, allocated by the library's own HIP
  * runtime so a host process never holds a second one (a framework's bundled

@@ -81,6 +81,18 @@
  *                       (j, s) = field idx(j) of derating map s over the grid; sets: [] (map 1) or
  *                       ncells 1-based map numbers.  'getlimits' then returns the values in force
  *                       mpcekf_mex('thermalscheduleend', h)            mpcekf_thermal_schedule_end
+ *                       mpcekf_mex('packbegin', h, series)             mpcekf_pack_begin
+ *                       the cells form ncells / series strings of `series` cells in series (cells
+ *                       (g-1)*series+1 .. g*series are string g); from then on every 'step' /
+ *                       'stepobs' / 'stepsummary' / 'stepthermal' / 'stepexpack' applies to each
+ *                       cell its string's current, the largest command among the string's cells
+ *   s                 = mpcekf_mex('packget', h)                       mpcekf_pack_get
+ *                       struct of ncells x 1 column vectors: nlim, steps, headroom (MPCEKF_PK_*)
+ *                       mpcekf_mex('packend', h)                       mpcekf_pack_end
+ *   [u,v,soc,phise,nexec,ucmd,limiter] = mpcekf_mex('stepexpack', h, nsteps[, tc])   mpcekf_step_ex_pack
+ *                       'step' on a pack context (u: the applied current), plus each cell's own
+ *                       command, ncells x nsteps, and each string's limiter, nstrings x nsteps
+ *                       int32, the 1-based in-string index or 0 for a string with no command
  * Per-cell vectors are 1 x ncells or ncells x 1; zk / zbk are (nz+2) x ncells, xm / xg
  * 4 x ncells (xm: 0-based model index t*nZ+z), lin 35 x ncells -- MATLAB's column-major
  * k x ncells is the library's cell-major [ncells][k], so no copy is made for them.
@@ -108,11 +120,13 @@ static void chk(int rc) {
  * stale or made-up uint64 raises a MATLAB error instead of crashing MATLAB. */
 #define MAXCTX 64
 static mpcekf_ctx *g_live[MAXCTX];
+static int32_t g_series[MAXCTX]; /* 'packbegin's series of g_live[i] (0: no pack): sizes 'stepexpack's limiter */
 
 static void track(mpcekf_ctx *h, int add) {
   for (int i = 0; i < MAXCTX; ++i)
     if (add ? g_live[i] == NULL : g_live[i] == h) {
       g_live[i] = add ? h : NULL;
+      g_series[i] = 0;
       return;
     }
 }
@@ -123,7 +137,14 @@ static void destroy_all(void) {
     if (g_live[i]) {
       (void)mpcekf_ctx_destroy(g_live[i]);
       g_live[i] = NULL;
+      g_series[i] = 0;
     }
+}
+
+static int32_t *series_of(mpcekf_ctx *h) {
+  for (int i = 0; i < MAXCTX; ++i)
+    if (g_live[i] == h) return &g_series[i];
+  return NULL;
 }
 
 static mpcekf_ctx *handle(const mxArray *a) {
@@ -397,7 +418,8 @@ static void gateway(mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
                                             "plantobs", "obsslots", "obslayout", "stepobs", "setlimits", "getlimits",
                                             "clearlimits", "summarybegin", "stepsummary", "getsummary", "summaryend",
                                             "thermalbegin", "thermalget", "thermalend", "stepthermal",
-                                            "thermalschedule", "thermalscheduleend"};
+                                            "thermalschedule", "thermalscheduleend",
+                                            "packbegin", "packget", "packend", "stepexpack"};
   int known = 0;
   for (size_t i = 0; i < sizeof with_handle / sizeof *with_handle; ++i) known = known || !strcmp(cmd, with_handle[i]);
   if (!known) mexErrMsgIdAndTxt("mpcekf:arg", "unknown command %s", cmd);
@@ -535,6 +557,30 @@ static void gateway(mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         if (!(sd[j] >= 1 && sd[j] <= (double)schsets) || sd[j] != (double)(int32_t)sd[j])
           mexErrMsgIdAndTxt("mpcekf:arg", "thermalschedule: sets(%zu) = %g is not a map 1..%zu", j + 1, sd[j], schsets);
     }
+  }
+  /* the pack commands likewise: output count, a series that is no positive integer, an nsteps
+     that is no non-negative integer, a tc of the wrong class */
+  const int pkbegin = !strcmp(cmd, "packbegin"), steppk = !strcmp(cmd, "stepexpack");
+  int32_t pkseries = 0, pksteps = 0;
+  if ((pkbegin || !strcmp(cmd, "packend")) && g_nlhs > 0) mexErrMsgIdAndTxt("mpcekf:arg", "%s: no output", cmd);
+  if (!strcmp(cmd, "packget") && g_nlhs > 1) mexErrMsgIdAndTxt("mpcekf:arg", "packget: at most 1 output");
+  if (steppk && g_nlhs > 7)
+    mexErrMsgIdAndTxt("mpcekf:arg", "stepexpack: at most 7 outputs [u, v, soc, phise, nexec, ucmd, limiter]");
+  if (pkbegin) {
+    need(nrhs, 3, "'packbegin', h, series");
+    const double sd = scalar(prhs[2], "packbegin: series");
+    if (!(sd >= 1 && sd <= 2147483647.0) || sd != (double)(int32_t)sd)
+      mexErrMsgIdAndTxt("mpcekf:arg", "packbegin: series = %g is not a positive integer", sd);
+    pkseries = (int32_t)sd;
+  }
+  if (steppk) {
+    need(nrhs, 3, "'stepexpack', h, nsteps[, tc]");
+    const double nsd = scalar(prhs[2], "nsteps");
+    if (!(nsd >= 0 && nsd <= 2147483647.0) || nsd != (double)(int32_t)nsd)
+      mexErrMsgIdAndTxt("mpcekf:arg", "nsteps: expected a non-negative integer");
+    pksteps = (int32_t)nsd;
+    if (nrhs > 3 && !mxIsEmpty(prhs[3]) && (!mxIsDouble(prhs[3]) || mxIsComplex(prhs[3])))
+      mexErrMsgIdAndTxt("mpcekf:arg", "stepexpack: tc: expected [] or ncells x nsteps real doubles");
   }
   mpcekf_ctx *h = handle(prhs[1]);
   int64_t n = 0;
@@ -761,6 +807,39 @@ static void gateway(mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
     chk(rc);
   } else if (!strcmp(cmd, "thermalscheduleend")) {
     chk(mpcekf_thermal_schedule_end(h));
+  } else if (pkbegin) {
+    chk(mpcekf_pack_begin(h, pkseries));
+    *series_of(h) = pkseries;
+  } else if (!strcmp(cmd, "packget")) {
+    static const char *const pk_names[MPCEKF_NPK] = {"nlim", "steps", "headroom"};
+    int32_t ids[MPCEKF_NPK];
+    double *vals = (double *)mxMalloc((size_t)MPCEKF_NPK * nc * sizeof(double) + 8);
+    for (int f = 0; f < MPCEKF_NPK; ++f) ids[f] = f;
+    chk(mpcekf_pack_get(h, MPCEKF_NPK, ids, vals));
+    plhs[0] = mxCreateStructMatrix(1, 1, MPCEKF_NPK, (const char **)pk_names);
+    for (int f = 0; f < MPCEKF_NPK; ++f) {
+      mxArray *a = dmat(nc, 1);
+      if (nc) memcpy(mxGetDoubles(a), vals + (size_t)f * nc, nc * sizeof(double));
+      mxSetField(plhs[0], 0, pk_names[f], a);
+    }
+    mxFree(vals);
+  } else if (!strcmp(cmd, "packend")) {
+    chk(mpcekf_pack_end(h));
+    *series_of(h) = 0;
+  } else if (steppk) {
+    /* without a 'packbegin' the library refuses the call before it touches a row */
+    const int32_t series = *series_of(h);
+    const size_t nstr = series ? nc / (size_t)series : 0;
+    const double *tc = nrhs > 3 ? opt_vec(prhs[3], nc * (size_t)pksteps, "stepexpack: tc (ncells x nsteps)") : NULL;
+    for (int i = 0; i < 6; ++i) plhs[i] = i == 4 ? imat(nc, (size_t)pksteps) : dmat(nc, (size_t)pksteps);
+    plhs[6] = imat(nstr, (size_t)pksteps);
+    mpcekf_traj tr;
+    memset(&tr, 0, sizeof tr);
+    tr.u = mxGetDoubles(plhs[0]); tr.v = mxGetDoubles(plhs[1]); tr.soc = mxGetDoubles(plhs[2]);
+    tr.phise = mxGetDoubles(plhs[3]); tr.nexec = (int32_t *)mxGetData(plhs[4]);
+    int32_t *lim = (int32_t *)mxGetData(plhs[6]);
+    chk(mpcekf_step_ex_pack(h, pksteps, tc, &tr, NULL, 0, NULL, NULL, NULL, mxGetDoubles(plhs[5]), series ? lim : NULL, 0));
+    for (size_t i = 0; i < nstr * (size_t)pksteps; ++i) lim[i] += 1; /* 1-based; 0: no command */
   } else if (!strcmp(cmd, "mpcdiag")) {
     need(nrhs, 3, "'mpcdiag', h, lin[, uk_1]");
     plhs[0] = mxCreateDoubleMatrix(7, (mwSize)nc, mxCOMPLEX);  /* interleaved (re, im): [ncells][7][2] */

@@ -25,6 +25,7 @@
 #include "../../include/mpcekf.h"
 #include "mpcekf_eig.hpp"
 #include "mpcekf_kernels.hpp"
+#include "mpcekf_pack.hpp"
 #include "mpcekf_summary.hpp"
 #include "mpcekf_thermal.hpp"
 #include "mpcekf_thermal_sched.hpp"
@@ -283,6 +284,10 @@ struct mpcekf_ctx {
     g.n = n;
     return g;
   }
+  // mpcekf_pack_begin .. _end: the record [NPKR][n] and the cells per string.  d_pk != nullptr:
+  // every fused step couples its strings with k_pack after Hildreth.
+  double *d_pk = nullptr;
+  int32_t pk_series = 0;
   double *d_uk1p = nullptr;                      // [n] uk_1 before the step (poles / sv)
   int flush_period = LAZY_H;      // steps between all-model flushes (<= LAZY_H)
   // rolling flush (MPCEKF_FLUSH_ROLL=1, off by default): step t flushes the cell slice
@@ -1198,7 +1203,7 @@ int mpcekf_ctx_destroy(mpcekf_ctx *X) {
                   X->w.prob, X->w.X, X->w.R, X->w.K, X->w.hii, X->w.it, X->w.smin, X->d_lin, X->d_zsoc, X->d_mb, X->d_uk1p,
                   X->w.q, X->w.list, X->w.hist, X->d_poly, X->d_szk, X->d_sxg, X->d_sxm, X->d_slin, X->d_sv, X->d_zslot,
                   X->d_obs_blob, X->d_obs, X->d_obs_plan, X->d_lim, X->d_sch_hdr, X->d_sch_tab, X->d_sch_val, X->d_sch_set, X->d_sum, X->d_sum_reach, X->d_sum_obs,
-                  X->d_sum_ring, X->d_th, X->d_th_par, X->d_th_i, X->d_th_ocv, X->d_hot, X->d_hot_i, X->d_hotp, X->d_hotp_i};
+                  X->d_sum_ring, X->d_pk, X->d_th, X->d_th_par, X->d_th_i, X->d_th_ocv, X->d_hot, X->d_hot_i, X->d_hotp, X->d_hotp_i};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   for (auto &g : X->graphs) (void)hipGraphExecDestroy(g.exec);
@@ -1314,9 +1319,14 @@ static int lerr(int rc, const char *what) {
 // A thermal context (mpcekf_thermal_begin): k_thermal last in every step advances s.Tc, which
 // the next step's kernels read (tc_in stays null); temp / heat (mpcekf_step_ex_thermal) are two
 // more [nsteps][ncells] output fields, written by k_thermal.
+// A pack context (mpcekf_pack_begin): k_pack after Hildreth and k_cl_diag replaces each cell's
+// command in s.uk, s.uk_1 and the u row by its string's current, before the summary fold and
+// k_thermal read them; ucmd [nsteps][ncells] and limiter [nsteps][ncells / series]
+// (mpcekf_step_ex_pack) are two more output fields, written by k_pack.
 static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const mpcekf_traj *tr,
                      const int32_t *slots, int32_t nslots, double *obs, int32_t outputs_on_device,
-                     bool sum = false, double *temp = nullptr, double *heat = nullptr) {
+                     bool sum = false, double *temp = nullptr, double *heat = nullptr, double *ucmd = nullptr,
+                     int32_t *limiter = nullptr) {
   // a thermal context owns the temperature: refused before anything of the context changes
   if (X && X->d_th && tc_degC)
     return fail(MPCEKF_E_ARG, "step: tc_degC on a thermal context (mpcekf_thermal_begin): the model sets the temperature");
@@ -1325,6 +1335,7 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
   if (rc) return rc;
   if (nsteps < 0) return fail(MPCEKF_E_ARG, "nsteps < 0");
   const bool thermal = X->d_th != nullptr;
+  const bool pack = X->d_pk != nullptr;
   if (sum && X->sum_slot >= 0) {  // checked by mpcekf_summary_begin
     slots = &X->sum_slot;
     nslots = 1;
@@ -1350,19 +1361,24 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
   // a constraint block off, or per-cell limits at Np = 5: the split route of mpcekf_switch.hip
   const bool switched = X->sw != 7 || (lim && !X->wide);
   const size_t n = (size_t)X->n, per = n * (size_t)nsteps, nzz = (size_t)X->nz + 2;
-  // the output fields, their element size and elements per cell-step
+  // the output fields, their element size and elements per cell-step (rows: elements of
+  // `width` per step where that is not ncells)
   struct F {
     void *host;
     size_t esz, width;
     char *dev;
+    size_t rows;
   } f[] = {{tr->u, 8, 1, nullptr},       {tr->v, 8, 1, nullptr},      {tr->soc, 8, 1, nullptr},
            {tr->phise, 8, 1, nullptr},   {tr->nexec, 4, 1, nullptr},  {tr->x, 8, 6, nullptr},
            {tr->zk, 8, nzz, nullptr},    {tr->zbk, 8, nzz, nullptr},  {tr->J_unc, 8, 1, nullptr},
            {tr->J_fin, 8, 1, nullptr},   {tr->norm_du, 8, 1, nullptr}, {tr->nviol, 4, 1, nullptr},
            {tr->poles, 8, 2 * NA, nullptr}, {tr->sv, 8, NA, nullptr},
            {nslots ? obs : nullptr, 8, (size_t)nslots, nullptr},  // [nsteps][nslots][ncells]
-           {temp, 8, 1, nullptr},        {heat, 8, 1, nullptr}};  // k_thermal's rows (a thermal context's only)
+           {temp, 8, 1, nullptr},        {heat, 8, 1, nullptr},   // k_thermal's rows (a thermal context's only)
+           {ucmd, 8, 1, nullptr},                                 // k_pack's rows (a pack context's only)
+           {limiter, 4, 1, nullptr, pack ? n / (size_t)X->pk_series : 0}};  // [nsteps][nstrings]
   constexpr int NF = sizeof(f) / sizeof(f[0]);
+  auto step_bytes = [&](const F &e) -> size_t { return (e.rows ? e.rows : n) * e.width * e.esz; };  // one step's block
   const double *dtc = tc_degC;  // [nsteps][n] device copy of the per-step temperatures
   // sum: rows of the window instead of rows of a trajectory, for outputs and temperatures alike
   const size_t ring = sum ? (size_t)SUM_WIN : 0;
@@ -1381,18 +1397,18 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
     for (F &e : f) e.dev = (char *)e.host;
   } else {
     size_t need = tc_degC ? ((per * 8 + 255) & ~(size_t)255) : 0;
-    for (F &e : f) need += e.host ? ((per * e.width * e.esz + 255) & ~(size_t)255) : 0;
+    for (F &e : f) need += e.host ? (((size_t)nsteps * step_bytes(e) + 255) & ~(size_t)255) : 0;
     if ((rc = X->tmp(need + 256))) return rc;
     char *p = (char *)X->d_tmp;
     for (F &e : f)
-      if (e.host) { e.dev = p; p += (per * e.width * e.esz + 255) & ~(size_t)255; }
+      if (e.host) { e.dev = p; p += ((size_t)nsteps * step_bytes(e) + 255) & ~(size_t)255; }
     if (tc_degC) {
       HIPCHK(hipMemcpyAsync(p, tc_degC, per * 8, hipMemcpyHostToDevice, X->stream));
       dtc = (const double *)p;
     }
   }
   auto row = [&](int i, int k) -> char * {  // step k's [ncells][width] block of field i
-    return f[i].dev ? f[i].dev + (ring ? (size_t)k % ring : (size_t)k) * n * f[i].width * f[i].esz : nullptr;
+    return f[i].dev ? f[i].dev + (ring ? (size_t)k % ring : (size_t)k) * step_bytes(f[i]) : nullptr;
   };
   auto tc_row = [&](int k) -> const double * {  // step k's temperatures
     return dtc ? dtc + (ring ? (size_t)k % ring : (size_t)k) * n : nullptr;
@@ -1596,6 +1612,18 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
         if ((rc = lerr(rc, "cl_diag"))) return rc;
       }
       if (E) HIPCHK(hipEventRecord(E[4], X->stream));
+      if (pack) {  // the strings' currents, once every cell's command stands in s.uk
+        KPack q{};
+        q.uk = X->s.uk;
+        q.uk_1 = X->s.uk_1;
+        q.u = (double *)row(0, k);
+        q.ucmd = (double *)row(17, k);
+        q.limiter = (int *)row(18, k);
+        q.rec = X->d_pk;
+        q.n = X->n;
+        q.series = X->pk_series;
+        if ((rc = lerr(launch_pack(q, X->stream), "pack"))) return rc;
+      }
       // k_bounds done before k_flush or the next step's k_cell rewrites the records it reads
       if (side) HIPCHK(hipStreamWaitEvent(X->stream, X->ev_bjoin, 0));
       if (slice && fork) HIPCHK(hipStreamWaitEvent(X->stream, X->ev_join, 0));
@@ -1653,7 +1681,10 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
     // the call's launches depend only on these (kernel arguments are call-relative:
     // lazy_t = 1..nsteps, the flush schedule, the output rows), so a repeated call shape
     // replays one instantiated graph instead of 5-7 launches per step
-    std::vector<uintptr_t> key = {(uintptr_t)nsteps, (uintptr_t)dtc, (uintptr_t)diag, (uintptr_t)bounds};
+    // the pack state fifth and sixth (its ucmd / limiter rows are among the output rows below):
+    // 0 on a context without a pack -- mpcekf_pack_end retires the graphs that name one
+    std::vector<uintptr_t> key = {(uintptr_t)nsteps, (uintptr_t)dtc, (uintptr_t)diag, (uintptr_t)bounds,
+                                  (uintptr_t)X->d_pk, (uintptr_t)X->pk_series};
     for (const F &e : f) key.push_back((uintptr_t)e.dev);
     key.push_back((uintptr_t)osel.plan);  // a regrown plan buffer retires the graphs that named the old one
     key.push_back((uintptr_t)nslots);
@@ -1682,7 +1713,7 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
   if (!outputs_on_device)
     for (int i = 0; i < NF; ++i)
       if (f[i].host)
-        HIPCHK(hipMemcpyAsync(f[i].host, f[i].dev, per * f[i].width * f[i].esz, hipMemcpyDeviceToHost, X->stream));
+        HIPCHK(hipMemcpyAsync(f[i].host, f[i].dev, (size_t)nsteps * step_bytes(f[i]), hipMemcpyDeviceToHost, X->stream));
   // mpcekf_get_zk returns the last step's zk / boundzk whichever buffers the steps wrote
   if (nsteps > 0 && f[6].dev)
     HIPCHK(hipMemcpyAsync(X->d_zk, row(6, nsteps - 1), n * nzz * 8, hipMemcpyDeviceToDevice, X->stream));
@@ -2166,6 +2197,80 @@ int mpcekf_step_ex_thermal(mpcekf_ctx *X, int32_t nsteps, const mpcekf_traj *tr,
   if (!X) return fail(MPCEKF_E_ARG, "step_ex_thermal: null ctx");
   if (!X->d_th) return fail(MPCEKF_E_STATE, "step_ex_thermal: call mpcekf_thermal_begin first");
   return step_impl(X, nsteps, nullptr, tr, slots, nslots, obs, outputs_on_device, false, temp, heat);
+}
+
+// ---- series strings along the fused loop (mpcekf_pack.hip) ----
+static_assert(NPKR == MPCEKF_NPK && PK_NLIM == MPCEKF_PK_NLIM && PK_STEPS == MPCEKF_PK_STEPS &&
+                  PK_HEADROOM == MPCEKF_PK_HEADROOM,
+              "mpcekf_pack.hpp's rows are include/mpcekf.h's MPCEKF_PK_*");
+
+int mpcekf_pack_begin(mpcekf_ctx *X, int32_t series) {
+  if (!X) return fail(MPCEKF_E_ARG, "pack_begin: null ctx");
+  if (series < 1) return fail(MPCEKF_E_ARG, "pack_begin: series = %d: a string has 1 cell or more", series);
+  if (X->n % series)
+    return fail(MPCEKF_E_ARG, "pack_begin: series = %d does not divide ncells = %lld", series, (long long)X->n);
+  int rc;
+  HIPCHK(hipSetDevice(X->device));
+  const size_t n = std::max<size_t>((size_t)X->n, 1);
+  double *rec = X->d_pk;
+  if (!rec && (rc = dalloc(&rec, n * NPKR))) return rc;
+  // all bits 0 is +0.0: the record's reset, behind every launch of an earlier call
+  HIPCHK(hipMemsetAsync(rec, 0, n * NPKR * 8, X->stream));
+  HIPCHK(hipStreamSynchronize(X->stream));
+  X->d_pk = rec;
+  X->pk_series = series;
+  return MPCEKF_OK;
+}
+
+int mpcekf_pack_get(mpcekf_ctx *X, int32_t nfields, const int32_t *fields, double *values) {
+  if (!X) return fail(MPCEKF_E_ARG, "pack_get: null ctx");
+  if (nfields < 1 || nfields > MPCEKF_NPK)
+    return fail(MPCEKF_E_ARG, "pack_get: nfields = %d outside 1..%d", nfields, (int)MPCEKF_NPK);
+  if (!fields) return fail(MPCEKF_E_ARG, "pack_get: null fields");
+  if (!values) return fail(MPCEKF_E_ARG, "pack_get: null values");
+  unsigned seen = 0;
+  for (int i = 0; i < nfields; ++i) {
+    if (fields[i] < 0 || fields[i] >= MPCEKF_NPK)
+      return fail(MPCEKF_E_ARG, "pack_get: fields[%d] = %d is not a MPCEKF_PK_* id (0..%d)", i, fields[i],
+                  (int)MPCEKF_NPK - 1);
+    if (seen >> fields[i] & 1) return fail(MPCEKF_E_ARG, "pack_get: fields: id %d given twice", fields[i]);
+    seen |= 1u << fields[i];
+  }
+  if (!X->d_pk) return fail(MPCEKF_E_STATE, "pack_get: call mpcekf_pack_begin first");
+  HIPCHK(hipSetDevice(X->device));
+  const size_t n = (size_t)X->n;
+  for (int i = 0; i < nfields && n; ++i)
+    HIPCHK(hipMemcpyAsync(values + (size_t)i * n, X->d_pk + (size_t)fields[i] * n, n * 8, hipMemcpyDeviceToHost,
+                          X->stream));
+  HIPCHK(hipStreamSynchronize(X->stream));
+  return MPCEKF_OK;
+}
+
+int mpcekf_pack_end(mpcekf_ctx *X) {
+  if (!X) return fail(MPCEKF_E_ARG, "pack_end: null ctx");
+  if (!X->d_pk) return MPCEKF_OK;
+  HIPCHK(hipSetDevice(X->device));
+  HIPCHK(hipStreamSynchronize(X->stream));
+  // the graphs captured on a pack context launch k_pack on the record: retired before it is freed
+  for (size_t i = X->graphs.size(); i-- > 0;)
+    if (X->graphs[i].key[4]) {
+      (void)hipGraphExecDestroy(X->graphs[i].exec);
+      X->graphs.erase(X->graphs.begin() + (std::ptrdiff_t)i);
+    }
+  (void)hipFree(X->d_pk);
+  X->d_pk = nullptr;
+  X->pk_series = 0;
+  return MPCEKF_OK;
+}
+
+int mpcekf_step_ex_pack(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const mpcekf_traj *tr,
+                        const int32_t *slots, int32_t nslots, double *obs, double *temp, double *heat, double *ucmd,
+                        int32_t *limiter, int32_t outputs_on_device) {
+  if (!X) return fail(MPCEKF_E_ARG, "step_ex_pack: null ctx");
+  if (!X->d_pk) return fail(MPCEKF_E_STATE, "step_ex_pack: call mpcekf_pack_begin first");
+  if ((temp || heat) && !X->d_th)
+    return fail(MPCEKF_E_STATE, "step_ex_pack: temp / heat rows: call mpcekf_thermal_begin first");
+  return step_impl(X, nsteps, tc_degC, tr, slots, nslots, obs, outputs_on_device, false, temp, heat, ucmd, limiter);
 }
 
 int mpcekf_set_timing(mpcekf_ctx *X, int32_t enable) {

@@ -275,7 +275,7 @@ class Context:
                        norm_du=(np.float64, ()), nviol=(np.int32, ()), poles=(np.float64, (7, 2)),
                        sv=(np.float64, (7,)))
 
-    def step(self, nsteps, outputs=("u", "v", "soc", "phise", "nexec"), tc=None, obs=None, thermal=None):
+    def step(self, nsteps, outputs=("u", "v", "soc", "phise", "nexec"), tc=None, obs=None, thermal=None, pack=None):
         """nsteps fused closed-loop steps (runMPC.m:83-112).  ``outputs`` names the per-step
         stores to return as [nsteps, ncells(, k)] arrays: u, v, soc, phise, nexec, and the
         diagnostics x (x_store), zk / zbk (zkEst / zkBound), J_unc, J_fin, norm_du, nviol
@@ -290,7 +290,12 @@ class Context:
         fields); only the selected slots are computed and copied.  None: the call as it was.
         ``thermal``: on a context with a thermal model (thermal_begin), the model's per-step rows
         to return as [nsteps, ncells] arrays: "temp" (the temperature each step used) and / or
-        "heat" (the heat it generated, W); mpcekf_step_ex_thermal.  None: the call as it was."""
+        "heat" (the heat it generated, W); mpcekf_step_ex_thermal.  None: the call as it was.
+        ``pack``: on a pack context (pack_begin), the pack's per-step rows to return: "ucmd"
+        [nsteps, ncells], each cell's own command before its string's reduction (``u`` holds the
+        applied current), and / or "limiter" [nsteps, ncells // series] int32, each string's
+        limiter as an in-string index or -1; mpcekf_step_ex_pack.  None: the call as it was (a
+        pack context couples its strings all the same)."""
         n = self.n
         fields, slots = self._obs_select(obs, "step")   # KeyError before any library call
         th = () if thermal is None else (thermal,) if isinstance(thermal, str) else tuple(thermal)
@@ -299,6 +304,10 @@ class Context:
                 raise KeyError(f"step: unknown thermal row {k!r} (one of ('temp', 'heat'))")
         if thermal is not None and tc is not None:
             raise ValueError("step: thermal rows come from the model, which takes no tc")
+        pk = () if pack is None else (pack,) if isinstance(pack, str) else tuple(pack)
+        for k in pk:
+            if k not in ("ucmd", "limiter"):
+                raise KeyError(f"step: unknown pack row {k!r} (one of ('ucmd', 'limiter'))")
         tcs = None if tc is None else tc_grid(tc, nsteps, n)
         out = {}
         tr = _lib.Traj()
@@ -311,10 +320,22 @@ class Context:
             setattr(tr, k, out[k].ctypes.data_as(C.c_void_p).value)
         tcp = tcs.ctypes.data_as(C.c_void_p) if tcs is not None else None
         rec = None if fields is None else np.empty((nsteps, slots.size, n))
-        if thermal is not None:
+        vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        if pack is not None:
             for k in th:
                 out[k] = np.empty((nsteps, n))
-            vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+            series = getattr(self, "_pack_series", 0)   # 0: no begin, the library refuses the call
+            if "ucmd" in pk:
+                out["ucmd"] = np.empty((nsteps, n))
+            if "limiter" in pk:
+                out["limiter"] = np.empty((nsteps, n // series if series else n), dtype=np.int32)
+            ns = 0 if fields is None else int(slots.size)
+            check(self.L.mpcekf_step_ex_pack(self.h, int(nsteps), tcp, C.byref(tr), iptr(slots) if ns else None, ns,
+                                             vp(rec) if ns else None, vp(out.get("temp")), vp(out.get("heat")),
+                                             vp(out.get("ucmd")), vp(out.get("limiter")), 0))
+        elif thermal is not None:
+            for k in th:
+                out[k] = np.empty((nsteps, n))
             ns = 0 if fields is None else int(slots.size)
             check(self.L.mpcekf_step_ex_thermal(self.h, int(nsteps), C.byref(tr), iptr(slots) if ns else None, ns,
                                                 vp(rec) if ns else None, vp(out.get("temp")), vp(out.get("heat")), 0))
@@ -587,6 +608,37 @@ class Context:
         """End the schedule (mpcekf_thermal_schedule_end): its fields go back to what set_limits
         or the configuration gave them."""
         check(self.L.mpcekf_thermal_schedule_end(self.h))
+
+    # -- series strings: one current per pack string ------------------------
+    PACK_FIELDS = _lib.PACK_FIELDS
+
+    def pack_begin(self, series):
+        """Make the context a pack of ncells // series strings of ``series`` cells in series
+        (mpcekf_pack_begin): string g is the cells [g * series, (g + 1) * series).  From then on
+        every fused step applies to each cell of a string the string's current, the largest
+        (least charging) command among its cells; a second call replaces the first and resets
+        the record.  series = 1 couples nothing."""
+        series = int(series)
+        check(self.L.mpcekf_pack_begin(self.h, series))
+        self._pack_series = series
+
+    def pack_get(self, fields=None):
+        """{name: [ncells] float64} of the pack record (mpcekf_pack_get): ``fields`` names of
+        PACK_FIELDS (default all): nlim, the steps the cell was its string's limiter; steps, the
+        steps it had a command; headroom, the sum of applied current minus own command (A steps)."""
+        names = self.PACK_FIELDS if fields is None else (fields,) if isinstance(fields, str) else tuple(fields)
+        for k in names:
+            if k not in self.PACK_FIELDS:
+                raise KeyError(f"pack_get: unknown field {k!r} (one of {self.PACK_FIELDS})")
+        ids = np.asarray([self.PACK_FIELDS.index(k) for k in names], dtype=np.int32)
+        vals = np.empty((ids.size, self.n))
+        check(self.L.mpcekf_pack_get(self.h, int(ids.size), iptr(ids), dptr(vals)))
+        return {k: vals[i] for i, k in enumerate(names)}
+
+    def pack_end(self):
+        """Drop the pack (mpcekf_pack_end): every cell is on its own again."""
+        check(self.L.mpcekf_pack_end(self.h))
+        self._pack_series = 0
 
     def set_timing(self, enable=True):
         """enable: True/1 = every step; N > 1 = sample every N-th step (less perturbation)."""
@@ -941,7 +993,7 @@ def _thermal_begin(ctx, thermal):
 
 
 def runMPC(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=None, obs=None, limits=None,
-           thermal=None):
+           thermal=None, pack=None):
     """runMPC.m:72-112 for a batch of cells; returns trajectories [nsteps, ncells].
     tc_traj [nsteps, ncells] (degC): a temperature profile (TC is the initial one).
     obs: the plant's observables of every step as out["obs"] (Context.step's obs=).
@@ -951,7 +1003,10 @@ def runMPC(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=None,
     heat themselves (TC is the initial temperature; no tc_traj); adds out["temp"], out["heat"]
     and out["thermal"], the model's record.  thermal["schedule"]: a dict of
     Context.thermal_schedule's arguments (T_lo, T_hi, sets, the tables): limits that follow the
-    cells' temperature; adds out["limits"], the values in force at the last step."""
+    cells' temperature; adds out["limits"], the values in force at the last step.
+    pack: dict(series=S): the cells form ncells // S series strings, each charged with the one
+    current its weakest cell accepts (Context.pack_begin); out["u"] is the applied current, and
+    out["ucmd"], out["limiter"] and out["pack"], the pack's record, are added."""
     SOC0 = np.atleast_1d(np.asarray(SOC0, dtype=np.float64))
     n = ncells or SOC0.shape[0]
     with Context(rom, n, cfg, device) as ctx:
@@ -960,7 +1015,12 @@ def runMPC(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=None,
             ctx.set_limits(**limits)
         if thermal:
             _thermal_begin(ctx, thermal)
-        out = ctx.step(nsteps, tc=tc_traj, obs=obs, thermal=("temp", "heat") if thermal else None)
+        if pack:
+            ctx.pack_begin(**pack)
+        out = ctx.step(nsteps, tc=tc_traj, obs=obs, thermal=("temp", "heat") if thermal else None,
+                       pack=("ucmd", "limiter") if pack else None)
+        if pack:
+            out["pack"] = ctx.pack_get()
         if thermal:
             out["thermal"] = ctx.thermal_get()
             if thermal.get("schedule"):
@@ -970,14 +1030,15 @@ def runMPC(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=None,
 
 
 def run_summary(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=None, limits=None, reach=None,
-                obs=None, chunk=None, thermal=None):
+                obs=None, chunk=None, thermal=None, pack=None):
     """runMPC.m:72-112 for a batch of cells, read out as the per-cell charge summary instead of
     trajectories: {field: [ncells]} of Context.get_summary plus "status".  limits: as runMPC's
     (a protocol sweep); reach, obs: Context.summary_begin's; tc_traj [nsteps, ncells] (degC): a
     temperature profile; chunk: steps per step_summary call (default all at once; with tc_traj
     a chunk bounds the host array each call converts).  Neither host nor device memory grows
     with nsteps.  thermal: as runMPC's, its "schedule" included (no tc_traj); adds "thermal", the
-    model's record."""
+    model's record.  pack: as runMPC's; adds "pack", the pack's record, beside the summary (whose
+    currents are the applied ones)."""
     SOC0 = np.atleast_1d(np.asarray(SOC0, dtype=np.float64))
     n = ncells or SOC0.shape[0]
     nsteps = int(nsteps)
@@ -991,11 +1052,15 @@ def run_summary(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=
             ctx.set_limits(**limits)
         if thermal:
             _thermal_begin(ctx, thermal)
+        if pack:
+            ctx.pack_begin(**pack)
         ctx.summary_begin(reach=reach, obs=obs)
         for k in range(0, nsteps, max(chunk, 1)):
             m = min(chunk, nsteps - k)
             ctx.step_summary(m, tc=None if tcs is None else tcs[k:k + m])
         out = ctx.get_summary()
+        if pack:
+            out["pack"] = ctx.pack_get()
         if thermal:
             out["thermal"] = ctx.thermal_get()
         out["status"] = ctx.get_state()["status"]
