@@ -688,6 +688,84 @@ int mpcekf_step_ex_pack(mpcekf_ctx *ctx, int32_t nsteps, const double *tc_degC, 
                         const int32_t *slots, int32_t nslots, double *obs, double *temp, double *heat, double *ucmd,
                         int32_t *limiter, int32_t outputs_on_device);
 
+/* ---- side-reaction losses per cell along the fused loop (not part of the reference interface) ----
+ * runMPC.m keeps phise_store above mpcData.const.phise_min so that lithium does not plate.  How
+ * much a protocol plated, or how much SEI (the solid-electrolyte interphase film on the negative
+ * electrode) it grew, is the integral over the charge of a Tafel-type side-reaction current
+ * driven by the side-reaction overpotential and the temperature.  A context can carry up to four
+ * such reactions per cell, each evaluated from the EKF's estimate (source EST), from the plant's
+ * own value (source PLANT), or both: what the controller believed it plated beside what the
+ * plant plated.
+ * Per cell c, after fused step t, for every enabled source s and every reaction r, every line
+ * one or more separately rounded fp64 operations in exactly this order (no contraction into
+ * fused multiply-adds, IEEE division, dexp the defined exp of the v3 Arrhenius factor: rom.py
+ * dexp, oracle/mpcekf_oracle.c orc_exp); F, R and Tref are the ROM's (mpcekf_rom):
+ *   T    = the temperature step t used: temp[t] of mpcekf_step_ex_thermal (the cell temperature
+ *          after the step has stored its tc_degC row, before the thermal model advances it)
+ *   TK   = T + 273.15
+ *   phi  = source EST:   phise_store(t), the step's traj.phise row (runMPC.m:94-95)
+ *          source PLANT: the negPhise0 slot of step t's row of mpcekf_step_ex_obs
+ *   eta  = phi - U_r
+ *   g    = (alpha_r * F) / (R * TK)
+ *   ar   = dexp((Ea_r / R) * (1.0 / Tref - 1.0 / TK))
+ *   j    = (i0_r * ar) * dexp(-(g * eta))           amperes; Tafel, cathodic
+ *   on   = eta < gate_r                             false for a NaN eta; gate = +inf: always on
+ *   if on and isfinite(j):
+ *          Q_SUM <- Q_SUM + j                       plain additions from +0 in step order
+ *                                                   (Ah = Q_SUM * Ts / 3600)
+ *          N_ON  <- N_ON + 1
+ *          if isnan(J_MAX) or j > J_MAX:            strict comparison: the first occurrence wins
+ *                 J_MAX <- j;  J_MAX_STEP <- tt
+ *   per source: STEPS += 1 if phi is not NaN, else NSKIP += 1
+ *   tt = STEPS + NSKIP + 1, read from the record before the update
+ * tt counts the source's steps since begin, from 1, across calls.  A cell in error or lock-out
+ * has a NaN phise from its failing step on: NSKIP counts those steps and the sums stay.
+ * The record, every value a double, counts and step indices exact integers: Q_SUM, J_MAX (NaN
+ * before the first step taken), J_MAX_STEP (0 likewise), N_ON per source and reaction; STEPS and
+ * NSKIP per source, the same for every reaction.
+ * The aging record is a property of the context, like the thermal model: mpcekf_step, _step_ex,
+ * _step_ex_obs, _step_ex_thermal, _step_ex_pack, _step_summary and _step_ex_aging all
+ * accumulate, graph replay included.  The stage route does not accumulate, as it does not
+ * advance the thermal model.  mpcekf_get_state / mpcekf_set_state carry neither the aging record
+ * nor the thermal one.  The kernel is not one of mpcekf_set_timing's five slots.
+ * Not modelled: stripping of plated lithium, feedback of the lost capacity into the plant. */
+#define MPCEKF_AG_SRC_EST 1   /* the EKF's estimate, phise_store                         */
+#define MPCEKF_AG_SRC_PLANT 2 /* the plant's own negPhise0 (OB_step.m:317)               */
+#define MPCEKF_AG_MAXREACT 4
+enum {
+  MPCEKF_AG_I0 = 0 /* A, at Tref and eta = 0 */, MPCEKF_AG_U /* V */, MPCEKF_AG_ALPHA, MPCEKF_AG_EA /* J/mol */,
+  MPCEKF_AG_GATE /* V, +inf: always on */, MPCEKF_NAGP
+};
+enum {
+  MPCEKF_AGR_Q_SUM = 0, MPCEKF_AGR_J_MAX, MPCEKF_AGR_J_MAX_STEP, MPCEKF_AGR_N_ON, MPCEKF_AGR_STEPS,
+  MPCEKF_AGR_NSKIP, MPCEKF_NAGR
+};
+/* Gives the context nreact reactions evaluated from the sources of the bit mask `sources`
+ * (MPCEKF_AG_SRC_*): params [nreact][MPCEKF_NAGP][ncells].  Allocates the record (first call) and
+ * resets it; a second begin replaces the first.  May be called before mpcekf_init_cells.
+ * MPCEKF_E_ARG (nothing changed): a NULL pointer; nreact outside 1..4; sources outside 1..3; an
+ * i0 that is not finite or is negative; a non-finite U or Ea; an alpha that is not finite and
+ * positive; a NaN gate.  MPCEKF_E_UNSUPPORTED: source PLANT on a ROM whose obs layout has no
+ * negPhise0 (none today: mpcekf_ctx_create refuses a ROM without exactly one phise row at the
+ * negative collector with MPCEKF_E_ROM). */
+int mpcekf_aging_begin(mpcekf_ctx *ctx, int32_t nreact, int32_t sources, const double *params);
+/* values [nfields][ncells]: row i = field fields[i] (distinct MPCEKF_AGR_* ids) of source
+ * `source` (one MPCEKF_AG_SRC_* bit the begin enabled), reaction `react` (0..nreact-1).
+ * MPCEKF_E_STATE without a begin; MPCEKF_E_ARG: a NULL pointer, a source that is not enabled, a
+ * react outside 0..nreact-1, nfields outside 1..MPCEKF_NAGR, an unknown or repeated id. */
+int mpcekf_aging_get(mpcekf_ctx *ctx, int32_t source, int32_t react, int32_t nfields, const int32_t *fields,
+                     double *values);
+/* Frees the record; the context then behaves as one that never began.  A no-op without a begin. */
+int mpcekf_aging_end(mpcekf_ctx *ctx);
+/* mpcekf_step_ex_pack's arguments (ucmd / limiter need a pack, temp / heat a model:
+ * MPCEKF_E_STATE without) plus rate [nsteps][nsrc * nreact][ncells] (host, or device when
+ * outputs_on_device != 0; may be NULL): the enabled sources in id order, the reactions inside.
+ * A rate row holds j where on && isfinite(j), NaN where phi is NaN, +0.0 otherwise.
+ * MPCEKF_E_STATE without a begin; a refused call leaves the context and the record as they were. */
+int mpcekf_step_ex_aging(mpcekf_ctx *ctx, int32_t nsteps, const double *tc_degC, const mpcekf_traj *traj,
+                         const int32_t *slots, int32_t nslots, double *obs, double *temp, double *heat, double *ucmd,
+                         int32_t *limiter, double *rate, int32_t outputs_on_device);
+
 /* ---- device memory (not part of the reference interface) ----
  * Device buffers for outputs_on_device calls, allocated by the library's own HIP
  * runtime so a host process never holds a second one (a framework's bundled

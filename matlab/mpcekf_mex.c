@@ -93,6 +93,18 @@
  *                       'step' on a pack context (u: the applied current), plus each cell's own
  *                       command, ncells x nsteps, and each string's limiter, nstrings x nsteps
  *                       int32, the 1-based in-string index or 0 for a string with no command
+ *                       mpcekf_mex('agingbegin', h, params, sources)   mpcekf_aging_begin
+ *                       side reactions (plating, SEI) integrated per cell after every fused step.
+ *                       params: ncells x 5 x nreact (nreact 1..4), columns i0 (A), U (V), alpha,
+ *                       Ea (J/mol), gate (V, Inf: always on); sources: 1 the EKF's phise, 2 the
+ *                       plant's negPhise0, 3 both
+ *   s                 = mpcekf_mex('agingget', h, source, react)       mpcekf_aging_get
+ *                       struct of ncells x 1 column vectors: q_sum, j_max, j_max_step, n_on, steps,
+ *                       nskip (MPCEKF_AGR_*) of source 1 or 2 and the 1-based reaction react
+ *                       mpcekf_mex('agingend', h)                      mpcekf_aging_end
+ *   [u,v,soc,phise,nexec,rate] = mpcekf_mex('stepexaging', h, nsteps[, tc])   mpcekf_step_ex_aging
+ *                       'step' on an aging context, plus every step's side-reaction currents (A),
+ *                       ncells x (nsrc*nreact) x nsteps: the enabled sources in order, reactions inside
  * Per-cell vectors are 1 x ncells or ncells x 1; zk / zbk are (nz+2) x ncells, xm / xg
  * 4 x ncells (xm: 0-based model index t*nZ+z), lin 35 x ncells -- MATLAB's column-major
  * k x ncells is the library's cell-major [ncells][k], so no copy is made for them.
@@ -121,12 +133,14 @@ static void chk(int rc) {
 #define MAXCTX 64
 static mpcekf_ctx *g_live[MAXCTX];
 static int32_t g_series[MAXCTX]; /* 'packbegin's series of g_live[i] (0: no pack): sizes 'stepexpack's limiter */
+static int32_t g_agrows[MAXCTX]; /* 'agingbegin's nsrc * nreact of g_live[i] (0: none): sizes 'stepexaging's rate */
 
 static void track(mpcekf_ctx *h, int add) {
   for (int i = 0; i < MAXCTX; ++i)
     if (add ? g_live[i] == NULL : g_live[i] == h) {
       g_live[i] = add ? h : NULL;
       g_series[i] = 0;
+      g_agrows[i] = 0;
       return;
     }
 }
@@ -138,12 +152,19 @@ static void destroy_all(void) {
       (void)mpcekf_ctx_destroy(g_live[i]);
       g_live[i] = NULL;
       g_series[i] = 0;
+      g_agrows[i] = 0;
     }
 }
 
 static int32_t *series_of(mpcekf_ctx *h) {
   for (int i = 0; i < MAXCTX; ++i)
     if (g_live[i] == h) return &g_series[i];
+  return NULL;
+}
+
+static int32_t *agrows_of(mpcekf_ctx *h) {
+  for (int i = 0; i < MAXCTX; ++i)
+    if (g_live[i] == h) return &g_agrows[i];
   return NULL;
 }
 
@@ -419,7 +440,8 @@ static void gateway(mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
                                             "clearlimits", "summarybegin", "stepsummary", "getsummary", "summaryend",
                                             "thermalbegin", "thermalget", "thermalend", "stepthermal",
                                             "thermalschedule", "thermalscheduleend",
-                                            "packbegin", "packget", "packend", "stepexpack"};
+                                            "packbegin", "packget", "packend", "stepexpack",
+                                            "agingbegin", "agingget", "agingend", "stepexaging"};
   int known = 0;
   for (size_t i = 0; i < sizeof with_handle / sizeof *with_handle; ++i) known = known || !strcmp(cmd, with_handle[i]);
   if (!known) mexErrMsgIdAndTxt("mpcekf:arg", "unknown command %s", cmd);
@@ -581,6 +603,46 @@ static void gateway(mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
     pksteps = (int32_t)nsd;
     if (nrhs > 3 && !mxIsEmpty(prhs[3]) && (!mxIsDouble(prhs[3]) || mxIsComplex(prhs[3])))
       mexErrMsgIdAndTxt("mpcekf:arg", "stepexpack: tc: expected [] or ncells x nsteps real doubles");
+  }
+  /* the aging commands likewise: output count, params that are no ncells x 5 x nreact doubles,
+     sources outside 1..3, a source / react that is no index, an nsteps that is no count */
+  const int agbegin = !strcmp(cmd, "agingbegin"), agget = !strcmp(cmd, "agingget"), stepag = !strcmp(cmd, "stepexaging");
+  int32_t agreact = 0, agsrc = 0, agsteps = 0;
+  if ((agbegin || !strcmp(cmd, "agingend")) && g_nlhs > 0) mexErrMsgIdAndTxt("mpcekf:arg", "%s: no output", cmd);
+  if (agget && g_nlhs > 1) mexErrMsgIdAndTxt("mpcekf:arg", "agingget: at most 1 output");
+  if (stepag && g_nlhs > 6)
+    mexErrMsgIdAndTxt("mpcekf:arg", "stepexaging: at most 6 outputs [u, v, soc, phise, nexec, rate]");
+  if (agbegin) {
+    need(nrhs, 4, "'agingbegin', h, params, sources");
+    if (!mxIsDouble(prhs[2]) || mxIsComplex(prhs[2]) || mxIsEmpty(prhs[2]))
+      mexErrMsgIdAndTxt("mpcekf:arg", "agingbegin: params: expected a real double ncells x 5 x nreact array");
+    const size_t rows = mxGetM(prhs[2]), cols = mxGetNumberOfElements(prhs[2]) / rows;
+    if (cols % MPCEKF_NAGP != 0 || cols / MPCEKF_NAGP < 1 || cols / MPCEKF_NAGP > MPCEKF_AG_MAXREACT)
+      mexErrMsgIdAndTxt("mpcekf:arg", "agingbegin: params: %zu x %zu: expected 5 columns per reaction, 1..4 reactions", rows,
+                        cols);
+    agreact = (int32_t)(cols / MPCEKF_NAGP);
+    const double sd = scalar(prhs[3], "agingbegin: sources");
+    if (!(sd >= 1 && sd <= 3) || sd != (double)(int32_t)sd)
+      mexErrMsgIdAndTxt("mpcekf:arg", "agingbegin: sources = %g is not 1 (est), 2 (plant) or 3 (both)", sd);
+    agsrc = (int32_t)sd;
+  }
+  if (agget) {
+    need(nrhs, 4, "'agingget', h, source, react");
+    const double sd = scalar(prhs[2], "agingget: source"), rd = scalar(prhs[3], "agingget: react");
+    if (sd != 1 && sd != 2) mexErrMsgIdAndTxt("mpcekf:arg", "agingget: source = %g is not 1 (est) or 2 (plant)", sd);
+    if (!(rd >= 1 && rd <= MPCEKF_AG_MAXREACT) || rd != (double)(int32_t)rd)
+      mexErrMsgIdAndTxt("mpcekf:arg", "agingget: react = %g is not a reaction 1..4", rd);
+    agsrc = (int32_t)sd;
+    agreact = (int32_t)rd - 1;
+  }
+  if (stepag) {
+    need(nrhs, 3, "'stepexaging', h, nsteps[, tc]");
+    const double nsd = scalar(prhs[2], "nsteps");
+    if (!(nsd >= 0 && nsd <= 2147483647.0) || nsd != (double)(int32_t)nsd)
+      mexErrMsgIdAndTxt("mpcekf:arg", "nsteps: expected a non-negative integer");
+    agsteps = (int32_t)nsd;
+    if (nrhs > 3 && !mxIsEmpty(prhs[3]) && (!mxIsDouble(prhs[3]) || mxIsComplex(prhs[3])))
+      mexErrMsgIdAndTxt("mpcekf:arg", "stepexaging: tc: expected [] or ncells x nsteps real doubles");
   }
   mpcekf_ctx *h = handle(prhs[1]);
   int64_t n = 0;
@@ -840,6 +902,37 @@ static void gateway(mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
     int32_t *lim = (int32_t *)mxGetData(plhs[6]);
     chk(mpcekf_step_ex_pack(h, pksteps, tc, &tr, NULL, 0, NULL, NULL, NULL, mxGetDoubles(plhs[5]), series ? lim : NULL, 0));
     for (size_t i = 0; i < nstr * (size_t)pksteps; ++i) lim[i] += 1; /* 1-based; 0: no command */
+  } else if (agbegin) {
+    /* ncells x 5 x nreact column-major is the library's [nreact][MPCEKF_NAGP][ncells] as it stands */
+    chk(mpcekf_aging_begin(h, agreact, agsrc, dvec(prhs[2], nc * MPCEKF_NAGP * (size_t)agreact, "agingbegin: params (ncells x 5 x nreact)")));
+    *agrows_of(h) = ((agsrc & 1) + (agsrc >> 1)) * agreact;
+  } else if (agget) {
+    static const char *const ag_names[MPCEKF_NAGR] = {"q_sum", "j_max", "j_max_step", "n_on", "steps", "nskip"};
+    int32_t ids[MPCEKF_NAGR];
+    double *vals = (double *)mxMalloc((size_t)MPCEKF_NAGR * nc * sizeof(double) + 8);
+    for (int f = 0; f < MPCEKF_NAGR; ++f) ids[f] = f;
+    chk(mpcekf_aging_get(h, agsrc, agreact, MPCEKF_NAGR, ids, vals));
+    plhs[0] = mxCreateStructMatrix(1, 1, MPCEKF_NAGR, (const char **)ag_names);
+    for (int f = 0; f < MPCEKF_NAGR; ++f) {
+      mxArray *a = dmat(nc, 1);
+      if (nc) memcpy(mxGetDoubles(a), vals + (size_t)f * nc, nc * sizeof(double));
+      mxSetField(plhs[0], 0, ag_names[f], a);
+    }
+    mxFree(vals);
+  } else if (!strcmp(cmd, "agingend")) {
+    chk(mpcekf_aging_end(h));
+    *agrows_of(h) = 0;
+  } else if (stepag) {
+    /* without an 'agingbegin' the library refuses the call before it touches a row */
+    const size_t rows = (size_t)*agrows_of(h);
+    const double *tc = nrhs > 3 ? opt_vec(prhs[3], nc * (size_t)agsteps, "stepexaging: tc (ncells x nsteps)") : NULL;
+    for (int i = 0; i < 5; ++i) plhs[i] = i == 4 ? imat(nc, (size_t)agsteps) : dmat(nc, (size_t)agsteps);
+    plhs[5] = dmat(nc, rows * (size_t)agsteps); /* ncells x (nsrc*nreact) x nsteps, its pages side by side */
+    mpcekf_traj tr;
+    memset(&tr, 0, sizeof tr);
+    tr.u = mxGetDoubles(plhs[0]); tr.v = mxGetDoubles(plhs[1]); tr.soc = mxGetDoubles(plhs[2]);
+    tr.phise = mxGetDoubles(plhs[3]); tr.nexec = (int32_t *)mxGetData(plhs[4]);
+    chk(mpcekf_step_ex_aging(h, agsteps, tc, &tr, NULL, 0, NULL, NULL, NULL, NULL, NULL, rows ? mxGetDoubles(plhs[5]) : NULL, 0));
   } else if (!strcmp(cmd, "mpcdiag")) {
     need(nrhs, 3, "'mpcdiag', h, lin[, uk_1]");
     plhs[0] = mxCreateDoubleMatrix(7, (mwSize)nc, mxCOMPLEX);  /* interleaved (re, im): [ncells][7][2] */

@@ -37,6 +37,11 @@ SCHEDULE_FIELDS = ("Crate", "u_max", "du_min", "du_max", "v_max", "phise_min")
 THERMAL_FIELDS = ("T", "T_max", "T_max_step", "T_min", "heat_sum", "steps", "nheld")
 # MPCEKF_PK_*: the series strings' per-cell record (mpcekf_pack_begin / _get)
 PACK_FIELDS = ("nlim", "steps", "headroom")
+# MPCEKF_AG_* / MPCEKF_AGR_*: one side reaction's parameters and the aging record's fields
+# (mpcekf_aging_begin / _get); MPCEKF_AG_SRC_*: the sources' bits
+AGING_PARAMS = ("i0", "U", "alpha", "Ea", "gate")
+AGING_FIELDS = ("q_sum", "j_max", "j_max_step", "n_on", "steps", "nskip")
+AGING_SOURCES = {"est": 1, "plant": 2}
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
@@ -101,6 +106,7 @@ EXPORTS = [
     "mpcekf_summary_begin", "mpcekf_step_summary", "mpcekf_get_summary", "mpcekf_summary_end",
     "mpcekf_thermal_begin", "mpcekf_thermal_get", "mpcekf_thermal_end", "mpcekf_step_ex_thermal",
     "mpcekf_pack_begin", "mpcekf_pack_get", "mpcekf_pack_end", "mpcekf_step_ex_pack",
+    "mpcekf_aging_begin", "mpcekf_aging_get", "mpcekf_aging_end", "mpcekf_step_ex_aging",
     "mpcekf_thermal_schedule", "mpcekf_thermal_schedule_end",
     # the _async stage twins (include/mpcekf.h)
     "mpcekf_plant_step_async", "mpcekf_ekf_step_async", "mpcekf_linearize_async", "mpcekf_lin_fields_async",
@@ -185,6 +191,10 @@ def load():
     L.mpcekf_pack_get.argtypes = [vp, C.c_int32, _ip, _dp]
     L.mpcekf_pack_end.argtypes = [vp]
     L.mpcekf_step_ex_pack.argtypes = [vp, C.c_int32, vp, C.POINTER(Traj), _ip, C.c_int32, vp, vp, vp, vp, vp, C.c_int32]
+    L.mpcekf_aging_begin.argtypes = [vp, C.c_int32, C.c_int32, _dp]
+    L.mpcekf_aging_get.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, _ip, _dp]
+    L.mpcekf_aging_end.argtypes = [vp]
+    L.mpcekf_step_ex_aging.argtypes = [vp, C.c_int32, vp, C.POINTER(Traj), _ip, C.c_int32, vp, vp, vp, vp, vp, vp, C.c_int32]
     for nm in ("plant_step", "ekf_step", "linearize", "lin_fields", "mpc_step", "mpc_step_ex", "mpc_diag",
                "get_scalars", "plant_step_obs", "plant_obs_slots"):   # the _async twins take the synchronous call's arguments
         getattr(L, f"mpcekf_{nm}_async").argtypes = getattr(L, f"mpcekf_{nm}").argtypes

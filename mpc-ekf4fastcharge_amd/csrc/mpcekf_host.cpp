@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../include/mpcekf.h"
+#include "mpcekf_aging.hpp"
 #include "mpcekf_eig.hpp"
 #include "mpcekf_kernels.hpp"
 #include "mpcekf_pack.hpp"
@@ -288,6 +289,15 @@ struct mpcekf_ctx {
   // every fused step couples its strings with k_pack after Hildreth.
   double *d_pk = nullptr;
   int32_t pk_series = 0;
+  // mpcekf_aging_begin .. _end: the record [AG_ROWS][n], the parameters [ag_nreact][NAGP][n]
+  // (room for AG_MAXR), and the rows k_aging reads when the call has none of its own: the
+  // step's phise row [n] (source EST, no traj.phise) and the plant's negPhise0 row [n] (source
+  // PLANT, negPhise0 not among the call's slots; d_ag_plan: that one-position plan of
+  // k_obs_traj, ag_need its OBS_NEED_* bits, ag_slot the record slot).  d_ag != nullptr: every
+  // fused step runs k_aging before k_thermal.
+  double *d_ag = nullptr, *d_ag_par = nullptr, *d_ag_phi = nullptr, *d_ag_obs = nullptr;
+  int *d_ag_plan = nullptr;
+  int32_t ag_nreact = 0, ag_sources = 0, ag_slot = -1, ag_need = 0;
   double *d_uk1p = nullptr;                      // [n] uk_1 before the step (poles / sv)
   int flush_period = LAZY_H;      // steps between all-model flushes (<= LAZY_H)
   // rolling flush (MPCEKF_FLUSH_ROLL=1, off by default): step t flushes the cell slice
@@ -1203,7 +1213,7 @@ int mpcekf_ctx_destroy(mpcekf_ctx *X) {
                   X->w.prob, X->w.X, X->w.R, X->w.K, X->w.hii, X->w.it, X->w.smin, X->d_lin, X->d_zsoc, X->d_mb, X->d_uk1p,
                   X->w.q, X->w.list, X->w.hist, X->d_poly, X->d_szk, X->d_sxg, X->d_sxm, X->d_slin, X->d_sv, X->d_zslot,
                   X->d_obs_blob, X->d_obs, X->d_obs_plan, X->d_lim, X->d_sch_hdr, X->d_sch_tab, X->d_sch_val, X->d_sch_set, X->d_sum, X->d_sum_reach, X->d_sum_obs,
-                  X->d_sum_ring, X->d_pk, X->d_th, X->d_th_par, X->d_th_i, X->d_th_ocv, X->d_hot, X->d_hot_i, X->d_hotp, X->d_hotp_i};
+                  X->d_sum_ring, X->d_pk, X->d_ag, X->d_ag_par, X->d_ag_phi, X->d_ag_obs, X->d_ag_plan, X->d_th, X->d_th_par, X->d_th_i, X->d_th_ocv, X->d_hot, X->d_hot_i, X->d_hotp, X->d_hotp_i};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   for (auto &g : X->graphs) (void)hipGraphExecDestroy(g.exec);
@@ -1323,10 +1333,16 @@ static int lerr(int rc, const char *what) {
 // command in s.uk, s.uk_1 and the u row by its string's current, before the summary fold and
 // k_thermal read them; ucmd [nsteps][ncells] and limiter [nsteps][ncells / series]
 // (mpcekf_step_ex_pack) are two more output fields, written by k_pack.
+// An aging context (mpcekf_aging_begin): k_aging before k_thermal reads the step's phise row
+// (source EST; the context's own row when the call has none) and the step's negPhise0 row
+// (source PLANT; from the call's obs rows when its slots name it, else from a one-position
+// k_obs_traj launch of the context's own, which leaves the caller's rows what they were); rate
+// [nsteps][nsrc * nreact][ncells] (mpcekf_step_ex_aging) is one more output field, written by
+// k_aging.
 static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const mpcekf_traj *tr,
                      const int32_t *slots, int32_t nslots, double *obs, int32_t outputs_on_device,
                      bool sum = false, double *temp = nullptr, double *heat = nullptr, double *ucmd = nullptr,
-                     int32_t *limiter = nullptr) {
+                     int32_t *limiter = nullptr, double *rate = nullptr) {
   // a thermal context owns the temperature: refused before anything of the context changes
   if (X && X->d_th && tc_degC)
     return fail(MPCEKF_E_ARG, "step: tc_degC on a thermal context (mpcekf_thermal_begin): the model sets the temperature");
@@ -1336,6 +1352,8 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
   if (nsteps < 0) return fail(MPCEKF_E_ARG, "nsteps < 0");
   const bool thermal = X->d_th != nullptr;
   const bool pack = X->d_pk != nullptr;
+  const bool aging = X->d_ag != nullptr;
+  const bool ag_est = aging && (X->ag_sources & MPCEKF_AG_SRC_EST), ag_plant = aging && (X->ag_sources & MPCEKF_AG_SRC_PLANT);
   if (sum && X->sum_slot >= 0) {  // checked by mpcekf_summary_begin
     slots = &X->sum_slot;
     nslots = 1;
@@ -1376,7 +1394,9 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
            {nslots ? obs : nullptr, 8, (size_t)nslots, nullptr},  // [nsteps][nslots][ncells]
            {temp, 8, 1, nullptr},        {heat, 8, 1, nullptr},   // k_thermal's rows (a thermal context's only)
            {ucmd, 8, 1, nullptr},                                 // k_pack's rows (a pack context's only)
-           {limiter, 4, 1, nullptr, pack ? n / (size_t)X->pk_series : 0}};  // [nsteps][nstrings]
+           {limiter, 4, 1, nullptr, pack ? n / (size_t)X->pk_series : 0},  // [nsteps][nstrings]
+           // k_aging's rows (an aging context's only): [nsteps][nsrc * nreact][ncells]
+           {rate, 8, aging ? (size_t)(((int)ag_est + (int)ag_plant) * X->ag_nreact) : 0, nullptr}};
   constexpr int NF = sizeof(f) / sizeof(f[0]);
   auto step_bytes = [&](const F &e) -> size_t { return (e.rows ? e.rows : n) * e.width * e.esz; };  // one step's block
   const double *dtc = tc_degC;  // [nsteps][n] device copy of the per-step temperatures
@@ -1443,6 +1463,13 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
     osel.plan = X->d_obs_plan;
     osel.nsel = nslots;
   }
+  // source PLANT: the position of negPhise0 among the call's slots, or the context's own launch
+  int ag_pos = -1;
+  if (ag_plant) {
+    for (int i = 0; i < nslots && ag_pos < 0; ++i)
+      if (slots[i] == X->ag_slot) ag_pos = i;
+    if (ag_pos < 0 && (rc = X->obs_blob_buf())) return rc;
+  }
   constexpr int NEV = 8;  // events per step: plant | cell | bounds | hild (+ diag) |, then | flush |, hild start (side)
   if (X->timing && X->ev.size() < (size_t)nsteps * NEV) {
     size_t old = X->ev.size();
@@ -1498,6 +1525,14 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
         ok.out = (double *)row(14, k);
         if ((rc = lerr(launch_obs_traj(X->r, X->s, X->ko, ok, t, tc_row(k), X->stream), "obs_traj"))) return rc;
       }
+      if (ag_plant && ag_pos < 0) {  // the plant's negPhise0 of step t for k_aging, into the context's row
+        KObsSel ok{};
+        ok.plan = X->d_ag_plan;
+        ok.nsel = 1;
+        ok.need = X->ag_need;
+        ok.out = X->d_ag_obs;
+        if ((rc = lerr(launch_obs_traj(X->r, X->s, X->ko, ok, t, tc_row(k), X->stream), "obs_traj (aging)"))) return rc;
+      }
       if (!plant_in_cell && (rc = lerr(launch_plant(X->r, X->s, X->s.uk, X->s.vk, t, tc_row(k), X->stream), "plant")))
         return rc;
       if (E) HIPCHK(hipEventRecord(E[1], X->stream));
@@ -1511,6 +1546,7 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
       io.v = (double *)row(1, k);
       io.soc = (double *)row(2, k);
       io.phise = (double *)row(3, k);
+      if (ag_est && !io.phise) io.phise = X->d_ag_phi;  // k_aging's input when the call asks for no phise row
       io.nexec = (int *)row(4, k);
       io.x_out = (double *)row(5, k);
       io.zk = f[6].dev ? (double *)row(6, k) : X->d_zk;
@@ -1649,6 +1685,21 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
         q.max_hild = X->cfg.max_hild;
         if ((rc = lerr(launch_summary(q, X->stream), "summary"))) return rc;
       }
+      if (aging) {  // before k_thermal: s.Tc is still the temperature the step used
+        KAging q{};
+        q.Tc = X->s.Tc;
+        q.phi[AG_SRC_EST] = ag_est ? io.phise : nullptr;
+        q.phi[AG_SRC_PLANT] = !ag_plant ? nullptr : ag_pos < 0 ? X->d_ag_obs : (const double *)row(14, k) + (size_t)ag_pos * n;
+        q.par = X->d_ag_par;
+        q.rec = X->d_ag;
+        q.rate = (double *)row(19, k);
+        q.n = X->n;
+        q.nreact = X->ag_nreact;
+        q.F = X->r.F;
+        q.R = X->r.R;
+        q.Tref = X->r.Tref;
+        if ((rc = lerr(launch_aging(q, X->stream), "aging"))) return rc;
+      }
       if (thermal) {  // last: after Hildreth stored the next command and the flush
         KTherm q{};
         q.Tc = X->s.Tc;
@@ -1684,7 +1735,12 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
     // the pack state fifth and sixth (its ucmd / limiter rows are among the output rows below):
     // 0 on a context without a pack -- mpcekf_pack_end retires the graphs that name one
     std::vector<uintptr_t> key = {(uintptr_t)nsteps, (uintptr_t)dtc, (uintptr_t)diag, (uintptr_t)bounds,
-                                  (uintptr_t)X->d_pk, (uintptr_t)X->pk_series};
+                                  (uintptr_t)X->d_pk, (uintptr_t)X->pk_series,
+                                  // the aging state seventh to tenth (its rate rows are among the output
+                                  // rows below): 0 on a context without one -- mpcekf_aging_end, and a
+                                  // begin that changes nreact or sources, retire the graphs that name one
+                                  (uintptr_t)X->d_ag, (uintptr_t)(X->ag_nreact | X->ag_sources << 8),
+                                  (uintptr_t)(aging ? X->d_ag_phi : nullptr), (uintptr_t)(aging ? X->d_ag_obs : nullptr)};
     for (const F &e : f) key.push_back((uintptr_t)e.dev);
     key.push_back((uintptr_t)osel.plan);  // a regrown plan buffer retires the graphs that named the old one
     key.push_back((uintptr_t)nslots);
@@ -2271,6 +2327,165 @@ int mpcekf_step_ex_pack(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, co
   if ((temp || heat) && !X->d_th)
     return fail(MPCEKF_E_STATE, "step_ex_pack: temp / heat rows: call mpcekf_thermal_begin first");
   return step_impl(X, nsteps, tc_degC, tr, slots, nslots, obs, outputs_on_device, false, temp, heat, ucmd, limiter);
+}
+
+// ---- side-reaction losses along the fused loop (mpcekf_aging.hip) ----
+static_assert(NAGP == MPCEKF_NAGP && AG_I0 == MPCEKF_AG_I0 && AG_U == MPCEKF_AG_U && AG_ALPHA == MPCEKF_AG_ALPHA &&
+                  AG_EA == MPCEKF_AG_EA && AG_GATE == MPCEKF_AG_GATE && NAGR == MPCEKF_NAGR &&
+                  AGR_Q_SUM == MPCEKF_AGR_Q_SUM && AGR_J_MAX == MPCEKF_AGR_J_MAX &&
+                  AGR_J_MAX_STEP == MPCEKF_AGR_J_MAX_STEP && AGR_N_ON == MPCEKF_AGR_N_ON &&
+                  AGR_STEPS == MPCEKF_AGR_STEPS && AGR_NSKIP == MPCEKF_AGR_NSKIP && AG_MAXR == MPCEKF_AG_MAXREACT &&
+                  (1 << AG_SRC_EST) == MPCEKF_AG_SRC_EST && (1 << AG_SRC_PLANT) == MPCEKF_AG_SRC_PLANT,
+              "mpcekf_aging.hpp's rows are include/mpcekf.h's MPCEKF_AG_* / MPCEKF_AGR_*");
+
+// the graphs captured on an aging context launch k_aging on the record and the rows: retired
+// before any of them is freed, or when the launches they hold no longer fit nreact / sources
+static void retire_aging_graphs(mpcekf_ctx *X) {
+  for (size_t i = X->graphs.size(); i-- > 0;)
+    if (X->graphs[i].key[6]) {
+      (void)hipGraphExecDestroy(X->graphs[i].exec);
+      X->graphs.erase(X->graphs.begin() + (std::ptrdiff_t)i);
+    }
+}
+
+int mpcekf_aging_begin(mpcekf_ctx *X, int32_t nreact, int32_t sources, const double *params) {
+  if (!X) return fail(MPCEKF_E_ARG, "aging_begin: null ctx");
+  if (!params) return fail(MPCEKF_E_ARG, "aging_begin: null params");
+  if (nreact < 1 || nreact > MPCEKF_AG_MAXREACT)
+    return fail(MPCEKF_E_ARG, "aging_begin: nreact = %d outside 1..%d", nreact, (int)MPCEKF_AG_MAXREACT);
+  if (sources < 1 || sources > (MPCEKF_AG_SRC_EST | MPCEKF_AG_SRC_PLANT))
+    return fail(MPCEKF_E_ARG, "aging_begin: sources = %d outside 1..3 (MPCEKF_AG_SRC_EST | MPCEKF_AG_SRC_PLANT)", sources);
+  const size_t nc = (size_t)X->n;
+  for (int r = 0; r < nreact; ++r) {
+    const double *P = params + (size_t)r * MPCEKF_NAGP * nc;
+    for (size_t c = 0; c < nc; ++c) {
+      const double i0 = P[MPCEKF_AG_I0 * nc + c], U = P[MPCEKF_AG_U * nc + c], al = P[MPCEKF_AG_ALPHA * nc + c];
+      const double Ea = P[MPCEKF_AG_EA * nc + c], gate = P[MPCEKF_AG_GATE * nc + c];
+      if (!std::isfinite(i0) || i0 < 0)
+        return fail(MPCEKF_E_ARG, "aging_begin: reaction %d: i0[%zu] = %g: must be finite and >= 0 (A)", r, c, i0);
+      if (!std::isfinite(U)) return fail(MPCEKF_E_ARG, "aging_begin: reaction %d: U[%zu] = %g is not finite", r, c, U);
+      if (!std::isfinite(al) || !(al > 0))
+        return fail(MPCEKF_E_ARG, "aging_begin: reaction %d: alpha[%zu] = %g: must be finite and > 0", r, c, al);
+      if (!std::isfinite(Ea)) return fail(MPCEKF_E_ARG, "aging_begin: reaction %d: Ea[%zu] = %g is not finite", r, c, Ea);
+      if (gate != gate) return fail(MPCEKF_E_ARG, "aging_begin: reaction %d: gate[%zu] is NaN (+inf: always on)", r, c);
+    }
+  }
+  // mpcekf_ctx_create accepts only a ROM with exactly one phise row at the negative collector
+  // (MPCEKF_E_ROM otherwise, iterEKF.m:692-725), so every context's obs layout has the negPhise0
+  // slot and this refusal cannot be reached today; it guards the plan below against a layout
+  // that ever drops the field
+  const int slot = X->obs_off[MPCEKF_OBS_negPhise0];
+  if ((sources & MPCEKF_AG_SRC_PLANT) && X->obs_off[MPCEKF_OBS_negPhise0 + 1] <= slot)
+    return fail(MPCEKF_E_UNSUPPORTED, "aging_begin: source PLANT: this ROM's obs layout has no negPhise0");
+  int rc;
+  HIPCHK(hipSetDevice(X->device));
+  const size_t n = std::max<size_t>(nc, 1);
+  // Every buffer before anything is stored: a failed allocation frees what this call allocated
+  // and leaves the context as it was.  The phise row only for source EST, the negPhise0 row and
+  // its plan only for source PLANT (a row an earlier begin allocated stays until mpcekf_aging_end).
+  double *rec = X->d_ag, *par = X->d_ag_par, *phi = X->d_ag_phi, *ob = X->d_ag_obs;
+  int *plan = X->d_ag_plan;
+  const bool want_phi = sources & MPCEKF_AG_SRC_EST, want_ob = sources & MPCEKF_AG_SRC_PLANT;
+  rc = MPCEKF_OK;
+  if (!rc && !rec) rc = dalloc(&rec, n * AG_ROWS);
+  if (!rc && !par) rc = dalloc(&par, n * AG_MAXR * NAGP);
+  if (!rc && want_phi && !phi) rc = dalloc(&phi, n);
+  if (!rc && want_ob && !ob) rc = dalloc(&ob, n);
+  if (!rc && want_ob && !plan) rc = dalloc(&plan, 1);
+  if (rc) {
+    if (rec != X->d_ag) (void)hipFree(rec);
+    if (par != X->d_ag_par) (void)hipFree(par);
+    if (phi != X->d_ag_phi) (void)hipFree(phi);
+    if (ob != X->d_ag_obs) (void)hipFree(ob);
+    if (plan != X->d_ag_plan) (void)hipFree(plan);
+    return rc;
+  }
+  if (X->d_ag && (X->ag_nreact != nreact || X->ag_sources != sources)) {
+    HIPCHK(hipStreamSynchronize(X->stream));
+    retire_aging_graphs(X);
+  }
+  X->d_ag = rec;
+  X->d_ag_par = par;
+  X->d_ag_phi = phi;
+  X->d_ag_obs = ob;
+  X->d_ag_plan = plan;
+  X->ag_nreact = nreact;
+  X->ag_sources = sources;
+  X->ag_slot = -1;
+  X->ag_need = 0;
+  int src = 0;
+  if (sources & MPCEKF_AG_SRC_PLANT) {  // the one-position plan, as step_impl forms a caller's
+    X->ag_slot = slot;
+    src = X->obs_slot_src[(size_t)slot];
+    const int kind = src >= 0 ? (int)(X->ko.desc[src] & 15u) : -1;
+    if (src == OBS_SRC_VCELL || kind == OBS_PPHIS) X->ag_need |= OBS_NEED_V;
+    if (src == OBS_SRC_PHIE0 || kind == OBS_NPHISE || kind == OBS_PHIE) X->ag_need |= OBS_NEED_UN;
+    if (kind == OBS_PPHISE) X->ag_need |= OBS_NEED_UP;
+  }
+  if (plan) HIPCHK(hipMemcpyAsync(plan, &src, sizeof(int), hipMemcpyHostToDevice, X->stream));
+  if (nc) HIPCHK(hipMemcpyAsync(par, params, nc * (size_t)nreact * NAGP * 8, hipMemcpyHostToDevice, X->stream));
+  if ((rc = lerr(launch_aging_reset(rec, X->n, X->stream), "aging_reset"))) return rc;
+  HIPCHK(hipStreamSynchronize(X->stream));
+  return MPCEKF_OK;
+}
+
+int mpcekf_aging_get(mpcekf_ctx *X, int32_t source, int32_t react, int32_t nfields, const int32_t *fields,
+                     double *values) {
+  if (!X) return fail(MPCEKF_E_ARG, "aging_get: null ctx");
+  if (nfields < 1 || nfields > MPCEKF_NAGR)
+    return fail(MPCEKF_E_ARG, "aging_get: nfields = %d outside 1..%d", nfields, (int)MPCEKF_NAGR);
+  if (!fields) return fail(MPCEKF_E_ARG, "aging_get: null fields");
+  if (!values) return fail(MPCEKF_E_ARG, "aging_get: null values");
+  unsigned seen = 0;
+  for (int i = 0; i < nfields; ++i) {
+    if (fields[i] < 0 || fields[i] >= MPCEKF_NAGR)
+      return fail(MPCEKF_E_ARG, "aging_get: fields[%d] = %d is not a MPCEKF_AGR_* id (0..%d)", i, fields[i],
+                  (int)MPCEKF_NAGR - 1);
+    if (seen >> fields[i] & 1) return fail(MPCEKF_E_ARG, "aging_get: fields: id %d given twice", fields[i]);
+    seen |= 1u << fields[i];
+  }
+  if (!X->d_ag) return fail(MPCEKF_E_STATE, "aging_get: call mpcekf_aging_begin first");
+  if ((source != MPCEKF_AG_SRC_EST && source != MPCEKF_AG_SRC_PLANT) || !(X->ag_sources & source))
+    return fail(MPCEKF_E_ARG, "aging_get: source = %d is not a source this context's begin enabled (mask %d)", source,
+                X->ag_sources);
+  if (react < 0 || react >= X->ag_nreact)
+    return fail(MPCEKF_E_ARG, "aging_get: react = %d outside 0..%d", react, X->ag_nreact - 1);
+  HIPCHK(hipSetDevice(X->device));
+  const size_t n = (size_t)X->n;
+  const int s = source == MPCEKF_AG_SRC_EST ? AG_SRC_EST : AG_SRC_PLANT;
+  for (int i = 0; i < nfields && n; ++i)
+    HIPCHK(hipMemcpyAsync(values + (size_t)i * n, X->d_ag + (size_t)ag_row(s, react, fields[i]) * n, n * 8,
+                          hipMemcpyDeviceToHost, X->stream));
+  HIPCHK(hipStreamSynchronize(X->stream));
+  return MPCEKF_OK;
+}
+
+int mpcekf_aging_end(mpcekf_ctx *X) {
+  if (!X) return fail(MPCEKF_E_ARG, "aging_end: null ctx");
+  if (!X->d_ag) return MPCEKF_OK;
+  HIPCHK(hipSetDevice(X->device));
+  HIPCHK(hipStreamSynchronize(X->stream));
+  retire_aging_graphs(X);
+  void *ptrs[] = {X->d_ag, X->d_ag_par, X->d_ag_phi, X->d_ag_obs, X->d_ag_plan};
+  for (void *p : ptrs)
+    if (p) (void)hipFree(p);
+  X->d_ag = X->d_ag_par = X->d_ag_phi = X->d_ag_obs = nullptr;
+  X->d_ag_plan = nullptr;
+  X->ag_nreact = X->ag_sources = X->ag_need = 0;
+  X->ag_slot = -1;
+  return MPCEKF_OK;
+}
+
+int mpcekf_step_ex_aging(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const mpcekf_traj *tr,
+                         const int32_t *slots, int32_t nslots, double *obs, double *temp, double *heat, double *ucmd,
+                         int32_t *limiter, double *rate, int32_t outputs_on_device) {
+  if (!X) return fail(MPCEKF_E_ARG, "step_ex_aging: null ctx");
+  if (!X->d_ag) return fail(MPCEKF_E_STATE, "step_ex_aging: call mpcekf_aging_begin first");
+  if ((temp || heat) && !X->d_th)
+    return fail(MPCEKF_E_STATE, "step_ex_aging: temp / heat rows: call mpcekf_thermal_begin first");
+  if ((ucmd || limiter) && !X->d_pk)
+    return fail(MPCEKF_E_STATE, "step_ex_aging: ucmd / limiter rows: call mpcekf_pack_begin first");
+  return step_impl(X, nsteps, tc_degC, tr, slots, nslots, obs, outputs_on_device, false, temp, heat, ucmd, limiter, rate);
 }
 
 int mpcekf_set_timing(mpcekf_ctx *X, int32_t enable) {

@@ -25,6 +25,8 @@
 
 #pragma clang fp contract(off)
 
+#include "mpcekf_dexp.hpp"  // dexp and dm::LN2_HI / LN2_LO, shared with mpcekf_aging.hip
+
 namespace mk {
 
 
@@ -59,7 +61,6 @@ __device__ __forceinline__ int pk(int r, int c) {
 // minimax series in s = f / (2 + f), f = m - 1 (Lg1..Lg7, fdlibm's public
 // coefficients).  Only +, -, *, /, sqrt and fma: correctly rounded on both sides.
 namespace dm {
-constexpr double LN2_HI = 6.93147180369123816490e-01, LN2_LO = 1.90821492927058770002e-10;
 constexpr double LN2 = 6.93147180559945286227e-01;
 constexpr double LG1 = 6.666666666666735130e-01, LG2 = 3.999999999940941908e-01, LG3 = 2.857142874366239149e-01,
                  LG4 = 2.222219843214978396e-01, LG5 = 1.818357216161805012e-01, LG6 = 1.531383769920937332e-01,
@@ -193,28 +194,6 @@ __device__ __forceinline__ void tabn2(const double *c, const double *map, int nu
   b = horner6(b01, b23, b45, s);
   if (x != x) a = b = __builtin_nan("");
 }
-// Defined exp of the v3 Arrhenius factor (oracle/mpcekf_oracle.c orc_exp, rom.py dexp):
-// x = k ln2 + r, k = floor(x / ln2 + 1/2), fdlibm's rational form for exp(r); only
-// +, -, *, /, floor and ldexp, exact or correctly rounded on both sides.
-// The special cases by selects (the in-range arithmetic unchanged), so that a lookup is one
-// basic block and neighbouring lookups' L2 loads can overlap (profiles/r05h_ab_branchfree.txt)
-__device__ __forceinline__ double dexp(double x0) {
-  const bool nan = x0 != x0, big = x0 > 709.782712893384, small = x0 < -745.1332191019412;
-  const double x = (nan || big || small) ? 0.0 : x0;
-  const double k = floor(x * 1.44269504088896338700e+00 + 0.5);
-  const double hi = x - k * dm::LN2_HI;
-  const double lo = k * dm::LN2_LO;
-  const double r = hi - lo;
-  const double t = r * r;
-  const double c = r - t * (1.66666666666666019037e-01 +
-                            t * (-2.77777777770155933842e-03 +
-                                 t * (6.61375632143793436117e-05 +
-                                      t * (-1.65339022054652515390e-06 + t * 4.13813679705723846039e-08))));
-  const double y = 1.0 - ((lo - (r * c) / (2.0 - c)) - hi);
-  const double v = ldexp(y, (int)k);
-  return nan ? x0 : big ? __builtin_inf() : small ? 0.0 : v;
-}
-
 // Electrode tables (include/mpcekf.h mpcekf_electrode; host: build_rom).  In LDS: a
 // header [Uocp1 [side][nth] | TK [MAXTT] | soc(0,T), soc(1,T) [side][2][MAXTT]], then
 // the 2-D tables [EF_*][side][nte][nth].  EF_CDL is last and only the plant blob

@@ -275,7 +275,8 @@ class Context:
                        norm_du=(np.float64, ()), nviol=(np.int32, ()), poles=(np.float64, (7, 2)),
                        sv=(np.float64, (7,)))
 
-    def step(self, nsteps, outputs=("u", "v", "soc", "phise", "nexec"), tc=None, obs=None, thermal=None, pack=None):
+    def step(self, nsteps, outputs=("u", "v", "soc", "phise", "nexec"), tc=None, obs=None, thermal=None, pack=None,
+             aging=None):
         """nsteps fused closed-loop steps (runMPC.m:83-112).  ``outputs`` names the per-step
         stores to return as [nsteps, ncells(, k)] arrays: u, v, soc, phise, nexec, and the
         diagnostics x (x_store), zk / zbk (zkEst / zkBound), J_unc, J_fin, norm_du, nviol
@@ -295,7 +296,11 @@ class Context:
         [nsteps, ncells], each cell's own command before its string's reduction (``u`` holds the
         applied current), and / or "limiter" [nsteps, ncells // series] int32, each string's
         limiter as an in-string index or -1; mpcekf_step_ex_pack.  None: the call as it was (a
-        pack context couples its strings all the same)."""
+        pack context couples its strings all the same).
+        ``aging``: on an aging context (aging_begin), ("rate",) returns out["rate"]
+        [nsteps, nsrc * nreact, ncells], every step's side-reaction currents (A): the enabled
+        sources in the order est, plant, the reactions inside; mpcekf_step_ex_aging.  None: the
+        call as it was (an aging context accumulates its record all the same)."""
         n = self.n
         fields, slots = self._obs_select(obs, "step")   # KeyError before any library call
         th = () if thermal is None else (thermal,) if isinstance(thermal, str) else tuple(thermal)
@@ -308,6 +313,10 @@ class Context:
         for k in pk:
             if k not in ("ucmd", "limiter"):
                 raise KeyError(f"step: unknown pack row {k!r} (one of ('ucmd', 'limiter'))")
+        ag = () if aging is None else (aging,) if isinstance(aging, str) else tuple(aging)
+        for k in ag:
+            if k != "rate":
+                raise KeyError(f"step: unknown aging row {k!r} (one of ('rate',))")
         tcs = None if tc is None else tc_grid(tc, nsteps, n)
         out = {}
         tr = _lib.Traj()
@@ -321,7 +330,22 @@ class Context:
         tcp = tcs.ctypes.data_as(C.c_void_p) if tcs is not None else None
         rec = None if fields is None else np.empty((nsteps, slots.size, n))
         vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
-        if pack is not None:
+        if aging is not None:
+            for k in th:
+                out[k] = np.empty((nsteps, n))
+            series = getattr(self, "_pack_series", 0)
+            if "ucmd" in pk:
+                out["ucmd"] = np.empty((nsteps, n))
+            if "limiter" in pk:
+                out["limiter"] = np.empty((nsteps, n // series if series else n), dtype=np.int32)
+            nreact, mask = getattr(self, "_aging", (0, 0))   # (0, 0): no begin, the library refuses the call
+            if "rate" in ag:
+                out["rate"] = np.empty((nsteps, max(bin(mask).count("1") * nreact, 1), n))
+            ns = 0 if fields is None else int(slots.size)
+            check(self.L.mpcekf_step_ex_aging(self.h, int(nsteps), tcp, C.byref(tr), iptr(slots) if ns else None, ns,
+                                              vp(rec) if ns else None, vp(out.get("temp")), vp(out.get("heat")),
+                                              vp(out.get("ucmd")), vp(out.get("limiter")), vp(out.get("rate")), 0))
+        elif pack is not None:
             for k in th:
                 out[k] = np.empty((nsteps, n))
             series = getattr(self, "_pack_series", 0)   # 0: no begin, the library refuses the call
@@ -639,6 +663,86 @@ class Context:
         """Drop the pack (mpcekf_pack_end): every cell is on its own again."""
         check(self.L.mpcekf_pack_end(self.h))
         self._pack_series = 0
+
+    # -- side-reaction losses per cell (plating, SEI) -----------------------
+    AGING_PARAMS = _lib.AGING_PARAMS
+    AGING_FIELDS = _lib.AGING_FIELDS
+    AGING_SOURCES = _lib.AGING_SOURCES
+
+    @classmethod
+    def _aging_args(cls, n, reactions, sources):
+        """aging_begin's arguments -> (float64 params [nreact][5][n], the sources' bit mask);
+        every check mpcekf_aging_begin makes, before the library is called."""
+        if isinstance(reactions, dict):
+            reactions = (reactions,)
+        reactions = tuple(reactions)
+        if not 1 <= len(reactions) <= 4:
+            raise ValueError(f"aging_begin: {len(reactions)} reactions: 1 to 4")
+        src = (sources,) if isinstance(sources, str) else tuple(sources)
+        mask = 0
+        for k in src:
+            if k not in cls.AGING_SOURCES:
+                raise ValueError(f"aging_begin: unknown source {k!r} (of {tuple(cls.AGING_SOURCES)})")
+            mask |= cls.AGING_SOURCES[k]
+        if not mask:
+            raise ValueError(f"aging_begin: no source given (of {tuple(cls.AGING_SOURCES)})")
+        par = np.empty((len(reactions), len(cls.AGING_PARAMS), n))
+        for r, d in enumerate(reactions):
+            d = dict(d)
+            d.setdefault("gate", np.inf)
+            for k in d:
+                if k not in cls.AGING_PARAMS:
+                    raise ValueError(f"aging_begin: reaction {r}: unknown parameter {k!r} (of {cls.AGING_PARAMS})")
+            for i, k in enumerate(cls.AGING_PARAMS):
+                if k not in d:
+                    raise ValueError(f"aging_begin: reaction {r}: {k} is missing")
+                par[r, i] = cls._per_cell(n, k, d[k], who=f"aging_begin: reaction {r}")
+            i0, U, al, Ea, gate = par[r]
+            if not (np.isfinite(i0) & (i0 >= 0)).all():
+                raise ValueError(f"aging_begin: reaction {r}: i0 must be finite and >= 0")
+            if not (np.isfinite(U).all() and np.isfinite(Ea).all()):
+                raise ValueError(f"aging_begin: reaction {r}: U and Ea must be finite")
+            if not (np.isfinite(al) & (al > 0)).all():
+                raise ValueError(f"aging_begin: reaction {r}: alpha must be finite and > 0")
+            if np.isnan(gate).any():
+                raise ValueError(f"aging_begin: reaction {r}: gate is NaN (inf: always on)")
+        return np.ascontiguousarray(par), mask
+
+    def aging_begin(self, reactions, sources=("est",)):
+        """Give the context side reactions (mpcekf_aging_begin): ``reactions`` is one dict or up
+        to four, each of i0 (A), U (V), alpha, Ea (J/mol) and gate (V, default inf: always on),
+        each a scalar or [ncells].  After every fused step each reaction's Tafel current
+        j = i0 exp(Ea/R (1/Tref - 1/T)) exp(-alpha F (phi - U) / (R T)) is added to the cell's
+        record where phi - U < gate, with phi the EKF's phise ("est"), the plant's negPhise0
+        ("plant"), or both (``sources``).  A second call replaces the first and resets the record."""
+        par, mask = self._aging_args(self.n, reactions, sources)
+        check(self.L.mpcekf_aging_begin(self.h, int(par.shape[0]), mask, dptr(par)))
+        self._aging = (int(par.shape[0]), mask)
+
+    def aging_get(self, source, react, fields=None):
+        """{name: [ncells] float64} of the aging record (mpcekf_aging_get) of ``source`` ("est" or
+        "plant") and reaction ``react``: ``fields`` names of AGING_FIELDS (default all).  Charge in
+        Ah = q_sum * Ts / 3600; steps and nskip are per source."""
+        if source not in self.AGING_SOURCES:
+            raise KeyError(f"aging_get: unknown source {source!r} (of {tuple(self.AGING_SOURCES)})")
+        names = self.AGING_FIELDS if fields is None else (fields,) if isinstance(fields, str) else tuple(fields)
+        for k in names:
+            if k not in self.AGING_FIELDS:
+                raise KeyError(f"aging_get: unknown field {k!r} (one of {self.AGING_FIELDS})")
+        ids = np.asarray([self.AGING_FIELDS.index(k) for k in names], dtype=np.int32)
+        vals = np.empty((ids.size, self.n))
+        check(self.L.mpcekf_aging_get(self.h, self.AGING_SOURCES[source], int(react), int(ids.size), iptr(ids), dptr(vals)))
+        return {k: vals[i] for i, k in enumerate(names)}
+
+    def aging_record(self):
+        """{source: [one aging_get dict per reaction]} for every enabled source."""
+        nreact, mask = getattr(self, "_aging", (0, 0))
+        return {k: [self.aging_get(k, r) for r in range(nreact)] for k, b in self.AGING_SOURCES.items() if mask & b}
+
+    def aging_end(self):
+        """Drop the side reactions and their record (mpcekf_aging_end)."""
+        check(self.L.mpcekf_aging_end(self.h))
+        self._aging = (0, 0)
 
     def set_timing(self, enable=True):
         """enable: True/1 = every step; N > 1 = sample every N-th step (less perturbation)."""
@@ -993,7 +1097,7 @@ def _thermal_begin(ctx, thermal):
 
 
 def runMPC(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=None, obs=None, limits=None,
-           thermal=None, pack=None):
+           thermal=None, pack=None, aging=None):
     """runMPC.m:72-112 for a batch of cells; returns trajectories [nsteps, ncells].
     tc_traj [nsteps, ncells] (degC): a temperature profile (TC is the initial one).
     obs: the plant's observables of every step as out["obs"] (Context.step's obs=).
@@ -1006,7 +1110,9 @@ def runMPC(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=None,
     cells' temperature; adds out["limits"], the values in force at the last step.
     pack: dict(series=S): the cells form ncells // S series strings, each charged with the one
     current its weakest cell accepts (Context.pack_begin); out["u"] is the applied current, and
-    out["ucmd"], out["limiter"] and out["pack"], the pack's record, are added."""
+    out["ucmd"], out["limiter"] and out["pack"], the pack's record, are added.
+    aging: a dict of Context.aging_begin's keywords (reactions, sources): adds out["rate"], every
+    step's side-reaction currents, and out["aging"], the record (Context.aging_record)."""
     SOC0 = np.atleast_1d(np.asarray(SOC0, dtype=np.float64))
     n = ncells or SOC0.shape[0]
     with Context(rom, n, cfg, device) as ctx:
@@ -1017,8 +1123,12 @@ def runMPC(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=None,
             _thermal_begin(ctx, thermal)
         if pack:
             ctx.pack_begin(**pack)
+        if aging:
+            ctx.aging_begin(**aging)
         out = ctx.step(nsteps, tc=tc_traj, obs=obs, thermal=("temp", "heat") if thermal else None,
-                       pack=("ucmd", "limiter") if pack else None)
+                       pack=("ucmd", "limiter") if pack else None, aging=("rate",) if aging else None)
+        if aging:
+            out["aging"] = ctx.aging_record()
         if pack:
             out["pack"] = ctx.pack_get()
         if thermal:
@@ -1030,7 +1140,7 @@ def runMPC(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=None,
 
 
 def run_summary(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=None, limits=None, reach=None,
-                obs=None, chunk=None, thermal=None, pack=None):
+                obs=None, chunk=None, thermal=None, pack=None, aging=None):
     """runMPC.m:72-112 for a batch of cells, read out as the per-cell charge summary instead of
     trajectories: {field: [ncells]} of Context.get_summary plus "status".  limits: as runMPC's
     (a protocol sweep); reach, obs: Context.summary_begin's; tc_traj [nsteps, ncells] (degC): a
@@ -1038,7 +1148,7 @@ def run_summary(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=
     a chunk bounds the host array each call converts).  Neither host nor device memory grows
     with nsteps.  thermal: as runMPC's, its "schedule" included (no tc_traj); adds "thermal", the
     model's record.  pack: as runMPC's; adds "pack", the pack's record, beside the summary (whose
-    currents are the applied ones)."""
+    currents are the applied ones).  aging: as runMPC's; adds "aging", the side reactions' record."""
     SOC0 = np.atleast_1d(np.asarray(SOC0, dtype=np.float64))
     n = ncells or SOC0.shape[0]
     nsteps = int(nsteps)
@@ -1054,11 +1164,15 @@ def run_summary(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=
             _thermal_begin(ctx, thermal)
         if pack:
             ctx.pack_begin(**pack)
+        if aging:
+            ctx.aging_begin(**aging)
         ctx.summary_begin(reach=reach, obs=obs)
         for k in range(0, nsteps, max(chunk, 1)):
             m = min(chunk, nsteps - k)
             ctx.step_summary(m, tc=None if tcs is None else tcs[k:k + m])
         out = ctx.get_summary()
+        if aging:
+            out["aging"] = ctx.aging_record()
         if pack:
             out["pack"] = ctx.pack_get()
         if thermal:
