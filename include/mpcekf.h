@@ -662,8 +662,8 @@ int mpcekf_thermal_schedule_end(mpcekf_ctx *ctx);
  * replay included.  The stage route (mpcekf_mpc_step(_ex)) is not coupled: a host loop over the
  * stage calls sees every cell's own command, as it does not advance the thermal model either.
  * The pack's kernel is not one of mpcekf_set_timing's five slots.
- * Not modelled: parallel groups, balancing or bypass currents, strings of unequal length, heat
- * conduction between neighbouring cells. */
+ * Heat conduction between neighbouring cells of a string: mpcekf_thermal_couple, below.
+ * Not modelled: parallel groups, balancing or bypass currents, strings of unequal length. */
 enum { MPCEKF_PK_NLIM = 0, MPCEKF_PK_STEPS, MPCEKF_PK_HEADROOM, MPCEKF_NPK };
 /* Makes the context a pack of ncells / series strings of `series` cells each, allocates the
  * record (first call) and resets it; a second begin replaces the first and resets the record.
@@ -765,6 +765,66 @@ int mpcekf_aging_end(mpcekf_ctx *ctx);
 int mpcekf_step_ex_aging(mpcekf_ctx *ctx, int32_t nsteps, const double *tc_degC, const mpcekf_traj *traj,
                          const int32_t *slots, int32_t nslots, double *obs, double *temp, double *heat, double *ucmd,
                          int32_t *limiter, double *rate, int32_t outputs_on_device);
+
+/* ---- heat conduction between neighbouring cells of a pack string (not part of the reference interface) ----
+ * The thermal model above exchanges heat with each cell's own ambient only, so a string of
+ * identical cells stays identical.  In a module the inner cells run hotter than the end cells.
+ * A context that has both a thermal model (mpcekf_thermal_begin) and a pack (mpcekf_pack_begin)
+ * can be given links: r_link[c] is the thermal resistance in K/W between cell c and cell c+1.
+ * It is used only when both cells are in the same string; the entry of a string's last cell is
+ * ignored; +inf means no link.
+ * Per cell c at in-string position p = c mod S, after fused step t: T, q and loss are exactly
+ * as in the thermal model's recurrence.  Tl and Tr are the temperatures that step t used for
+ * the cells c-1 and c+1: their temp[t], not values already advanced in this launch.  Every line
+ * one or more separately rounded fp64 operations in exactly this order (no contraction into
+ * fused multiply-adds, IEEE division):
+ *   qn = +0.0;  nl = 0
+ *   if p > 0     and isfinite(r_link[c-1]):  dl = Tl - T;  qn = qn + dl / r_link[c-1];  nl += 1
+ *   if p < S - 1 and isfinite(r_link[c]):    dr = Tr - T;  qn = qn + dr / r_link[c];    nl += 1
+ *   Tn = nl == 0 ? T + ((q - loss) * Ts) / Cth              the uncoupled line, bit for bit
+ *                : T + (((q - loss) + qn) * Ts) / Cth
+ *   T <- Tn if isfinite(Tn) and Tn <= 100; otherwise T is held: the accept-or-hold rule is unchanged
+ * A cell whose T is held because it is in error (its q is NaN) keeps its finite T, and its
+ * neighbours still conduct to and from it.  Tl - T on one side of a link and T - Tr on the other
+ * are exact negatives (an fp64 subtraction with its operands swapped gives the negated result),
+ * and both are divided by the same r_link: the two flows over a link cancel exactly, so
+ * conduction moves heat and makes none.
+ * The record, per cell, every value a double, step indices exact integers that count the
+ * model's steps from 1 across calls, as T_MAX_STEP does:
+ *   NB_SUM       qn added in step order, plain fp64 additions from +0: only finite values, and
+ *                only on steps with nl > 0 (energy in J = NB_SUM * Ts)
+ *   DT_MAX, DT_MAX_STEP   the largest |dl| or |dr| over the cell's finite links and the step it
+ *                occurred in; within a step the left link is examined first; replaced only on a
+ *                strict >.  NaN / 0 before the first such step
+ * The links are a property of the context: once set, mpcekf_step, _step_ex, _step_ex_obs,
+ * _step_ex_thermal, _step_ex_pack, _step_ex_aging, _step_summary and _step_ex_couple all run
+ * the coupled step, graph replay included.  The stage route does not advance the model, as
+ * ever.  S = 1, or every link +inf, runs the uncoupled model's bits.  The kernels are not among
+ * mpcekf_set_timing's five slots.
+ * Not modelled: 2-D or 3-D neighbourhoods, conduction between strings, tab or busbar heat. */
+enum { MPCEKF_TCR_NB_SUM = 0, MPCEKF_TCR_DT_MAX, MPCEKF_TCR_DT_MAX_STEP, MPCEKF_NTCR };
+/* Sets the links: r_link [ncells].  Allocates the coupling's device buffers (first call) and
+ * resets the record; a second call replaces the links and resets the record.  Every entry is
+ * validated, the ignored string-end entries included, so a later mpcekf_pack_begin with another
+ * series is safe: a second mpcekf_pack_begin keeps the coupling, the links following the new
+ * strings; a second mpcekf_thermal_begin keeps it and resets its record.
+ * MPCEKF_E_ARG (nothing changed): a NULL ctx or r_link; an entry that is NaN or not > 0 (+inf
+ * allowed).  MPCEKF_E_STATE (nothing changed): no thermal model, or no pack. */
+int mpcekf_thermal_couple(mpcekf_ctx *ctx, const double *r_link);
+/* values [nfields][ncells]: row i = field fields[i] (distinct MPCEKF_TCR_* ids).
+ * MPCEKF_E_STATE without links; MPCEKF_E_ARG: a NULL pointer, nfields outside
+ * 1..MPCEKF_NTCR, an unknown or repeated id. */
+int mpcekf_thermal_couple_get(mpcekf_ctx *ctx, int32_t nfields, const int32_t *fields, double *values);
+/* Frees the links and the record; the context then runs the uncoupled model again.
+ * mpcekf_thermal_end and mpcekf_pack_end do the same implicitly.  A no-op without links. */
+int mpcekf_thermal_couple_end(mpcekf_ctx *ctx);
+/* mpcekf_step_ex_aging's arguments (rate needs an aging record: MPCEKF_E_STATE without) plus
+ * cond [nsteps][ncells] (host, or device when outputs_on_device != 0; may be NULL): each step's
+ * qn, +0.0 where nl == 0.  MPCEKF_E_STATE without links; a refused call leaves the context and
+ * the records as they were. */
+int mpcekf_step_ex_couple(mpcekf_ctx *ctx, int32_t nsteps, const double *tc_degC, const mpcekf_traj *traj,
+                          const int32_t *slots, int32_t nslots, double *obs, double *temp, double *heat, double *ucmd,
+                          int32_t *limiter, double *rate, double *cond, int32_t outputs_on_device);
 
 /* ---- device memory (not part of the reference interface) ----
  * Device buffers for outputs_on_device calls, allocated by the library's own HIP

@@ -81,6 +81,16 @@
  *                       (j, s) = field idx(j) of derating map s over the grid; sets: [] (map 1) or
  *                       ncells 1-based map numbers.  'getlimits' then returns the values in force
  *                       mpcekf_mex('thermalscheduleend', h)            mpcekf_thermal_schedule_end
+ *                       mpcekf_mex('thermalcouple', h, r_link)         mpcekf_thermal_couple
+ *                       heat conduction between neighbouring cells of a pack string (needs
+ *                       'thermalbegin' and 'packbegin'): r_link, ncells resistances (K/W, Inf: no
+ *                       link) between cell c and c+1, used where both are in one string
+ *   s                 = mpcekf_mex('thermalcoupleget', h)              mpcekf_thermal_couple_get
+ *                       struct of ncells x 1 column vectors: nb_sum, dt_max, dt_max_step (MPCEKF_TCR_*)
+ *                       mpcekf_mex('thermalcoupleend', h)              mpcekf_thermal_couple_end
+ *   [u,v,soc,phise,nexec,temp,heat,cond] = mpcekf_mex('stepexcouple', h, nsteps)   mpcekf_step_ex_couple
+ *                       'stepthermal' on a context with links, plus the heat each cell's
+ *                       neighbours conducted to it in every step (W), ncells x nsteps
  *                       mpcekf_mex('packbegin', h, series)             mpcekf_pack_begin
  *                       the cells form ncells / series strings of `series` cells in series (cells
  *                       (g-1)*series+1 .. g*series are string g); from then on every 'step' /
@@ -440,6 +450,7 @@ static void gateway(mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
                                             "clearlimits", "summarybegin", "stepsummary", "getsummary", "summaryend",
                                             "thermalbegin", "thermalget", "thermalend", "stepthermal",
                                             "thermalschedule", "thermalscheduleend",
+                                            "thermalcouple", "thermalcoupleget", "thermalcoupleend", "stepexcouple",
                                             "packbegin", "packget", "packend", "stepexpack",
                                             "agingbegin", "agingget", "agingend", "stepexaging"};
   int known = 0;
@@ -579,6 +590,26 @@ static void gateway(mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         if (!(sd[j] >= 1 && sd[j] <= (double)schsets) || sd[j] != (double)(int32_t)sd[j])
           mexErrMsgIdAndTxt("mpcekf:arg", "thermalschedule: sets(%zu) = %g is not a map 1..%zu", j + 1, sd[j], schsets);
     }
+  }
+  /* the coupling commands likewise: output count, the links' class, an nsteps that is no
+     non-negative integer */
+  const int tcset = !strcmp(cmd, "thermalcouple"), steptc = !strcmp(cmd, "stepexcouple");
+  int32_t tcsteps = 0;
+  if ((tcset || !strcmp(cmd, "thermalcoupleend")) && g_nlhs > 0) mexErrMsgIdAndTxt("mpcekf:arg", "%s: no output", cmd);
+  if (!strcmp(cmd, "thermalcoupleget") && g_nlhs > 1) mexErrMsgIdAndTxt("mpcekf:arg", "thermalcoupleget: at most 1 output");
+  if (steptc && g_nlhs > 8)
+    mexErrMsgIdAndTxt("mpcekf:arg", "stepexcouple: at most 8 outputs [u, v, soc, phise, nexec, temp, heat, cond]");
+  if (tcset) {
+    need(nrhs, 3, "'thermalcouple', h, r_link");
+    if (!mxIsDouble(prhs[2]) || mxIsComplex(prhs[2]))
+      mexErrMsgIdAndTxt("mpcekf:arg", "thermalcouple: r_link: expected ncells real doubles");
+  }
+  if (steptc) {
+    need(nrhs, 3, "'stepexcouple', h, nsteps");
+    const double nsd = scalar(prhs[2], "nsteps");
+    if (!(nsd >= 0 && nsd <= 2147483647.0) || nsd != (double)(int32_t)nsd)
+      mexErrMsgIdAndTxt("mpcekf:arg", "nsteps: expected a non-negative integer");
+    tcsteps = (int32_t)nsd;
   }
   /* the pack commands likewise: output count, a series that is no positive integer, an nsteps
      that is no non-negative integer, a tc of the wrong class */
@@ -869,6 +900,31 @@ static void gateway(mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
     chk(rc);
   } else if (!strcmp(cmd, "thermalscheduleend")) {
     chk(mpcekf_thermal_schedule_end(h));
+  } else if (tcset) {
+    chk(mpcekf_thermal_couple(h, dvec(prhs[2], nc, "thermalcouple: r_link (ncells)")));
+  } else if (!strcmp(cmd, "thermalcoupleget")) {
+    static const char *const tc_names[MPCEKF_NTCR] = {"nb_sum", "dt_max", "dt_max_step"};
+    int32_t ids[MPCEKF_NTCR];
+    double *vals = (double *)mxMalloc((size_t)MPCEKF_NTCR * nc * sizeof(double) + 8);
+    for (int f = 0; f < MPCEKF_NTCR; ++f) ids[f] = f;
+    chk(mpcekf_thermal_couple_get(h, MPCEKF_NTCR, ids, vals));
+    plhs[0] = mxCreateStructMatrix(1, 1, MPCEKF_NTCR, (const char **)tc_names);
+    for (int f = 0; f < MPCEKF_NTCR; ++f) {
+      mxArray *a = dmat(nc, 1);
+      if (nc) memcpy(mxGetDoubles(a), vals + (size_t)f * nc, nc * sizeof(double));
+      mxSetField(plhs[0], 0, tc_names[f], a);
+    }
+    mxFree(vals);
+  } else if (!strcmp(cmd, "thermalcoupleend")) {
+    chk(mpcekf_thermal_couple_end(h));
+  } else if (steptc) {
+    for (int i = 0; i < 8; ++i) plhs[i] = i == 4 ? imat(nc, (size_t)tcsteps) : dmat(nc, (size_t)tcsteps);
+    mpcekf_traj tr;
+    memset(&tr, 0, sizeof tr);
+    tr.u = mxGetDoubles(plhs[0]); tr.v = mxGetDoubles(plhs[1]); tr.soc = mxGetDoubles(plhs[2]);
+    tr.phise = mxGetDoubles(plhs[3]); tr.nexec = (int32_t *)mxGetData(plhs[4]);
+    chk(mpcekf_step_ex_couple(h, tcsteps, NULL, &tr, NULL, 0, NULL, mxGetDoubles(plhs[5]), mxGetDoubles(plhs[6]), NULL,
+                              NULL, NULL, mxGetDoubles(plhs[7]), 0));
   } else if (pkbegin) {
     chk(mpcekf_pack_begin(h, pkseries));
     *series_of(h) = pkseries;

@@ -108,6 +108,7 @@ EXPORTS = [
     "mpcekf_pack_begin", "mpcekf_pack_get", "mpcekf_pack_end", "mpcekf_step_ex_pack",
     "mpcekf_aging_begin", "mpcekf_aging_get", "mpcekf_aging_end", "mpcekf_step_ex_aging",
     "mpcekf_thermal_schedule", "mpcekf_thermal_schedule_end",
+    "mpcekf_thermal_couple", "mpcekf_thermal_couple_get", "mpcekf_thermal_couple_end", "mpcekf_step_ex_couple",
     # the _async stage twins (include/mpcekf.h)
     "mpcekf_plant_step_async", "mpcekf_ekf_step_async", "mpcekf_linearize_async", "mpcekf_lin_fields_async",
     "mpcekf_mpc_step_async", "mpcekf_mpc_step_ex_async", "mpcekf_mpc_diag_async", "mpcekf_get_scalars_async",
@@ -195,6 +196,11 @@ def load():
     L.mpcekf_aging_get.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, _ip, _dp]
     L.mpcekf_aging_end.argtypes = [vp]
     L.mpcekf_step_ex_aging.argtypes = [vp, C.c_int32, vp, C.POINTER(Traj), _ip, C.c_int32, vp, vp, vp, vp, vp, vp, C.c_int32]
+    L.mpcekf_thermal_couple.argtypes = [vp, _dp]
+    L.mpcekf_thermal_couple_get.argtypes = [vp, C.c_int32, _ip, _dp]
+    L.mpcekf_thermal_couple_end.argtypes = [vp]
+    L.mpcekf_step_ex_couple.argtypes = [vp, C.c_int32, vp, C.POINTER(Traj), _ip, C.c_int32, vp, vp, vp, vp, vp, vp, vp,
+                                        C.c_int32]
     for nm in ("plant_step", "ekf_step", "linearize", "lin_fields", "mpc_step", "mpc_step_ex", "mpc_diag",
                "get_scalars", "plant_step_obs", "plant_obs_slots"):   # the _async twins take the synchronous call's arguments
         getattr(L, f"mpcekf_{nm}_async").argtypes = getattr(L, f"mpcekf_{nm}").argtypes

@@ -30,6 +30,7 @@
 #include "mpcekf_summary.hpp"
 #include "mpcekf_thermal.hpp"
 #include "mpcekf_thermal_sched.hpp"
+#include "mpcekf_thermal_couple.hpp"
 
 using namespace mk;
 namespace mk {
@@ -289,6 +290,11 @@ struct mpcekf_ctx {
   // every fused step couples its strings with k_pack after Hildreth.
   double *d_pk = nullptr;
   int32_t pk_series = 0;
+  // mpcekf_thermal_couple .. _couple_end (needs a model and a pack): the record [NTCR][n], the
+  // links [n] and the snapshot pair [2][n] the neighbours are read from (mpcekf_thermal_couple.hip).
+  // d_tc != nullptr: every fused call seeds the snapshot and every step ends with
+  // k_thermal_couple(_sched) in k_thermal(_sched)'s place.
+  double *d_tc = nullptr, *d_tc_link = nullptr, *d_tc_snap = nullptr;
   // mpcekf_aging_begin .. _end: the record [AG_ROWS][n], the parameters [ag_nreact][NAGP][n]
   // (room for AG_MAXR), and the rows k_aging reads when the call has none of its own: the
   // step's phise row [n] (source EST, no traj.phise) and the plant's negPhise0 row [n] (source
@@ -1213,7 +1219,7 @@ int mpcekf_ctx_destroy(mpcekf_ctx *X) {
                   X->w.prob, X->w.X, X->w.R, X->w.K, X->w.hii, X->w.it, X->w.smin, X->d_lin, X->d_zsoc, X->d_mb, X->d_uk1p,
                   X->w.q, X->w.list, X->w.hist, X->d_poly, X->d_szk, X->d_sxg, X->d_sxm, X->d_slin, X->d_sv, X->d_zslot,
                   X->d_obs_blob, X->d_obs, X->d_obs_plan, X->d_lim, X->d_sch_hdr, X->d_sch_tab, X->d_sch_val, X->d_sch_set, X->d_sum, X->d_sum_reach, X->d_sum_obs,
-                  X->d_sum_ring, X->d_pk, X->d_ag, X->d_ag_par, X->d_ag_phi, X->d_ag_obs, X->d_ag_plan, X->d_th, X->d_th_par, X->d_th_i, X->d_th_ocv, X->d_hot, X->d_hot_i, X->d_hotp, X->d_hotp_i};
+                  X->d_sum_ring, X->d_pk, X->d_tc, X->d_tc_link, X->d_tc_snap, X->d_ag, X->d_ag_par, X->d_ag_phi, X->d_ag_obs, X->d_ag_plan, X->d_th, X->d_th_par, X->d_th_i, X->d_th_ocv, X->d_hot, X->d_hot_i, X->d_hotp, X->d_hotp_i};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   for (auto &g : X->graphs) (void)hipGraphExecDestroy(g.exec);
@@ -1339,10 +1345,14 @@ static int lerr(int rc, const char *what) {
 // k_obs_traj launch of the context's own, which leaves the caller's rows what they were); rate
 // [nsteps][nsrc * nreact][ncells] (mpcekf_step_ex_aging) is one more output field, written by
 // k_aging.
+// A coupled context (mpcekf_thermal_couple): k_couple_seed once before the call's first step,
+// and k_thermal_couple(_sched) in k_thermal(_sched)'s place reads each cell's neighbours from
+// the snapshot of the step's parity; cond [nsteps][ncells] (mpcekf_step_ex_couple) is one more
+// output field, written by that kernel.
 static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const mpcekf_traj *tr,
                      const int32_t *slots, int32_t nslots, double *obs, int32_t outputs_on_device,
                      bool sum = false, double *temp = nullptr, double *heat = nullptr, double *ucmd = nullptr,
-                     int32_t *limiter = nullptr, double *rate = nullptr) {
+                     int32_t *limiter = nullptr, double *rate = nullptr, double *cond = nullptr) {
   // a thermal context owns the temperature: refused before anything of the context changes
   if (X && X->d_th && tc_degC)
     return fail(MPCEKF_E_ARG, "step: tc_degC on a thermal context (mpcekf_thermal_begin): the model sets the temperature");
@@ -1353,6 +1363,7 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
   const bool thermal = X->d_th != nullptr;
   const bool pack = X->d_pk != nullptr;
   const bool aging = X->d_ag != nullptr;
+  const bool coupled = X->d_tc != nullptr;  // thermal && pack: either's end ends the coupling
   const bool ag_est = aging && (X->ag_sources & MPCEKF_AG_SRC_EST), ag_plant = aging && (X->ag_sources & MPCEKF_AG_SRC_PLANT);
   if (sum && X->sum_slot >= 0) {  // checked by mpcekf_summary_begin
     slots = &X->sum_slot;
@@ -1396,7 +1407,8 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
            {ucmd, 8, 1, nullptr},                                 // k_pack's rows (a pack context's only)
            {limiter, 4, 1, nullptr, pack ? n / (size_t)X->pk_series : 0},  // [nsteps][nstrings]
            // k_aging's rows (an aging context's only): [nsteps][nsrc * nreact][ncells]
-           {rate, 8, aging ? (size_t)(((int)ag_est + (int)ag_plant) * X->ag_nreact) : 0, nullptr}};
+           {rate, 8, aging ? (size_t)(((int)ag_est + (int)ag_plant) * X->ag_nreact) : 0, nullptr},
+           {cond, 8, 1, nullptr}};  // k_thermal_couple's row (a coupled context's only)
   constexpr int NF = sizeof(f) / sizeof(f[0]);
   auto step_bytes = [&](const F &e) -> size_t { return (e.rows ? e.rows : n) * e.width * e.esz; };  // one step's block
   const double *dtc = tc_degC;  // [nsteps][n] device copy of the per-step temperatures
@@ -1506,6 +1518,9 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
     // the schedule at the temperature the call's first step finds (mpcekf_thermal_sched.hip);
     // before the first timing event, so no slot of mpcekf_set_timing counts it
     if (sched && nsteps > 0 && (rc = lerr(launch_sched(ksch, X->stream), "sched"))) return rc;
+    // the temperatures the call's first step finds, for its neighbours (mpcekf_thermal_couple.hip)
+    if (coupled && nsteps > 0 && (rc = lerr(launch_couple_seed(X->s.Tc, X->d_tc_snap, X->n, X->stream), "couple_seed")))
+      return rc;
     for (int k = 0; k < nsteps; ++k) {
       const int t = k + 1;
       // sampled steps: every timing_every-th (k = every-1, 2 every-1, ...: with every dividing
@@ -1718,8 +1733,20 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
         q.th0n = X->r.th0n;
         q.th100n = X->r.th100n;
         q.Ts = X->r.Ts;
-        // a schedule: the next step's limits at the temperature this launch leaves
-        if (sched && k + 1 < nsteps) {
+        // a schedule: the next step's limits at the temperature this launch leaves; links: the
+        // neighbours from the snapshot of the call-relative parity
+        if (coupled) {
+          KCouple h{};
+          h.rlink = X->d_tc_link;
+          h.rec = X->d_tc;
+          h.snap_in = X->d_tc_snap + (size_t)(k & 1) * n;
+          h.snap_out = X->d_tc_snap + (size_t)((k + 1) & 1) * n;
+          h.cond = (double *)row(20, k);
+          h.series = X->pk_series;
+          rc = sched && k + 1 < nsteps ? lerr(launch_thermal_couple_sched(q, h, ksch, X->stream), "thermal_couple_sched")
+                                       : lerr(launch_thermal_couple(q, h, X->stream), "thermal_couple");
+          if (rc) return rc;
+        } else if (sched && k + 1 < nsteps) {
           if ((rc = lerr(launch_thermal_sched(q, ksch, X->stream), "thermal_sched"))) return rc;
         } else if ((rc = lerr(launch_thermal(q, X->stream), "thermal"))) {
           return rc;
@@ -1740,7 +1767,11 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
                                   // rows below): 0 on a context without one -- mpcekf_aging_end, and a
                                   // begin that changes nreact or sources, retire the graphs that name one
                                   (uintptr_t)X->d_ag, (uintptr_t)(X->ag_nreact | X->ag_sources << 8),
-                                  (uintptr_t)(aging ? X->d_ag_phi : nullptr), (uintptr_t)(aging ? X->d_ag_obs : nullptr)};
+                                  (uintptr_t)(aging ? X->d_ag_phi : nullptr), (uintptr_t)(aging ? X->d_ag_obs : nullptr),
+                                  // the coupling's buffers eleventh to thirteenth (its cond rows are among
+                                  // the output rows below): 0 on a context without links --
+                                  // mpcekf_thermal_couple_end retires the graphs that name them
+                                  (uintptr_t)X->d_tc, (uintptr_t)X->d_tc_link, (uintptr_t)X->d_tc_snap};
     for (const F &e : f) key.push_back((uintptr_t)e.dev);
     key.push_back((uintptr_t)osel.plan);  // a regrown plan buffer retires the graphs that named the old one
     key.push_back((uintptr_t)nslots);
@@ -2111,6 +2142,8 @@ int mpcekf_thermal_begin(mpcekf_ctx *X, const double *params, int32_t nocv, cons
   HIPCHK(hipMemcpyAsync(tab, ocv, (size_t)nocv * 8, hipMemcpyHostToDevice, X->stream));
   if (nc && t0_degC) HIPCHK(hipMemcpyAsync(X->s.Tc, t0_degC, nc * 8, hipMemcpyHostToDevice, X->stream));
   if ((rc = lerr(launch_thermal_reset(rec, X->n, X->stream), "thermal_reset"))) return rc;
+  // a second begin keeps the links; the coupling's step indices are the model's, so its record restarts too
+  if (X->d_tc && (rc = lerr(launch_couple_reset(X->d_tc, X->n, X->stream), "couple_reset"))) return rc;
   HIPCHK(hipStreamSynchronize(X->stream));
   return MPCEKF_OK;
 }
@@ -2145,6 +2178,7 @@ int mpcekf_thermal_end(mpcekf_ctx *X) {
   if (!X->d_th) return MPCEKF_OK;
   int rc = mpcekf_thermal_schedule_end(X);  // the scheduled fields back to set_limits' / the configuration's values
   if (rc) return rc;
+  if ((rc = mpcekf_thermal_couple_end(X))) return rc;  // links need a model
   HIPCHK(hipSetDevice(X->device));
   HIPCHK(hipStreamSynchronize(X->stream));
   retire_thermal_graphs(X);
@@ -2305,6 +2339,8 @@ int mpcekf_pack_get(mpcekf_ctx *X, int32_t nfields, const int32_t *fields, doubl
 int mpcekf_pack_end(mpcekf_ctx *X) {
   if (!X) return fail(MPCEKF_E_ARG, "pack_end: null ctx");
   if (!X->d_pk) return MPCEKF_OK;
+  int rc = mpcekf_thermal_couple_end(X);  // links need strings
+  if (rc) return rc;
   HIPCHK(hipSetDevice(X->device));
   HIPCHK(hipStreamSynchronize(X->stream));
   // the graphs captured on a pack context launch k_pack on the record: retired before it is freed
@@ -2486,6 +2522,99 @@ int mpcekf_step_ex_aging(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, c
   if ((ucmd || limiter) && !X->d_pk)
     return fail(MPCEKF_E_STATE, "step_ex_aging: ucmd / limiter rows: call mpcekf_pack_begin first");
   return step_impl(X, nsteps, tc_degC, tr, slots, nslots, obs, outputs_on_device, false, temp, heat, ucmd, limiter, rate);
+}
+
+// ---- heat conduction between neighbouring cells of a pack string (mpcekf_thermal_couple.hip) ----
+static_assert(NTCR == MPCEKF_NTCR && TCR_NB_SUM == MPCEKF_TCR_NB_SUM && TCR_DT_MAX == MPCEKF_TCR_DT_MAX &&
+                  TCR_DT_MAX_STEP == MPCEKF_TCR_DT_MAX_STEP,
+              "mpcekf_thermal_couple.hpp's rows are include/mpcekf.h's MPCEKF_TCR_*");
+
+int mpcekf_thermal_couple(mpcekf_ctx *X, const double *r_link) {
+  if (!X) return fail(MPCEKF_E_ARG, "thermal_couple: null ctx");
+  if (!r_link) return fail(MPCEKF_E_ARG, "thermal_couple: null r_link");
+  const size_t nc = (size_t)X->n;
+  // every entry, the string ends' included: a later mpcekf_pack_begin may make any of them a link
+  for (size_t c = 0; c < nc; ++c)
+    if (!(r_link[c] > 0))
+      return fail(MPCEKF_E_ARG, "thermal_couple: r_link[%zu] = %g: must be > 0 (K/W; +inf: no link)", c, r_link[c]);
+  if (!X->d_th) return fail(MPCEKF_E_STATE, "thermal_couple: call mpcekf_thermal_begin first");
+  if (!X->d_pk) return fail(MPCEKF_E_STATE, "thermal_couple: call mpcekf_pack_begin first");
+  int rc;
+  HIPCHK(hipSetDevice(X->device));
+  const size_t n = std::max<size_t>(nc, 1);
+  // every buffer before anything is stored: a failed allocation leaves the context as it was
+  double *rec = X->d_tc, *link = X->d_tc_link, *snap = X->d_tc_snap;
+  rc = MPCEKF_OK;
+  if (!rc && !rec) rc = dalloc(&rec, n * NTCR);
+  if (!rc && !link) rc = dalloc(&link, n);
+  if (!rc && !snap) rc = dalloc(&snap, n * 2);
+  if (rc) {
+    if (rec != X->d_tc) (void)hipFree(rec);
+    if (link != X->d_tc_link) (void)hipFree(link);
+    if (snap != X->d_tc_snap) (void)hipFree(snap);
+    return rc;
+  }
+  X->d_tc = rec;
+  X->d_tc_link = link;
+  X->d_tc_snap = snap;
+  // behind every launch of an earlier call on the stream; a captured graph reads the links from
+  // this buffer, so a replaced set needs no new graph
+  if (nc) HIPCHK(hipMemcpyAsync(link, r_link, nc * 8, hipMemcpyHostToDevice, X->stream));
+  if ((rc = lerr(launch_couple_reset(rec, X->n, X->stream), "couple_reset"))) return rc;
+  HIPCHK(hipStreamSynchronize(X->stream));
+  return MPCEKF_OK;
+}
+
+int mpcekf_thermal_couple_get(mpcekf_ctx *X, int32_t nfields, const int32_t *fields, double *values) {
+  if (!X) return fail(MPCEKF_E_ARG, "thermal_couple_get: null ctx");
+  if (nfields < 1 || nfields > MPCEKF_NTCR)
+    return fail(MPCEKF_E_ARG, "thermal_couple_get: nfields = %d outside 1..%d", nfields, (int)MPCEKF_NTCR);
+  if (!fields) return fail(MPCEKF_E_ARG, "thermal_couple_get: null fields");
+  if (!values) return fail(MPCEKF_E_ARG, "thermal_couple_get: null values");
+  unsigned seen = 0;
+  for (int i = 0; i < nfields; ++i) {
+    if (fields[i] < 0 || fields[i] >= MPCEKF_NTCR)
+      return fail(MPCEKF_E_ARG, "thermal_couple_get: fields[%d] = %d is not a MPCEKF_TCR_* id (0..%d)", i, fields[i],
+                  (int)MPCEKF_NTCR - 1);
+    if (seen >> fields[i] & 1) return fail(MPCEKF_E_ARG, "thermal_couple_get: fields: id %d given twice", fields[i]);
+    seen |= 1u << fields[i];
+  }
+  if (!X->d_tc) return fail(MPCEKF_E_STATE, "thermal_couple_get: call mpcekf_thermal_couple first");
+  HIPCHK(hipSetDevice(X->device));
+  const size_t n = (size_t)X->n;
+  for (int i = 0; i < nfields && n; ++i)
+    HIPCHK(hipMemcpyAsync(values + (size_t)i * n, X->d_tc + (size_t)fields[i] * n, n * 8, hipMemcpyDeviceToHost,
+                          X->stream));
+  HIPCHK(hipStreamSynchronize(X->stream));
+  return MPCEKF_OK;
+}
+
+int mpcekf_thermal_couple_end(mpcekf_ctx *X) {
+  if (!X) return fail(MPCEKF_E_ARG, "thermal_couple_end: null ctx");
+  if (!X->d_tc) return MPCEKF_OK;
+  HIPCHK(hipSetDevice(X->device));
+  HIPCHK(hipStreamSynchronize(X->stream));
+  // the graphs captured on a coupled context launch its kernels on these buffers: retired before
+  // they are freed
+  for (size_t i = X->graphs.size(); i-- > 0;)
+    if (X->graphs[i].key[10]) {
+      (void)hipGraphExecDestroy(X->graphs[i].exec);
+      X->graphs.erase(X->graphs.begin() + (std::ptrdiff_t)i);
+    }
+  void *ptrs[] = {X->d_tc, X->d_tc_link, X->d_tc_snap};
+  for (void *p : ptrs) (void)hipFree(p);
+  X->d_tc = X->d_tc_link = X->d_tc_snap = nullptr;
+  return MPCEKF_OK;
+}
+
+int mpcekf_step_ex_couple(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const mpcekf_traj *tr,
+                          const int32_t *slots, int32_t nslots, double *obs, double *temp, double *heat, double *ucmd,
+                          int32_t *limiter, double *rate, double *cond, int32_t outputs_on_device) {
+  if (!X) return fail(MPCEKF_E_ARG, "step_ex_couple: null ctx");
+  if (!X->d_tc) return fail(MPCEKF_E_STATE, "step_ex_couple: call mpcekf_thermal_couple first");
+  if (rate && !X->d_ag) return fail(MPCEKF_E_STATE, "step_ex_couple: rate rows: call mpcekf_aging_begin first");
+  return step_impl(X, nsteps, tc_degC, tr, slots, nslots, obs, outputs_on_device, false, temp, heat, ucmd, limiter, rate,
+                   cond);
 }
 
 int mpcekf_set_timing(mpcekf_ctx *X, int32_t enable) {

@@ -33,29 +33,6 @@ namespace {
 
 __device__ __forceinline__ bool isnan_(double x) { return x != x; }
 
-// cell c's scheduled fields at temperature T
-__device__ __forceinline__ void sched_eval(const KSched &g, int64_t c, double T) {
-  const SchedHdr *h = g.hdr;
-  const int64_t n = g.n;
-  const int nf = h->nf, ntab = h->ntab;
-  const double T_lo = h->T_lo, T_hi = h->T_hi, Q = h->Q;
-  const double x = (T - T_lo) / (T_hi - T_lo);
-  double xc = x > 0.0 ? x : 0.0;  // NaN -> 0
-  xc = xc < 1.0 ? xc : 1.0;
-  const double s = xc * (double)(ntab - 1);
-  int j = (int)s;
-  if (j > ntab - 2) j = ntab - 2;
-  const double f = s - (double)j;
-  const double *tab = g.tab + (int64_t)g.set[c] * nf * ntab + j;
-  for (int i = 0; i < SCHED_MAXF; ++i) {
-    if (i >= nf) break;
-    const double t0 = tab[(int64_t)i * ntab], t1 = tab[(int64_t)i * ntab + 1];
-    const double val = t0 + f * (t1 - t0);
-    g.lim[(int64_t)h->slot[i] * n + c] = h->crate[i] ? -Q * val : val;  // initMPC.m:66-67
-    g.val[(int64_t)i * n + c] = val;
-  }
-}
-
 __global__ void __launch_bounds__(256) k_sched(KSched g) {
   const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= g.n) return;

@@ -3,6 +3,10 @@
 // mpcekf_thermal_sched.hip.  Not a reference function: runMPC.m:30-44 sets its limits once.
 #pragma once
 
+#ifdef __HIPCC__
+#include <hip/hip_runtime.h>
+#endif
+
 #include <cstdint>
 
 #include "mpcekf_thermal.hpp"
@@ -38,5 +42,35 @@ int launch_sched(const KSched &g, void *stream);
 // k_thermal's step of the model, then the schedule at the temperature it leaves: the last kernel
 // of a step that another step of the same call follows
 int launch_thermal_sched(const KTherm &q, const KSched &g, void *stream);
+
+#ifdef __HIPCC__
+// The lookup, written once for every kernel that evaluates the schedule (k_sched,
+// k_thermal_sched, k_thermal_couple_sched).  Every operation is one separately rounded fp64
+// operation in the order include/mpcekf.h spells out: the including file sets
+// `#pragma clang fp contract(off)` before its kernels.
+#pragma clang fp contract(off)
+// cell c's scheduled fields at temperature T
+static __device__ __forceinline__ void sched_eval(const KSched &g, int64_t c, double T) {
+  const SchedHdr *h = g.hdr;
+  const int64_t n = g.n;
+  const int nf = h->nf, ntab = h->ntab;
+  const double T_lo = h->T_lo, T_hi = h->T_hi, Q = h->Q;
+  const double x = (T - T_lo) / (T_hi - T_lo);
+  double xc = x > 0.0 ? x : 0.0;  // NaN -> 0
+  xc = xc < 1.0 ? xc : 1.0;
+  const double s = xc * (double)(ntab - 1);
+  int j = (int)s;
+  if (j > ntab - 2) j = ntab - 2;
+  const double f = s - (double)j;
+  const double *tab = g.tab + (int64_t)g.set[c] * nf * ntab + j;
+  for (int i = 0; i < SCHED_MAXF; ++i) {
+    if (i >= nf) break;
+    const double t0 = tab[(int64_t)i * ntab], t1 = tab[(int64_t)i * ntab + 1];
+    const double val = t0 + f * (t1 - t0);
+    g.lim[(int64_t)h->slot[i] * n + c] = h->crate[i] ? -Q * val : val;  // initMPC.m:66-67
+    g.val[(int64_t)i * n + c] = val;
+  }
+}
+#endif  // __HIPCC__
 
 }  // namespace mk

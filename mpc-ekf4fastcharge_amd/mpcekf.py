@@ -291,7 +291,9 @@ class Context:
         fields); only the selected slots are computed and copied.  None: the call as it was.
         ``thermal``: on a context with a thermal model (thermal_begin), the model's per-step rows
         to return as [nsteps, ncells] arrays: "temp" (the temperature each step used) and / or
-        "heat" (the heat it generated, W); mpcekf_step_ex_thermal.  None: the call as it was.
+        "heat" (the heat it generated, W); mpcekf_step_ex_thermal.  On a context with links
+        (thermal_couple) also "cond" (the heat the cell's neighbours conducted to it, W; +0.0 for a
+        cell without a link); mpcekf_step_ex_couple.  None: the call as it was.
         ``pack``: on a pack context (pack_begin), the pack's per-step rows to return: "ucmd"
         [nsteps, ncells], each cell's own command before its string's reduction (``u`` holds the
         applied current), and / or "limiter" [nsteps, ncells // series] int32, each string's
@@ -305,8 +307,8 @@ class Context:
         fields, slots = self._obs_select(obs, "step")   # KeyError before any library call
         th = () if thermal is None else (thermal,) if isinstance(thermal, str) else tuple(thermal)
         for k in th:
-            if k not in ("temp", "heat"):
-                raise KeyError(f"step: unknown thermal row {k!r} (one of ('temp', 'heat'))")
+            if k not in ("temp", "heat", "cond"):
+                raise KeyError(f"step: unknown thermal row {k!r} (one of ('temp', 'heat', 'cond'))")
         if thermal is not None and tc is not None:
             raise ValueError("step: thermal rows come from the model, which takes no tc")
         pk = () if pack is None else (pack,) if isinstance(pack, str) else tuple(pack)
@@ -330,7 +332,23 @@ class Context:
         tcp = tcs.ctypes.data_as(C.c_void_p) if tcs is not None else None
         rec = None if fields is None else np.empty((nsteps, slots.size, n))
         vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
-        if aging is not None:
+        if "cond" in th:   # every row of a coupled context: it has a model and a pack
+            for k in th:
+                out[k] = np.empty((nsteps, n))
+            series = getattr(self, "_pack_series", 0)   # 0: no begin, the library refuses the call
+            if "ucmd" in pk:
+                out["ucmd"] = np.empty((nsteps, n))
+            if "limiter" in pk:
+                out["limiter"] = np.empty((nsteps, n // series if series else n), dtype=np.int32)
+            nreact, mask = getattr(self, "_aging", (0, 0))
+            if "rate" in ag:
+                out["rate"] = np.empty((nsteps, max(bin(mask).count("1") * nreact, 1), n))
+            ns = 0 if fields is None else int(slots.size)
+            check(self.L.mpcekf_step_ex_couple(self.h, int(nsteps), tcp, C.byref(tr), iptr(slots) if ns else None, ns,
+                                               vp(rec) if ns else None, vp(out.get("temp")), vp(out.get("heat")),
+                                               vp(out.get("ucmd")), vp(out.get("limiter")), vp(out.get("rate")),
+                                               vp(out["cond"]), 0))
+        elif aging is not None:
             for k in th:
                 out[k] = np.empty((nsteps, n))
             series = getattr(self, "_pack_series", 0)
@@ -632,6 +650,49 @@ class Context:
         """End the schedule (mpcekf_thermal_schedule_end): its fields go back to what set_limits
         or the configuration gave them."""
         check(self.L.mpcekf_thermal_schedule_end(self.h))
+
+    # -- heat conduction between neighbouring cells of a pack string --------
+    COUPLE_FIELDS = ("NB_SUM", "DT_MAX", "DT_MAX_STEP")   # include/mpcekf.h MPCEKF_TCR_*
+
+    @staticmethod
+    def _couple_links(n, R_link):
+        """thermal_couple's argument -> float64 [n]; every check mpcekf_thermal_couple makes on
+        the links, before the library is called."""
+        r = np.asarray(R_link, dtype=np.float64)
+        if r.ndim == 0:
+            r = np.full(n, float(r))
+        if r.shape != (n,):
+            raise ValueError(f"thermal_couple: R_link must be a scalar or a length-{n} array, got shape {r.shape}")
+        r = np.ascontiguousarray(r)
+        if not np.all(r > 0):   # NaN fails the comparison
+            raise ValueError("thermal_couple: R_link must be > 0 (K/W; np.inf: no link) and not NaN")
+        return r
+
+    def thermal_couple(self, R_link):
+        """Link neighbouring cells of every pack string thermally (mpcekf_thermal_couple):
+        ``R_link`` (K/W, a scalar or [ncells]) is the resistance between cell c and cell c + 1,
+        used where both are in one string; np.inf: no link.  Needs thermal_begin and pack_begin.
+        From then on every fused call conducts heat between the linked cells; a second call
+        replaces the links and resets the coupling's record."""
+        r = self._couple_links(self.n, R_link)
+        check(self.L.mpcekf_thermal_couple(self.h, dptr(r)))
+
+    def thermal_couple_get(self, fields=None):
+        """{name: [ncells] float64} of the coupling's record (mpcekf_thermal_couple_get):
+        ``fields`` names of COUPLE_FIELDS, None: all."""
+        names = self.COUPLE_FIELDS if fields is None else (fields,) if isinstance(fields, str) else tuple(fields)
+        for k in names:
+            if k not in self.COUPLE_FIELDS:
+                raise KeyError(f"thermal_couple_get: unknown field {k!r} (one of {self.COUPLE_FIELDS})")
+        ids = np.array([self.COUPLE_FIELDS.index(k) for k in names], dtype=np.int32)
+        vals = np.empty((ids.size, self.n))
+        check(self.L.mpcekf_thermal_couple_get(self.h, int(ids.size), iptr(ids), dptr(vals)))
+        return {k: vals[i] for i, k in enumerate(names)}
+
+    def thermal_couple_end(self):
+        """Drop the links and their record (mpcekf_thermal_couple_end): the model is per cell
+        again.  thermal_end and pack_end do the same implicitly."""
+        check(self.L.mpcekf_thermal_couple_end(self.h))
 
     # -- series strings: one current per pack string ------------------------
     PACK_FIELDS = _lib.PACK_FIELDS
@@ -1088,12 +1149,23 @@ def thermal_ocv(rom, n=101, T_degC=25.0):
 
 def _thermal_begin(ctx, thermal):
     """runMPC's / run_summary's thermal dict: thermal_begin's keywords, plus an optional
-    "schedule": a dict of thermal_schedule's (T_lo, T_hi, sets and the tables)."""
+    "schedule": a dict of thermal_schedule's (T_lo, T_hi, sets and the tables), and an optional
+    "couple": thermal_couple's R_link, which the caller sets once the pack stands."""
     kw = dict(thermal)
     sched = kw.pop("schedule", None)
+    kw.pop("couple", None)
     ctx.thermal_begin(**kw)
     if sched:
         ctx.thermal_schedule(**sched)
+
+
+def _couple_links(n, thermal, pack, who):
+    """thermal["couple"] checked before a context exists: None when the dict has none."""
+    if not thermal or thermal.get("couple") is None:
+        return None
+    if not pack:
+        raise ValueError(f"{who}: thermal['couple'] links the cells of a pack string: pass pack=dict(series=S)")
+    return Context._couple_links(n, thermal["couple"])
 
 
 def runMPC(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=None, obs=None, limits=None,
@@ -1112,9 +1184,12 @@ def runMPC(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=None,
     current its weakest cell accepts (Context.pack_begin); out["u"] is the applied current, and
     out["ucmd"], out["limiter"] and out["pack"], the pack's record, are added.
     aging: a dict of Context.aging_begin's keywords (reactions, sources): adds out["rate"], every
-    step's side-reaction currents, and out["aging"], the record (Context.aging_record)."""
+    step's side-reaction currents, and out["aging"], the record (Context.aging_record).
+    thermal["couple"] with a pack: Context.thermal_couple's R_link, heat conduction between
+    neighbouring cells of a string; adds out["cond"] and out["couple"], the coupling's record."""
     SOC0 = np.atleast_1d(np.asarray(SOC0, dtype=np.float64))
     n = ncells or SOC0.shape[0]
+    links = _couple_links(n, thermal, pack, "runMPC")
     with Context(rom, n, cfg, device) as ctx:
         ctx.init_cells(SOC0, TC)
         if limits:
@@ -1123,14 +1198,19 @@ def runMPC(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=None,
             _thermal_begin(ctx, thermal)
         if pack:
             ctx.pack_begin(**pack)
+        if links is not None:
+            ctx.thermal_couple(links)
         if aging:
             ctx.aging_begin(**aging)
-        out = ctx.step(nsteps, tc=tc_traj, obs=obs, thermal=("temp", "heat") if thermal else None,
+        th_rows = ("temp", "heat", "cond") if links is not None else ("temp", "heat")
+        out = ctx.step(nsteps, tc=tc_traj, obs=obs, thermal=th_rows if thermal else None,
                        pack=("ucmd", "limiter") if pack else None, aging=("rate",) if aging else None)
         if aging:
             out["aging"] = ctx.aging_record()
         if pack:
             out["pack"] = ctx.pack_get()
+        if links is not None:
+            out["couple"] = ctx.thermal_couple_get()
         if thermal:
             out["thermal"] = ctx.thermal_get()
             if thermal.get("schedule"):
@@ -1148,7 +1228,8 @@ def run_summary(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=
     a chunk bounds the host array each call converts).  Neither host nor device memory grows
     with nsteps.  thermal: as runMPC's, its "schedule" included (no tc_traj); adds "thermal", the
     model's record.  pack: as runMPC's; adds "pack", the pack's record, beside the summary (whose
-    currents are the applied ones).  aging: as runMPC's; adds "aging", the side reactions' record."""
+    currents are the applied ones).  aging: as runMPC's; adds "aging", the side reactions' record.
+    thermal["couple"] with a pack: as runMPC's; adds "couple", the coupling's record."""
     SOC0 = np.atleast_1d(np.asarray(SOC0, dtype=np.float64))
     n = ncells or SOC0.shape[0]
     nsteps = int(nsteps)
@@ -1156,6 +1237,7 @@ def run_summary(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=
     if chunk < 0 or (chunk == 0 and nsteps):
         raise ValueError(f"run_summary: chunk = {chunk}")
     tcs = None if tc_traj is None else tc_grid(tc_traj, nsteps, n)
+    links = _couple_links(n, thermal, pack, "run_summary")
     with Context(rom, n, cfg, device) as ctx:
         ctx.init_cells(SOC0, TC)
         if limits:
@@ -1164,6 +1246,8 @@ def run_summary(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=
             _thermal_begin(ctx, thermal)
         if pack:
             ctx.pack_begin(**pack)
+        if links is not None:
+            ctx.thermal_couple(links)
         if aging:
             ctx.aging_begin(**aging)
         ctx.summary_begin(reach=reach, obs=obs)
@@ -1175,6 +1259,8 @@ def run_summary(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=
             out["aging"] = ctx.aging_record()
         if pack:
             out["pack"] = ctx.pack_get()
+        if links is not None:
+            out["couple"] = ctx.thermal_couple_get()
         if thermal:
             out["thermal"] = ctx.thermal_get()
         out["status"] = ctx.get_state()["status"]
