@@ -826,6 +826,98 @@ int mpcekf_step_ex_couple(mpcekf_ctx *ctx, int32_t nsteps, const double *tc_degC
                           const int32_t *slots, int32_t nslots, double *obs, double *temp, double *heat, double *ucmd,
                           int32_t *limiter, double *rate, double *cond, int32_t outputs_on_device);
 
+/* ---- charge termination along the fused loop (not part of the reference interface) ----
+ * runMPC.m steps its one cell for a fixed time, and its z_max row holds the SOC at the target for
+ * the rest of it.  A charger terminates: at a SOC, in the CV phase once the current has tapered
+ * below a threshold for a few samples, or on a temperature cut-off.  With a termination rule the
+ * context decides per cell, on the device, once per fused step, after the QP has produced the
+ * cell's command, whether the cell is done; a done cell rests at 0 A from then on, and
+ * mpcekf_step_until stops the loop when no cell is left.
+ * Parameters, [ncells] each; a NaN turns its criterion off, which falls out of the comparisons:
+ *   soc_stop   a fraction 0..1, in mpcekf_traj.soc's unit, like soc_reach
+ *   i_taper    A
+ *   T_cut      degC
+ *   hold       a step count >= 1, one per context
+ * Per-cell state: OPEN (initial), LATCHED or DEAD.  t counts the fused steps since
+ * mpcekf_term_begin, from 1, across calls.
+ * Inputs at step t, read after Hildreth, the slow path and k_cl_diag, and before k_pack:
+ *   z = this step's soc row, zk(end) (mpcekf_traj.soc)
+ *   u = the cell's own command in s.uk (MPCEKF_S_UK)
+ *   T = s.Tc, the temperature the step used, whatever set it (temp[t] of mpcekf_step_ex_thermal)
+ * For an OPEN cell, in this order (STEPS += 1 first: for an OPEN cell STEPS == t):
+ *   a. If z or u is NaN, the cell becomes DEAD and DONE_STEP = t.  Nothing else changes, now or
+ *      later.
+ *   b. On a pack (mpcekf_pack_begin, S > 1): if the cell's string had a LATCHED cell after step
+ *      t - 1, the cell becomes LATCHED with REASON = 8.  So string-mates follow one step late.
+ *      The lag is part of the rule: during the lag step k_pack already gives the string 0 A,
+ *      because the latched cell's +0 is the largest command.  The taper counter is not advanced.
+ *   c. Otherwise:
+ *      if fabs(u) > i_taper:                    armed = 1;  run = 0
+ *      else if armed and fabs(u) <= i_taper:    run += 1
+ *      else:                                    run = 0
+ *      REASON = (z >= soc_stop ? 1 : 0) | (run >= hold ? 2 : 0) | (T >= T_cut ? 4 : 0)
+ *      If REASON is non-zero, the cell becomes LATCHED.
+ *      armed and run start at 0: a current that never exceeded i_taper does not count as tapered.
+ * On latching: DONE_STEP = t, SOC_DONE = z, U_DONE = u, T_DONE = T.
+ * A LATCHED cell, one latched in this step included: if its u is not NaN, s.uk, s.uk_1
+ * (MPCEKF_S_UK, MPCEKF_S_UK_1) and the step's u row all become +0.0 (a -0.0 command too), and
+ * REST += 1.  A NaN command is left alone, as k_pack leaves it.
+ * Downstream, all without further change: a latched cell's +0 is the largest command of its
+ * string, so k_pack applies 0 A to the whole string; the plant, the EKF's ik, the summary's
+ * charge, k_aging and k_thermal all see a resting cell, and k_thermal lets it cool.
+ * The record, [ncells] each, every value a double, counts and step indices exact integers:
+ *   STATE      MPCEKF_TERM_OPEN, _LATCHED or _DEAD
+ *   DONE_STEP  the step the cell latched or died in; 0: none
+ *   REASON     the bits above; 0 for an OPEN or DEAD cell
+ *   SOC_DONE, U_DONE, T_DONE   z, u and T of the latching step; NaN: none
+ *   REST       the steps the cell's command was replaced by +0.0
+ *   STEPS      the steps evaluated while OPEN, the latching or dying one included
+ * The open counter is one device integer: the number of OPEN cells after the latest step.
+ * The rule is a property of the context, like the pack: mpcekf_step, _step_ex, _step_ex_obs,
+ * _step_ex_thermal, _step_ex_pack, _step_ex_aging, _step_ex_couple and _step_summary all run it,
+ * graph replay included, at every horizon and on every route of the fused step.  The stage route
+ * (mpcekf_mpc_step(_ex)) does not run the rule, as it does not couple a pack's strings either.
+ * mpcekf_get_state / mpcekf_set_state do not carry the termination state.  A context whose
+ * thresholds never hold runs the bits of one without a rule.  The kernel is not one of
+ * mpcekf_set_timing's five slots.
+ * Not modelled: a T_max row in the QP, resuming a latched cell, skipping a done cell's step. */
+enum { MPCEKF_TMP_SOC_STOP = 0, MPCEKF_TMP_I_TAPER, MPCEKF_TMP_T_CUT, MPCEKF_NTMP };
+enum { MPCEKF_TERM_OPEN = 0, MPCEKF_TERM_LATCHED, MPCEKF_TERM_DEAD };
+enum {
+  MPCEKF_TM_STATE = 0, MPCEKF_TM_DONE_STEP, MPCEKF_TM_REASON, MPCEKF_TM_SOC_DONE, MPCEKF_TM_U_DONE,
+  MPCEKF_TM_T_DONE, MPCEKF_TM_REST, MPCEKF_TM_STEPS, MPCEKF_NTM
+};
+/* Gives the context a termination rule: params [MPCEKF_NTMP][ncells], hold >= 1.  Allocates the
+ * rule's device buffers (first call) and resets every cell to OPEN, the record, the taper
+ * counters and t; a second begin replaces the first and resets likewise.  May be called before
+ * mpcekf_init_cells.
+ * MPCEKF_E_ARG (nothing changed): a NULL ctx or params, hold < 1. */
+int mpcekf_term_begin(mpcekf_ctx *ctx, const double *params, int32_t hold);
+/* values [nfields][ncells]: row i = field fields[i] (distinct MPCEKF_TM_* ids).
+ * MPCEKF_E_STATE without a begin; MPCEKF_E_ARG: a NULL pointer, nfields outside
+ * 1..MPCEKF_NTM, an unknown or repeated id. */
+int mpcekf_term_get(mpcekf_ctx *ctx, int32_t nfields, const int32_t *fields, double *values);
+/* *open_cells = the open counter (one 4-byte copy).  MPCEKF_E_STATE without a begin;
+ * MPCEKF_E_ARG: a NULL pointer. */
+int mpcekf_term_open(mpcekf_ctx *ctx, int64_t *open_cells);
+/* Frees the rule; the cells keep their state (a latched cell's s.uk is the +0.0 it was given)
+ * and the context then behaves as one that never began.  A no-op without a begin. */
+int mpcekf_term_end(mpcekf_ctx *ctx);
+/* Runs the fused loop with no trajectory output in calls of `chunk` steps (the last one shorter
+ * when max_steps % chunk != 0, so a repeated shape replays one graph), reads the open counter
+ * after each, and stops when it is 0 or max_steps is reached.  On a context with a summary begun
+ * (mpcekf_summary_begin) each chunk is a mpcekf_step_summary call and the record folds as usual;
+ * otherwise each chunk is mpcekf_step with NULL outputs.  tc_degC: NULL, or [ncells], the same
+ * row for every step; NULL with a thermal model.  *steps_run = the steps run, a multiple of
+ * chunk or max_steps; *open_cells = the counter after them (either may be NULL).  By
+ * construction the state afterwards is that of plain stepping for *steps_run steps: the
+ * overshoot is under `chunk` resting steps.
+ * MPCEKF_E_STATE without a mpcekf_term_begin or before mpcekf_init_cells; MPCEKF_E_ARG: a NULL
+ * ctx, max_steps < 0, chunk < 1, a tc_degC with a thermal model or out of range.  A refused call
+ * changes nothing. */
+int mpcekf_step_until(mpcekf_ctx *ctx, int32_t max_steps, int32_t chunk, const double *tc_degC, int32_t *steps_run,
+                      int64_t *open_cells);
+
 /* ---- device memory (not part of the reference interface) ----
  * Device buffers for outputs_on_device calls, allocated by the library's own HIP
  * runtime so a host process never holds a second one (a framework's bundled

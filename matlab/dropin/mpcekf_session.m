@@ -10,6 +10,17 @@ function [S, out] = mpcekf_session(op, name, value)
 %     such as {'negPhise0', 'Thetae'}, the names of initCfg.obsFields -- adds out.obs, the
 %     plant's own observables at every step: each field len x ncells x nsteps (len = 1 for
 %     the scalar fields).  out.phise is the EKF's estimate; out.obs.negPhise0 the plant's.
+%   mpcekf_session('termbegin', params, hold)
+%     charge termination on the session's context (mpcekf_term_begin): params ncells x 3, columns
+%     soc_stop (a fraction 0..1), i_taper (A), T_cut (degC), NaN: that criterion off; hold (default
+%     1): the steps the current stays at or under i_taper.  From then on 'step' and 'stepuntil'
+%     latch the cells that meet a criterion and rest them at 0 A.
+%   [S, out] = mpcekf_session('termget')     out: the record, a struct of ncells x 1 vectors (state,
+%     done_step, reason, soc_done, u_done, T_done, rest, steps)
+%   mpcekf_session('termend')
+%   [S, out] = mpcekf_session('stepuntil', max_steps, chunk)
+%     fused steps in calls of chunk (default 64) until no cell is open or max_steps are run
+%     (mpcekf_step_until): out.steps_run, out.open.
   persistent P
   % zk_last / ekf_tick: the zk the last iterEKF returned and a counter of iterEKF calls, so
   % EKFmatsHandler knows when the library's device copies of zk and Xind are the caller's
@@ -58,6 +69,21 @@ function [S, out] = mpcekf_session(op, name, value)
           out.obs.(value{k}) = permute(rows(:, at + 1 : at + m, :), [2 1 3]);
           at = at + m;
         end
+      end
+    case {'termbegin', 'termget', 'termend', 'stepuntil'}
+      if isempty(P.h), error('mpcekf_session: %s before the first OB_step call created the context', op); end
+      switch op
+        case 'termbegin'
+          if nargin < 3 || isempty(value), value = 1; end
+          mpcekf_mex('termbegin', P.h, name, value);
+        case 'termget'
+          out = mpcekf_mex('termget', P.h);
+        case 'termend'
+          mpcekf_mex('termend', P.h);
+        case 'stepuntil'
+          if nargin < 3 || isempty(value), value = 64; end
+          [run, left] = mpcekf_mex('stepuntil', P.h, name, value);
+          out = struct('steps_run', run, 'open', left);
       end
     otherwise
       error('mpcekf_session: unknown op %s', op);

@@ -115,6 +115,18 @@
  *   [u,v,soc,phise,nexec,rate] = mpcekf_mex('stepexaging', h, nsteps[, tc])   mpcekf_step_ex_aging
  *                       'step' on an aging context, plus every step's side-reaction currents (A),
  *                       ncells x (nsrc*nreact) x nsteps: the enabled sources in order, reactions inside
+ *                       mpcekf_mex('termbegin', h, params, hold)       mpcekf_term_begin
+ *                       charge termination: params ncells x 3, columns soc_stop (a fraction 0..1),
+ *                       i_taper (A), T_cut (degC), NaN: that criterion off; hold: the steps the
+ *                       current stays at or under i_taper.  From then on every fused step latches
+ *                       the cells that meet a criterion and rests them at 0 A
+ *   s                 = mpcekf_mex('termget', h)                       mpcekf_term_get
+ *                       struct of ncells x 1 column vectors: state (0 open, 1 latched, 2 dead),
+ *                       done_step, reason, soc_done, u_done, T_done, rest, steps (MPCEKF_TM_*)
+ *                       mpcekf_mex('termend', h)                       mpcekf_term_end
+ *   [steps_run, open] = mpcekf_mex('stepuntil', h, max_steps, chunk[, tc])   mpcekf_step_until
+ *                       fused steps in calls of `chunk` until no cell is open or max_steps are
+ *                       run; tc: [] or ncells temperatures, the same for every step
  * Per-cell vectors are 1 x ncells or ncells x 1; zk / zbk are (nz+2) x ncells, xm / xg
  * 4 x ncells (xm: 0-based model index t*nZ+z), lin 35 x ncells -- MATLAB's column-major
  * k x ncells is the library's cell-major [ncells][k], so no copy is made for them.
@@ -452,7 +464,8 @@ static void gateway(mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
                                             "thermalschedule", "thermalscheduleend",
                                             "thermalcouple", "thermalcoupleget", "thermalcoupleend", "stepexcouple",
                                             "packbegin", "packget", "packend", "stepexpack",
-                                            "agingbegin", "agingget", "agingend", "stepexaging"};
+                                            "agingbegin", "agingget", "agingend", "stepexaging",
+                                            "termbegin", "termget", "termend", "stepuntil"};
   int known = 0;
   for (size_t i = 0; i < sizeof with_handle / sizeof *with_handle; ++i) known = known || !strcmp(cmd, with_handle[i]);
   if (!known) mexErrMsgIdAndTxt("mpcekf:arg", "unknown command %s", cmd);
@@ -674,6 +687,34 @@ static void gateway(mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
     agsteps = (int32_t)nsd;
     if (nrhs > 3 && !mxIsEmpty(prhs[3]) && (!mxIsDouble(prhs[3]) || mxIsComplex(prhs[3])))
       mexErrMsgIdAndTxt("mpcekf:arg", "stepexaging: tc: expected [] or ncells x nsteps real doubles");
+  }
+  /* the termination commands likewise: output count, params that are no real doubles, a hold or
+     chunk that is no positive integer, a max_steps that is no count, a tc of the wrong class */
+  const int tmbegin = !strcmp(cmd, "termbegin"), until = !strcmp(cmd, "stepuntil");
+  int32_t tmhold = 0, tmmax = 0, tmchunk = 0;
+  if ((tmbegin || !strcmp(cmd, "termend")) && g_nlhs > 0) mexErrMsgIdAndTxt("mpcekf:arg", "%s: no output", cmd);
+  if (!strcmp(cmd, "termget") && g_nlhs > 1) mexErrMsgIdAndTxt("mpcekf:arg", "termget: at most 1 output");
+  if (until && g_nlhs > 2) mexErrMsgIdAndTxt("mpcekf:arg", "stepuntil: at most 2 outputs [steps_run, open]");
+  if (tmbegin) {
+    need(nrhs, 4, "'termbegin', h, params, hold");
+    if (!mxIsDouble(prhs[2]) || mxIsComplex(prhs[2]))
+      mexErrMsgIdAndTxt("mpcekf:arg", "termbegin: params: expected ncells x 3 real doubles");
+    const double hd = scalar(prhs[3], "termbegin: hold");
+    if (!(hd >= 1 && hd <= 2147483647.0) || hd != (double)(int32_t)hd)
+      mexErrMsgIdAndTxt("mpcekf:arg", "termbegin: hold = %g is not a positive integer", hd);
+    tmhold = (int32_t)hd;
+  }
+  if (until) {
+    need(nrhs, 4, "'stepuntil', h, max_steps, chunk[, tc]");
+    const double md = scalar(prhs[2], "max_steps"), cd = scalar(prhs[3], "stepuntil: chunk");
+    if (!(md >= 0 && md <= 2147483647.0) || md != (double)(int32_t)md)
+      mexErrMsgIdAndTxt("mpcekf:arg", "max_steps: expected a non-negative integer");
+    if (!(cd >= 1 && cd <= 2147483647.0) || cd != (double)(int32_t)cd)
+      mexErrMsgIdAndTxt("mpcekf:arg", "stepuntil: chunk = %g is not a positive integer", cd);
+    tmmax = (int32_t)md;
+    tmchunk = (int32_t)cd;
+    if (nrhs > 4 && !mxIsEmpty(prhs[4]) && (!mxIsDouble(prhs[4]) || mxIsComplex(prhs[4])))
+      mexErrMsgIdAndTxt("mpcekf:arg", "stepuntil: tc: expected [] or ncells real doubles");
   }
   mpcekf_ctx *h = handle(prhs[1]);
   int64_t n = 0;
@@ -958,6 +999,32 @@ static void gateway(mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
     int32_t *lim = (int32_t *)mxGetData(plhs[6]);
     chk(mpcekf_step_ex_pack(h, pksteps, tc, &tr, NULL, 0, NULL, NULL, NULL, mxGetDoubles(plhs[5]), series ? lim : NULL, 0));
     for (size_t i = 0; i < nstr * (size_t)pksteps; ++i) lim[i] += 1; /* 1-based; 0: no command */
+  } else if (tmbegin) {
+    /* ncells x 3 column-major is the library's [MPCEKF_NTMP][ncells] as it stands */
+    chk(mpcekf_term_begin(h, dvec(prhs[2], nc * MPCEKF_NTMP, "termbegin: params (ncells x 3)"), tmhold));
+  } else if (!strcmp(cmd, "termget")) {
+    static const char *const tm_names[MPCEKF_NTM] = {"state", "done_step", "reason", "soc_done",
+                                                     "u_done", "T_done", "rest", "steps"};
+    int32_t ids[MPCEKF_NTM];
+    double *vals = (double *)mxMalloc((size_t)MPCEKF_NTM * nc * sizeof(double) + 8);
+    for (int f = 0; f < MPCEKF_NTM; ++f) ids[f] = f;
+    chk(mpcekf_term_get(h, MPCEKF_NTM, ids, vals));
+    plhs[0] = mxCreateStructMatrix(1, 1, MPCEKF_NTM, (const char **)tm_names);
+    for (int f = 0; f < MPCEKF_NTM; ++f) {
+      mxArray *a = dmat(nc, 1);
+      if (nc) memcpy(mxGetDoubles(a), vals + (size_t)f * nc, nc * sizeof(double));
+      mxSetField(plhs[0], 0, tm_names[f], a);
+    }
+    mxFree(vals);
+  } else if (!strcmp(cmd, "termend")) {
+    chk(mpcekf_term_end(h));
+  } else if (until) {
+    const double *tc = nrhs > 4 ? opt_vec(prhs[4], nc, "stepuntil: tc (ncells)") : NULL;
+    int32_t run = 0;
+    int64_t left = 0;
+    chk(mpcekf_step_until(h, tmmax, tmchunk, tc, &run, &left));
+    plhs[0] = mxCreateDoubleScalar((double)run);
+    plhs[1] = mxCreateDoubleScalar((double)left);
   } else if (agbegin) {
     /* ncells x 5 x nreact column-major is the library's [nreact][MPCEKF_NAGP][ncells] as it stands */
     chk(mpcekf_aging_begin(h, agreact, agsrc, dvec(prhs[2], nc * MPCEKF_NAGP * (size_t)agreact, "agingbegin: params (ncells x 5 x nreact)")));

@@ -27,6 +27,7 @@
 #include "mpcekf_eig.hpp"
 #include "mpcekf_kernels.hpp"
 #include "mpcekf_pack.hpp"
+#include "mpcekf_term.hpp"
 #include "mpcekf_summary.hpp"
 #include "mpcekf_thermal.hpp"
 #include "mpcekf_thermal_sched.hpp"
@@ -304,6 +305,16 @@ struct mpcekf_ctx {
   double *d_ag = nullptr, *d_ag_par = nullptr, *d_ag_phi = nullptr, *d_ag_obs = nullptr;
   int *d_ag_plan = nullptr;
   int32_t ag_nreact = 0, ag_sources = 0, ag_slot = -1, ag_need = 0;
+  // mpcekf_term_begin .. _end: the record [NTMR][n], the thresholds [NTMP][n], the soc row k_term
+  // reads when the call has none of its own, and the integers [4 n + 1]: the taper counters
+  // [2][n], the string flags' pair [2][n] (room for series = 1) and the open counter.
+  // d_tm != nullptr: every fused step runs k_term after Hildreth, before k_pack.
+  double *d_tm = nullptr, *d_tm_par = nullptr, *d_tm_soc = nullptr;
+  int *d_tm_int = nullptr;
+  int32_t tm_hold = 0;
+  int *tm_cnt() const { return d_tm_int; }
+  int *tm_flag(int half) const { return d_tm_int + (size_t)(2 + half) * std::max<size_t>((size_t)n, 1); }
+  int *tm_open() const { return d_tm_int + 4 * std::max<size_t>((size_t)n, 1); }
   double *d_uk1p = nullptr;                      // [n] uk_1 before the step (poles / sv)
   int flush_period = LAZY_H;      // steps between all-model flushes (<= LAZY_H)
   // rolling flush (MPCEKF_FLUSH_ROLL=1, off by default): step t flushes the cell slice
@@ -1219,7 +1230,7 @@ int mpcekf_ctx_destroy(mpcekf_ctx *X) {
                   X->w.prob, X->w.X, X->w.R, X->w.K, X->w.hii, X->w.it, X->w.smin, X->d_lin, X->d_zsoc, X->d_mb, X->d_uk1p,
                   X->w.q, X->w.list, X->w.hist, X->d_poly, X->d_szk, X->d_sxg, X->d_sxm, X->d_slin, X->d_sv, X->d_zslot,
                   X->d_obs_blob, X->d_obs, X->d_obs_plan, X->d_lim, X->d_sch_hdr, X->d_sch_tab, X->d_sch_val, X->d_sch_set, X->d_sum, X->d_sum_reach, X->d_sum_obs,
-                  X->d_sum_ring, X->d_pk, X->d_tc, X->d_tc_link, X->d_tc_snap, X->d_ag, X->d_ag_par, X->d_ag_phi, X->d_ag_obs, X->d_ag_plan, X->d_th, X->d_th_par, X->d_th_i, X->d_th_ocv, X->d_hot, X->d_hot_i, X->d_hotp, X->d_hotp_i};
+                  X->d_sum_ring, X->d_pk, X->d_tc, X->d_tc_link, X->d_tc_snap, X->d_ag, X->d_ag_par, X->d_ag_phi, X->d_ag_obs, X->d_ag_plan, X->d_tm, X->d_tm_par, X->d_tm_soc, X->d_tm_int, X->d_th, X->d_th_par, X->d_th_i, X->d_th_ocv, X->d_hot, X->d_hot_i, X->d_hotp, X->d_hotp_i};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   for (auto &g : X->graphs) (void)hipGraphExecDestroy(g.exec);
@@ -1345,6 +1356,10 @@ static int lerr(int rc, const char *what) {
 // k_obs_traj launch of the context's own, which leaves the caller's rows what they were); rate
 // [nsteps][nsrc * nreact][ncells] (mpcekf_step_ex_aging) is one more output field, written by
 // k_aging.
+// A terminating context (mpcekf_term_begin): k_term after Hildreth and k_cl_diag, before k_pack,
+// applies the termination rule to every cell and rests the latched ones (+0.0 in s.uk, s.uk_1
+// and the u row); it reads the step's soc row (the context's own when the call has none) and,
+// on a pack, the string flags of the step's call-relative parity, seeded once per call.
 // A coupled context (mpcekf_thermal_couple): k_couple_seed once before the call's first step,
 // and k_thermal_couple(_sched) in k_thermal(_sched)'s place reads each cell's neighbours from
 // the snapshot of the step's parity; cond [nsteps][ncells] (mpcekf_step_ex_couple) is one more
@@ -1364,6 +1379,8 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
   const bool pack = X->d_pk != nullptr;
   const bool aging = X->d_ag != nullptr;
   const bool coupled = X->d_tc != nullptr;  // thermal && pack: either's end ends the coupling
+  const bool term = X->d_tm != nullptr;
+  const bool term_str = term && pack && X->pk_series > 1;  // strings whose cells follow their first latched one
   const bool ag_est = aging && (X->ag_sources & MPCEKF_AG_SRC_EST), ag_plant = aging && (X->ag_sources & MPCEKF_AG_SRC_PLANT);
   if (sum && X->sum_slot >= 0) {  // checked by mpcekf_summary_begin
     slots = &X->sum_slot;
@@ -1521,6 +1538,11 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
     // the temperatures the call's first step finds, for its neighbours (mpcekf_thermal_couple.hip)
     if (coupled && nsteps > 0 && (rc = lerr(launch_couple_seed(X->s.Tc, X->d_tc_snap, X->n, X->stream), "couple_seed")))
       return rc;
+    // the strings that hold a latched cell as the call's first step finds them (mpcekf_term.hip)
+    if (term_str && nsteps > 0) {
+      HIPCHK(hipMemsetAsync(X->tm_flag(0), 0, 2 * n * sizeof(int), X->stream));
+      if ((rc = lerr(launch_term_seed(X->d_tm, X->tm_flag(0), X->n, X->pk_series, X->stream), "term_seed"))) return rc;
+    }
     for (int k = 0; k < nsteps; ++k) {
       const int t = k + 1;
       // sampled steps: every timing_every-th (k = every-1, 2 every-1, ...: with every dividing
@@ -1562,6 +1584,7 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
       io.soc = (double *)row(2, k);
       io.phise = (double *)row(3, k);
       if (ag_est && !io.phise) io.phise = X->d_ag_phi;  // k_aging's input when the call asks for no phise row
+      if (term && !io.soc) io.soc = X->d_tm_soc;         // k_term's input when the call asks for no soc row
       io.nexec = (int *)row(4, k);
       io.x_out = (double *)row(5, k);
       io.zk = f[6].dev ? (double *)row(6, k) : X->d_zk;
@@ -1663,6 +1686,24 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
         if ((rc = lerr(rc, "cl_diag"))) return rc;
       }
       if (E) HIPCHK(hipEventRecord(E[4], X->stream));
+      if (term) {  // the termination rule on every cell's own command, before the strings' reduction
+        KTerm q{};
+        q.uk = X->s.uk;
+        q.uk_1 = X->s.uk_1;
+        q.u = (double *)row(0, k);
+        q.soc = io.soc;
+        q.Tc = X->s.Tc;
+        q.par = X->d_tm_par;
+        q.rec = X->d_tm;
+        q.cnt = X->tm_cnt();
+        q.flag_in = term_str ? X->tm_flag(k & 1) : nullptr;
+        q.flag_out = term_str ? X->tm_flag((k + 1) & 1) : nullptr;
+        q.open = X->tm_open();
+        q.n = X->n;
+        q.series = pack ? X->pk_series : 1;
+        q.hold = X->tm_hold;
+        if ((rc = lerr(launch_term(q, X->stream), "term"))) return rc;
+      }
       if (pack) {  // the strings' currents, once every cell's command stands in s.uk
         KPack q{};
         q.uk = X->s.uk;
@@ -1771,7 +1812,10 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
                                   // the coupling's buffers eleventh to thirteenth (its cond rows are among
                                   // the output rows below): 0 on a context without links --
                                   // mpcekf_thermal_couple_end retires the graphs that name them
-                                  (uintptr_t)X->d_tc, (uintptr_t)X->d_tc_link, (uintptr_t)X->d_tc_snap};
+                                  (uintptr_t)X->d_tc, (uintptr_t)X->d_tc_link, (uintptr_t)X->d_tc_snap,
+                                  // the termination state fourteenth to sixteenth: 0 on a context without
+                                  // one -- mpcekf_term_end retires the graphs that name it
+                                  (uintptr_t)X->d_tm, (uintptr_t)X->tm_hold, (uintptr_t)(term ? X->d_tm_soc : nullptr)};
     for (const F &e : f) key.push_back((uintptr_t)e.dev);
     key.push_back((uintptr_t)osel.plan);  // a regrown plan buffer retires the graphs that named the old one
     key.push_back((uintptr_t)nslots);
@@ -2363,6 +2407,136 @@ int mpcekf_step_ex_pack(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, co
   if ((temp || heat) && !X->d_th)
     return fail(MPCEKF_E_STATE, "step_ex_pack: temp / heat rows: call mpcekf_thermal_begin first");
   return step_impl(X, nsteps, tc_degC, tr, slots, nslots, obs, outputs_on_device, false, temp, heat, ucmd, limiter);
+}
+
+// ---- charge termination along the fused loop (mpcekf_term.hip) ----
+static_assert(NTMR == MPCEKF_NTM && TM_STATE == MPCEKF_TM_STATE && TM_DONE_STEP == MPCEKF_TM_DONE_STEP &&
+                  TM_REASON == MPCEKF_TM_REASON && TM_SOC_DONE == MPCEKF_TM_SOC_DONE && TM_U_DONE == MPCEKF_TM_U_DONE &&
+                  TM_T_DONE == MPCEKF_TM_T_DONE && TM_REST == MPCEKF_TM_REST && TM_STEPS == MPCEKF_TM_STEPS &&
+                  NTMP == MPCEKF_NTMP && TMP_SOC_STOP == MPCEKF_TMP_SOC_STOP && TMP_I_TAPER == MPCEKF_TMP_I_TAPER &&
+                  TMP_T_CUT == MPCEKF_TMP_T_CUT && TERM_OPEN == MPCEKF_TERM_OPEN && TERM_LATCHED == MPCEKF_TERM_LATCHED &&
+                  TERM_DEAD == MPCEKF_TERM_DEAD,
+              "mpcekf_term.hpp's rows are include/mpcekf.h's MPCEKF_TM_* / MPCEKF_TMP_* / MPCEKF_TERM_*");
+
+int mpcekf_term_begin(mpcekf_ctx *X, const double *params, int32_t hold) {
+  if (!X) return fail(MPCEKF_E_ARG, "term_begin: null ctx");
+  if (!params) return fail(MPCEKF_E_ARG, "term_begin: null params");
+  if (hold < 1) return fail(MPCEKF_E_ARG, "term_begin: hold = %d: a taper holds for 1 step or more", hold);
+  int rc;
+  HIPCHK(hipSetDevice(X->device));
+  const size_t n = std::max<size_t>((size_t)X->n, 1);
+  // every buffer before anything is stored: a failed allocation leaves the context as it was
+  double *rec = X->d_tm, *par = X->d_tm_par, *soc = X->d_tm_soc;
+  int *ints = X->d_tm_int;
+  if ((!rec && (rc = dalloc(&rec, n * NTMR))) || (!par && (rc = dalloc(&par, n * NTMP))) ||
+      (!soc && (rc = dalloc(&soc, n))) || (!ints && (rc = dalloc(&ints, 4 * n + 1)))) {
+    if (rec != X->d_tm) (void)hipFree(rec);
+    if (par != X->d_tm_par) (void)hipFree(par);
+    if (soc != X->d_tm_soc) (void)hipFree(soc);
+    return rc;
+  }
+  X->d_tm = rec;
+  X->d_tm_par = par;
+  X->d_tm_soc = soc;
+  X->d_tm_int = ints;
+  X->tm_hold = hold;
+  // behind every launch of an earlier call, which the stream orders before these
+  if (X->n) HIPCHK(hipMemcpyAsync(par, params, (size_t)X->n * NTMP * 8, hipMemcpyHostToDevice, X->stream));
+  if ((rc = lerr(launch_term_reset(rec, X->tm_cnt(), X->tm_flag(0), X->tm_open(), X->n, X->stream), "term_reset")))
+    return rc;
+  HIPCHK(hipStreamSynchronize(X->stream));
+  return MPCEKF_OK;
+}
+
+int mpcekf_term_get(mpcekf_ctx *X, int32_t nfields, const int32_t *fields, double *values) {
+  if (!X) return fail(MPCEKF_E_ARG, "term_get: null ctx");
+  if (nfields < 1 || nfields > MPCEKF_NTM)
+    return fail(MPCEKF_E_ARG, "term_get: nfields = %d outside 1..%d", nfields, (int)MPCEKF_NTM);
+  if (!fields) return fail(MPCEKF_E_ARG, "term_get: null fields");
+  if (!values) return fail(MPCEKF_E_ARG, "term_get: null values");
+  unsigned seen = 0;
+  for (int i = 0; i < nfields; ++i) {
+    if (fields[i] < 0 || fields[i] >= MPCEKF_NTM)
+      return fail(MPCEKF_E_ARG, "term_get: fields[%d] = %d is not a MPCEKF_TM_* id (0..%d)", i, fields[i],
+                  (int)MPCEKF_NTM - 1);
+    if (seen >> fields[i] & 1) return fail(MPCEKF_E_ARG, "term_get: fields: id %d given twice", fields[i]);
+    seen |= 1u << fields[i];
+  }
+  if (!X->d_tm) return fail(MPCEKF_E_STATE, "term_get: call mpcekf_term_begin first");
+  HIPCHK(hipSetDevice(X->device));
+  const size_t n = (size_t)X->n;
+  for (int i = 0; i < nfields && n; ++i)
+    HIPCHK(hipMemcpyAsync(values + (size_t)i * n, X->d_tm + (size_t)fields[i] * n, n * 8, hipMemcpyDeviceToHost,
+                          X->stream));
+  HIPCHK(hipStreamSynchronize(X->stream));
+  return MPCEKF_OK;
+}
+
+int mpcekf_term_open(mpcekf_ctx *X, int64_t *open_cells) {
+  if (!X) return fail(MPCEKF_E_ARG, "term_open: null ctx");
+  if (!open_cells) return fail(MPCEKF_E_ARG, "term_open: null open_cells");
+  if (!X->d_tm) return fail(MPCEKF_E_STATE, "term_open: call mpcekf_term_begin first");
+  HIPCHK(hipSetDevice(X->device));
+  int v = 0;
+  HIPCHK(hipMemcpyAsync(&v, X->tm_open(), sizeof(int), hipMemcpyDeviceToHost, X->stream));
+  HIPCHK(hipStreamSynchronize(X->stream));
+  *open_cells = v;
+  return MPCEKF_OK;
+}
+
+int mpcekf_term_end(mpcekf_ctx *X) {
+  if (!X) return fail(MPCEKF_E_ARG, "term_end: null ctx");
+  if (!X->d_tm) return MPCEKF_OK;
+  HIPCHK(hipSetDevice(X->device));
+  HIPCHK(hipStreamSynchronize(X->stream));
+  // the graphs captured on a terminating context launch k_term on these buffers: retired before
+  // they are freed
+  for (size_t i = X->graphs.size(); i-- > 0;)
+    if (X->graphs[i].key[13]) {
+      (void)hipGraphExecDestroy(X->graphs[i].exec);
+      X->graphs.erase(X->graphs.begin() + (std::ptrdiff_t)i);
+    }
+  void *ptrs[] = {X->d_tm, X->d_tm_par, X->d_tm_soc, X->d_tm_int};
+  for (void *p : ptrs)
+    if (p) (void)hipFree(p);
+  X->d_tm = X->d_tm_par = X->d_tm_soc = nullptr;
+  X->d_tm_int = nullptr;
+  X->tm_hold = 0;
+  return MPCEKF_OK;
+}
+
+int mpcekf_step_until(mpcekf_ctx *X, int32_t max_steps, int32_t chunk, const double *tc_degC, int32_t *steps_run,
+                      int64_t *open_cells) {
+  if (!X) return fail(MPCEKF_E_ARG, "step_until: null ctx");
+  if (max_steps < 0) return fail(MPCEKF_E_ARG, "step_until: max_steps = %d < 0", max_steps);
+  if (chunk < 1) return fail(MPCEKF_E_ARG, "step_until: chunk = %d: 1 step or more per call", chunk);
+  if (!X->d_tm) return fail(MPCEKF_E_STATE, "step_until: call mpcekf_term_begin first");
+  if (!X->initialized) return fail(MPCEKF_E_STATE, "step_until: call mpcekf_init_cells first");
+  if (X->d_th && tc_degC)
+    return fail(MPCEKF_E_ARG, "step_until: tc_degC on a thermal context (mpcekf_thermal_begin): the model sets the temperature");
+  int rc;
+  const size_t n = (size_t)X->n;
+  if (tc_degC && (rc = check_tc(tc_degC, n))) return rc;
+  // the same row for every step of a chunk; the calls' shape repeats, so one graph replays
+  std::vector<double> tcs;
+  if (tc_degC)
+    for (int k = 0; k < std::min(chunk, max_steps); ++k) tcs.insert(tcs.end(), tc_degC, tc_degC + n);
+  const double *tcp = tc_degC ? tcs.data() : nullptr;
+  int32_t run = 0;
+  int64_t open = 0;
+  if ((rc = mpcekf_term_open(X, &open))) return rc;
+  while (run < max_steps) {
+    const int32_t m = std::min(chunk, max_steps - run);
+    rc = X->d_sum ? step_impl(X, m, tcp, nullptr, nullptr, 0, nullptr, 0, true)
+                  : step_impl(X, m, tcp, nullptr, nullptr, 0, nullptr, 0);
+    if (rc) return rc;
+    run += m;
+    if ((rc = mpcekf_term_open(X, &open))) return rc;  // one 4-byte copy
+    if (open == 0) break;
+  }
+  if (steps_run) *steps_run = run;
+  if (open_cells) *open_cells = open;
+  return MPCEKF_OK;
 }
 
 // ---- side-reaction losses along the fused loop (mpcekf_aging.hip) ----

@@ -725,6 +725,69 @@ class Context:
         check(self.L.mpcekf_pack_end(self.h))
         self._pack_series = 0
 
+    # -- charge termination: latch, rest, stop when done --------------------
+    TERM_PARAMS = _lib.TERM_PARAMS
+    TERM_FIELDS = _lib.TERM_FIELDS
+
+    @classmethod
+    def _term_args(cls, n, soc_stop, i_taper, hold, T_cut):
+        """term_begin's arguments -> (float64 [3, n] thresholds with NaN for None, int hold).
+        ValueError for a bad shape or a hold that is no count >= 1: before any library call."""
+        par = np.full((len(cls.TERM_PARAMS), n), np.nan)
+        for i, (name, v) in enumerate(zip(cls.TERM_PARAMS, (soc_stop, i_taper, T_cut))):
+            if v is not None:
+                par[i] = cls._per_cell(n, name, v, who="term_begin")
+        if isinstance(hold, bool) or int(hold) != hold or int(hold) < 1:
+            raise ValueError(f"term_begin: hold = {hold!r}: a step count >= 1")
+        return par, int(hold)
+
+    def term_begin(self, soc_stop=None, i_taper=None, hold=1, T_cut=None):
+        """Give the context a termination rule (mpcekf_term_begin), each threshold a scalar or
+        [ncells], None (or NaN) for a criterion that is off: ``soc_stop`` a SOC in the unit of
+        step()'s ``soc`` (a fraction 0..1); ``i_taper`` (A) with ``hold``: the current has been at
+        or under i_taper for ``hold`` steps in a row after having been above it; ``T_cut`` (degC).
+        From then on every fused step latches the cells that meet a criterion and rests them at
+        0 A; on a pack a string follows its first latched cell.  A second call resets."""
+        par, hold = self._term_args(self.n, soc_stop, i_taper, hold, T_cut)   # ValueError before any library call
+        check(self.L.mpcekf_term_begin(self.h, dptr(par), hold))
+
+    def term_get(self, fields=None):
+        """{name: [ncells] float64} of the termination record (mpcekf_term_get): ``fields`` names
+        of TERM_FIELDS (default all): state (0 open, 1 latched, 2 dead), done_step, reason (bits:
+        1 soc_stop, 2 taper, 4 T_cut, 8 string), soc_done, u_done, T_done, rest, steps."""
+        names = self.TERM_FIELDS if fields is None else (fields,) if isinstance(fields, str) else tuple(fields)
+        for k in names:
+            if k not in self.TERM_FIELDS:
+                raise KeyError(f"term_get: unknown field {k!r} (one of {self.TERM_FIELDS})")
+        ids = np.asarray([self.TERM_FIELDS.index(k) for k in names], dtype=np.int32)
+        vals = np.empty((ids.size, self.n))
+        check(self.L.mpcekf_term_get(self.h, int(ids.size), iptr(ids), dptr(vals)))
+        return {k: vals[i] for i, k in enumerate(names)}
+
+    def term_open(self):
+        """The number of cells still open (mpcekf_term_open): one 4-byte copy."""
+        v = C.c_int64()
+        check(self.L.mpcekf_term_open(self.h, C.byref(v)))
+        return v.value
+
+    def term_end(self):
+        """Drop the termination rule (mpcekf_term_end): every cell steps on as it stands."""
+        check(self.L.mpcekf_term_end(self.h))
+
+    def step_until(self, max_steps, chunk=64, tc=None):
+        """Fused steps in calls of ``chunk`` until no cell is open or ``max_steps`` are run
+        (mpcekf_step_until); no trajectory is returned; with a summary begun the record folds as in
+        step_summary.  ``tc``: None, or the temperature (degC, a scalar or [ncells]) of every
+        step.  Returns (steps_run, open)."""
+        if isinstance(max_steps, bool) or int(max_steps) != max_steps or int(max_steps) < 0:
+            raise ValueError(f"step_until: max_steps = {max_steps!r}: a step count >= 0")
+        if isinstance(chunk, bool) or int(chunk) != chunk or int(chunk) < 1:
+            raise ValueError(f"step_until: chunk = {chunk!r}: a step count >= 1")
+        t = None if tc is None else np.ascontiguousarray(self._per_cell(self.n, "tc", tc, who="step_until"))
+        run, left = C.c_int32(), C.c_int64()
+        check(self.L.mpcekf_step_until(self.h, int(max_steps), int(chunk), dptr(t), C.byref(run), C.byref(left)))
+        return run.value, left.value
+
     # -- side-reaction losses per cell (plating, SEI) -----------------------
     AGING_PARAMS = _lib.AGING_PARAMS
     AGING_FIELDS = _lib.AGING_FIELDS
@@ -1168,8 +1231,25 @@ def _couple_links(n, thermal, pack, who):
     return Context._couple_links(n, thermal["couple"])
 
 
+def _stop_args(n, stop, who, chunk=False):
+    """runMPC's / run_summary's stop dict checked before a context exists: (term_begin's
+    thresholds [3, n], hold, chunk), or None when there is no dict.  KeyError for an unknown key,
+    ValueError for a bad shape, hold or chunk."""
+    if stop is None:
+        return None
+    known = ("soc_stop", "i_taper", "hold", "T_cut") + (("chunk",) if chunk else ())
+    for k in stop:
+        if k not in known:
+            raise KeyError(f"{who}: unknown stop key {k!r} (one of {known})")
+    par, hold = Context._term_args(n, stop.get("soc_stop"), stop.get("i_taper"), stop.get("hold", 1), stop.get("T_cut"))
+    c = stop.get("chunk", 64)
+    if isinstance(c, bool) or int(c) != c or int(c) < 1:
+        raise ValueError(f"{who}: stop['chunk'] = {c!r}: a step count >= 1")
+    return par, hold, int(c)
+
+
 def runMPC(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=None, obs=None, limits=None,
-           thermal=None, pack=None, aging=None):
+           thermal=None, pack=None, aging=None, stop=None):
     """runMPC.m:72-112 for a batch of cells; returns trajectories [nsteps, ncells].
     tc_traj [nsteps, ncells] (degC): a temperature profile (TC is the initial one).
     obs: the plant's observables of every step as out["obs"] (Context.step's obs=).
@@ -1186,10 +1266,13 @@ def runMPC(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=None,
     aging: a dict of Context.aging_begin's keywords (reactions, sources): adds out["rate"], every
     step's side-reaction currents, and out["aging"], the record (Context.aging_record).
     thermal["couple"] with a pack: Context.thermal_couple's R_link, heat conduction between
-    neighbouring cells of a string; adds out["cond"] and out["couple"], the coupling's record."""
+    neighbouring cells of a string; adds out["cond"] and out["couple"], the coupling's record.
+    stop: a dict of Context.term_begin's keywords (soc_stop, i_taper, hold, T_cut): the termination
+    rule over the fixed nsteps; a done cell rests at 0 A; adds out["term"], the rule's record."""
     SOC0 = np.atleast_1d(np.asarray(SOC0, dtype=np.float64))
     n = ncells or SOC0.shape[0]
     links = _couple_links(n, thermal, pack, "runMPC")
+    term = _stop_args(n, stop, "runMPC")
     with Context(rom, n, cfg, device) as ctx:
         ctx.init_cells(SOC0, TC)
         if limits:
@@ -1202,11 +1285,15 @@ def runMPC(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=None,
             ctx.thermal_couple(links)
         if aging:
             ctx.aging_begin(**aging)
+        if term:
+            check(ctx.L.mpcekf_term_begin(ctx.h, dptr(term[0]), term[1]))
         th_rows = ("temp", "heat", "cond") if links is not None else ("temp", "heat")
         out = ctx.step(nsteps, tc=tc_traj, obs=obs, thermal=th_rows if thermal else None,
                        pack=("ucmd", "limiter") if pack else None, aging=("rate",) if aging else None)
         if aging:
             out["aging"] = ctx.aging_record()
+        if term:
+            out["term"] = ctx.term_get()
         if pack:
             out["pack"] = ctx.pack_get()
         if links is not None:
@@ -1220,7 +1307,7 @@ def runMPC(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=None,
 
 
 def run_summary(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=None, limits=None, reach=None,
-                obs=None, chunk=None, thermal=None, pack=None, aging=None):
+                obs=None, chunk=None, thermal=None, pack=None, aging=None, stop=None):
     """runMPC.m:72-112 for a batch of cells, read out as the per-cell charge summary instead of
     trajectories: {field: [ncells]} of Context.get_summary plus "status".  limits: as runMPC's
     (a protocol sweep); reach, obs: Context.summary_begin's; tc_traj [nsteps, ncells] (degC): a
@@ -1229,7 +1316,10 @@ def run_summary(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=
     with nsteps.  thermal: as runMPC's, its "schedule" included (no tc_traj); adds "thermal", the
     model's record.  pack: as runMPC's; adds "pack", the pack's record, beside the summary (whose
     currents are the applied ones).  aging: as runMPC's; adds "aging", the side reactions' record.
-    thermal["couple"] with a pack: as runMPC's; adds "couple", the coupling's record."""
+    thermal["couple"] with a pack: as runMPC's; adds "couple", the coupling's record.
+    stop: a dict of Context.term_begin's keywords plus chunk (default 64): the loop runs through
+    Context.step_until with nsteps as the cap and ends when every cell is done (no tc_traj: TC
+    holds); adds "steps_run", the steps run, and "term", the rule's record."""
     SOC0 = np.atleast_1d(np.asarray(SOC0, dtype=np.float64))
     n = ncells or SOC0.shape[0]
     nsteps = int(nsteps)
@@ -1238,6 +1328,9 @@ def run_summary(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=
         raise ValueError(f"run_summary: chunk = {chunk}")
     tcs = None if tc_traj is None else tc_grid(tc_traj, nsteps, n)
     links = _couple_links(n, thermal, pack, "run_summary")
+    term = _stop_args(n, stop, "run_summary", chunk=True)
+    if term and tc_traj is not None:
+        raise ValueError("run_summary: stop runs step_until, which takes one temperature row: no tc_traj")
     with Context(rom, n, cfg, device) as ctx:
         ctx.init_cells(SOC0, TC)
         if limits:
@@ -1251,10 +1344,17 @@ def run_summary(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=
         if aging:
             ctx.aging_begin(**aging)
         ctx.summary_begin(reach=reach, obs=obs)
-        for k in range(0, nsteps, max(chunk, 1)):
-            m = min(chunk, nsteps - k)
-            ctx.step_summary(m, tc=None if tcs is None else tcs[k:k + m])
+        if term:
+            check(ctx.L.mpcekf_term_begin(ctx.h, dptr(term[0]), term[1]))
+            steps_run, _ = ctx.step_until(nsteps, chunk=term[2])
+        else:
+            for k in range(0, nsteps, max(chunk, 1)):
+                m = min(chunk, nsteps - k)
+                ctx.step_summary(m, tc=None if tcs is None else tcs[k:k + m])
         out = ctx.get_summary()
+        if term:
+            out["steps_run"] = steps_run
+            out["term"] = ctx.term_get()
         if aging:
             out["aging"] = ctx.aging_record()
         if pack:
