@@ -663,7 +663,8 @@ int mpcekf_thermal_schedule_end(mpcekf_ctx *ctx);
  * stage calls sees every cell's own command, as it does not advance the thermal model either.
  * The pack's kernel is not one of mpcekf_set_timing's five slots.
  * Heat conduction between neighbouring cells of a string: mpcekf_thermal_couple, below.
- * Not modelled: parallel groups, balancing or bypass currents, strings of unequal length. */
+ * Passive balancing (a bleed current around the cells that are ahead): mpcekf_balance_begin, below.
+ * Not modelled: parallel groups, active balancing, strings of unequal length. */
 enum { MPCEKF_PK_NLIM = 0, MPCEKF_PK_STEPS, MPCEKF_PK_HEADROOM, MPCEKF_NPK };
 /* Makes the context a pack of ncells / series strings of `series` cells each, allocates the
  * record (first call) and resets it; a second begin replaces the first and resets the record.
@@ -687,6 +688,96 @@ int mpcekf_pack_end(mpcekf_ctx *ctx);
 int mpcekf_step_ex_pack(mpcekf_ctx *ctx, int32_t nsteps, const double *tc_degC, const mpcekf_traj *traj,
                         const int32_t *slots, int32_t nslots, double *obs, double *temp, double *heat, double *ucmd,
                         int32_t *limiter, int32_t outputs_on_device);
+
+/* ---- passive balancing of pack strings: bleed currents along the fused loop (not part of the reference interface) ----
+ * A string that starts with an SOC spread keeps it: every cell gets the same current, the cell
+ * that is furthest ahead becomes the limiter and the others stop short of the target.  A passive
+ * balancer is a bleed resistor per cell that diverts part of the string current around a cell
+ * that is ahead.  A balancer is a property of a pack context (mpcekf_pack_begin first); on such
+ * a context the rule below runs once per fused step in k_pack's place, after k_term.
+ * Parameters, [ncells] each:
+ *   i_bleed    A, >= 0; 0: the cell has no bleeder
+ *   dz_on      a SOC fraction in mpcekf_traj.soc's unit, > 0
+ *   dz_off     a SOC fraction, 0 <= dz_off <= dz_on (hysteresis)
+ *   compensate 0 or 1, one per context
+ * Per-cell state: one flag `on`.  It starts at 0, is reset by begin and persists across calls.
+ * Inputs at fused step t, for string g = cells [g*S, (g+1)*S), read after k_term:
+ *   u_c = the cell's own command in s.uk (MPCEKF_S_UK); for a latched cell the +0.0 k_term wrote
+ *   z_c = this step's soc row, zk(end) (mpcekf_traj.soc)
+ * 1. A cell is valid when neither u_c nor z_c is NaN.  zmin_g is the smallest z_c over the valid
+ *    cells of the string.  Comparison is by value; on a tie the lowest in-string index wins, and
+ *    zmin_g is that cell's z_c bit for bit.  If the string has no valid cell, zmin_g is NaN.
+ * 2. For a valid cell, d = z_c - zmin_g, one rounded subtraction.
+ *      if d >= dz_on:        on = 1
+ *      else if d <= dz_off:  on = 0
+ *      else:                 on keeps its value
+ *    For a cell that is not valid, on = 0.
+ *    The cell is bleeding when on && i_bleed_c > 0.  b_c = i_bleed_c when bleeding, else +0.0.
+ * 3. The effective command is e_c = u_c - b_c (one rounded subtraction) when
+ *    compensate && bleeding && u_c < 0.  Otherwise e_c = u_c bit for bit.  So with compensate on,
+ *    the charger supplies what the cell accepts plus what its bleeder diverts.  A resting or
+ *    latched cell has u_c = +0.0, which is not < 0, so it is never compensated and still stops
+ *    its string.
+ * 4. The limiter is chosen by the pack's rule applied to e_c: the largest e_c among the cells
+ *    whose u_c is not NaN, compared by value, on a tie the lowest in-string index wins.
+ *    m_g = e_lim, bit for bit.  A string with no non-NaN command writes nothing to s.uk, s.uk_1
+ *    and the u row, and its limiter is -1.
+ * 5. The applied current is a_c = m_g + b_c (one rounded addition) for a bleeding cell.  For any
+ *    other cell with a non-NaN command it is a_c = m_g, bit for bit.  s.uk, s.uk_1 and the
+ *    step's u row get a_c.  A cell with a NaN command keeps its NaN, and its s.uk_1 is
+ *    untouched.  Everything downstream reads these locations, so it sees the cell's own current
+ *    with no further change: the plant, the EKF's ik, the summary's current and charge, k_aging
+ *    and k_thermal's carried current.
+ * 6. Records.  The pack record keeps its three fields, with e_c in u_c's place: STEPS += 1 for
+ *    a non-NaN command, NLIM += 1 for the limiter on e, HEADROOM += m_g - e_c (finite terms
+ *    only).  The balance record, [ncells] each, every value a double, counts exact integers,
+ *    accumulated over any number of calls and reset by begin:
+ *      STEPS_ON   the steps the cell was bleeding
+ *      Q_BLEED    the sequential sum in step order of b_c over the bleeding steps, from +0, A*steps
+ *      SWITCHES   the off -> on transitions of `on`
+ *      DZ_MAX     the largest non-NaN d seen; NaN: none
+ *      DZ_LAST    d of the latest step; NaN for a cell that is not valid
+ *      STEPS      the steps the cell was valid
+ * Identities: i_bleed = 0 everywhere leaves every bit of the same pack context without a
+ * balancer.  A dz_on that no cell reaches leaves every bit too.  S = 1 is the identity, because
+ * d = 0 < dz_on.
+ * The balancer is a property of the context, like the pack: mpcekf_step, _step_ex, _step_ex_obs,
+ * _step_ex_thermal, _step_ex_pack, _step_ex_aging, _step_ex_couple, _step_ex_balance,
+ * _step_summary and _step_until all run it, graph replay included, at every horizon and on every
+ * route of the fused step, in the same launch that couples the strings.  mpcekf_get_state /
+ * mpcekf_set_state do not carry the flag.  The kernel is not one of mpcekf_set_timing's five
+ * slots.
+ * Not modelled: a voltage-based criterion, a bleed current that depends on the cell voltage
+ * (v / R), the bleeder's own heat in the thermal model, active (charge-shuttling) balancing, the
+ * stage route (mpcekf_mpc_step(_ex) neither couples nor balances). */
+enum { MPCEKF_BLP_I_BLEED = 0, MPCEKF_BLP_DZ_ON, MPCEKF_BLP_DZ_OFF, MPCEKF_NBLP };
+enum {
+  MPCEKF_BL_STEPS_ON = 0, MPCEKF_BL_Q_BLEED, MPCEKF_BL_SWITCHES, MPCEKF_BL_DZ_MAX, MPCEKF_BL_DZ_LAST,
+  MPCEKF_BL_STEPS, MPCEKF_NBL
+};
+/* Gives the pack context a balancer: params [MPCEKF_NBLP][ncells], compensate 0 or 1.  Allocates
+ * the balancer's device buffers (first call) and resets the flags and the record; a second begin
+ * replaces the first and resets likewise.  May be called before mpcekf_init_cells.  A later
+ * mpcekf_pack_begin with another series keeps the balancer (parameters and flags are per cell);
+ * mpcekf_pack_end ends it.
+ * MPCEKF_E_STATE (nothing changed): no pack.  MPCEKF_E_ARG (nothing changed): a NULL pointer, a
+ * negative or NaN i_bleed, dz_on <= 0 or NaN, dz_off outside [0, dz_on], a compensate that is
+ * not 0 / 1. */
+int mpcekf_balance_begin(mpcekf_ctx *ctx, const double *params, int32_t compensate);
+/* values [nfields][ncells]: row i = field fields[i] (distinct MPCEKF_BL_* ids).
+ * MPCEKF_E_STATE without a begin; MPCEKF_E_ARG: a NULL pointer, nfields outside
+ * 1..MPCEKF_NBL, an unknown or repeated id. */
+int mpcekf_balance_get(mpcekf_ctx *ctx, int32_t nfields, const int32_t *fields, double *values);
+/* Frees the balancer; the cells keep their state and the context then behaves as a pack that
+ * never had one.  A no-op without a begin. */
+int mpcekf_balance_end(mpcekf_ctx *ctx);
+/* mpcekf_step_ex_pack's arguments plus the balancer's rows (host, or device when
+ * outputs_on_device != 0), either may be NULL: bleed [nsteps][ncells], b_c, NaN for a cell with
+ * a NaN command; zmin [nsteps][ncells / series], zmin_g.  MPCEKF_E_STATE without a balancer; a
+ * refused call leaves the context and the records as they were. */
+int mpcekf_step_ex_balance(mpcekf_ctx *ctx, int32_t nsteps, const double *tc_degC, const mpcekf_traj *traj,
+                           const int32_t *slots, int32_t nslots, double *obs, double *temp, double *heat, double *ucmd,
+                           int32_t *limiter, double *bleed, double *zmin, int32_t outputs_on_device);
 
 /* ---- side-reaction losses per cell along the fused loop (not part of the reference interface) ----
  * runMPC.m keeps phise_store above mpcData.const.phise_min so that lithium does not plate.  How

@@ -85,6 +85,20 @@ function [S, out] = mpcekf_session(op, name, value)
           [run, left] = mpcekf_mex('stepuntil', P.h, name, value);
           out = struct('steps_run', run, 'open', left);
       end
+    case {'balancebegin', 'balanceget', 'balanceend', 'stepexbalance'}
+      if isempty(P.h), error('mpcekf_session: %s before the first OB_step call created the context', op); end
+      switch op
+        case 'balancebegin'
+          if nargin < 3 || isempty(value), value = 1; end
+          mpcekf_mex('balancebegin', P.h, name, value);
+        case 'balanceget'
+          out = mpcekf_mex('balanceget', P.h);
+        case 'balanceend'
+          mpcekf_mex('balanceend', P.h);
+        case 'stepexbalance'
+          [o.u, o.v, o.soc, o.phise, o.nexec, o.ucmd, o.limiter, o.bleed, o.zmin] = mpcekf_mex('stepexbalance', P.h, name);
+          out = o;
+      end
     otherwise
       error('mpcekf_session: unknown op %s', op);
   end

@@ -124,6 +124,20 @@
  *                       struct of ncells x 1 column vectors: state (0 open, 1 latched, 2 dead),
  *                       done_step, reason, soc_done, u_done, T_done, rest, steps (MPCEKF_TM_*)
  *                       mpcekf_mex('termend', h)                       mpcekf_term_end
+ *                       mpcekf_mex('balancebegin', h, params, compensate)   mpcekf_balance_begin
+ *                       passive balancing on a pack ('packbegin' first): params ncells x 3, columns
+ *                       i_bleed (A, >= 0), dz_on (a SOC fraction > 0), dz_off (0 .. dz_on);
+ *                       compensate 0 / 1: the charger adds a bleeding cell's bleed current.  From then
+ *                       on every fused step bleeds the cells that are dz_on above their string's
+ *                       smallest soc
+ *   s                 = mpcekf_mex('balanceget', h)                    mpcekf_balance_get
+ *                       struct of ncells x 1 column vectors: steps_on, q_bleed, switches, dz_max,
+ *                       dz_last, steps (MPCEKF_BL_*)
+ *                       mpcekf_mex('balanceend', h)                    mpcekf_balance_end
+ *   [u,v,soc,phise,nexec,ucmd,limiter,bleed,zmin] = mpcekf_mex('stepexbalance', h, nsteps[, tc])
+ *                       mpcekf_step_ex_balance:
+ *                       'stepexpack' on a context with a balancer, plus each cell's bleed current,
+ *                       ncells x nsteps, and each string's smallest soc, nstrings x nsteps
  *   [steps_run, open] = mpcekf_mex('stepuntil', h, max_steps, chunk[, tc])   mpcekf_step_until
  *                       fused steps in calls of `chunk` until no cell is open or max_steps are
  *                       run; tc: [] or ncells temperatures, the same for every step
@@ -398,7 +412,7 @@ static const double *opt_vec(const mxArray *a, size_t n, const char *what) {
 
 /* Every command builds its outputs in plhs[0..MAXOUT); mexFunction hands MATLAB the
  * first max(nlhs, 1) of them (MATLAB's plhs has room for no more) and frees the rest. */
-#define MAXOUT 8
+#define MAXOUT 9
 static void need(int nrhs, int k, const char *usage) {
   if (nrhs < k) mexErrMsgIdAndTxt("mpcekf:arg", "usage: mpcekf_mex(%s)", usage);
 }
@@ -465,7 +479,8 @@ static void gateway(mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
                                             "thermalcouple", "thermalcoupleget", "thermalcoupleend", "stepexcouple",
                                             "packbegin", "packget", "packend", "stepexpack",
                                             "agingbegin", "agingget", "agingend", "stepexaging",
-                                            "termbegin", "termget", "termend", "stepuntil"};
+                                            "termbegin", "termget", "termend", "stepuntil",
+                                            "balancebegin", "balanceget", "balanceend", "stepexbalance"};
   int known = 0;
   for (size_t i = 0; i < sizeof with_handle / sizeof *with_handle; ++i) known = known || !strcmp(cmd, with_handle[i]);
   if (!known) mexErrMsgIdAndTxt("mpcekf:arg", "unknown command %s", cmd);
@@ -715,6 +730,32 @@ static void gateway(mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
     tmchunk = (int32_t)cd;
     if (nrhs > 4 && !mxIsEmpty(prhs[4]) && (!mxIsDouble(prhs[4]) || mxIsComplex(prhs[4])))
       mexErrMsgIdAndTxt("mpcekf:arg", "stepuntil: tc: expected [] or ncells real doubles");
+  }
+  /* the balance commands likewise: output count, params that are no real doubles, a compensate
+     that is not 0 / 1, an nsteps that is no non-negative integer, a tc of the wrong class */
+  const int blbegin = !strcmp(cmd, "balancebegin"), stepbl = !strcmp(cmd, "stepexbalance");
+  int32_t blcomp = 0, blsteps = 0;
+  if ((blbegin || !strcmp(cmd, "balanceend")) && g_nlhs > 0) mexErrMsgIdAndTxt("mpcekf:arg", "%s: no output", cmd);
+  if (!strcmp(cmd, "balanceget") && g_nlhs > 1) mexErrMsgIdAndTxt("mpcekf:arg", "balanceget: at most 1 output");
+  if (stepbl && g_nlhs > 9)
+    mexErrMsgIdAndTxt("mpcekf:arg",
+                      "stepexbalance: at most 9 outputs [u, v, soc, phise, nexec, ucmd, limiter, bleed, zmin]");
+  if (blbegin) {
+    need(nrhs, 4, "'balancebegin', h, params, compensate");
+    if (!mxIsDouble(prhs[2]) || mxIsComplex(prhs[2]))
+      mexErrMsgIdAndTxt("mpcekf:arg", "balancebegin: params: expected ncells x 3 real doubles");
+    const double cd = scalar(prhs[3], "balancebegin: compensate");
+    if (cd != 0.0 && cd != 1.0) mexErrMsgIdAndTxt("mpcekf:arg", "balancebegin: compensate = %g is not 0 or 1", cd);
+    blcomp = (int32_t)cd;
+  }
+  if (stepbl) {
+    need(nrhs, 3, "'stepexbalance', h, nsteps[, tc]");
+    const double nsd = scalar(prhs[2], "nsteps");
+    if (!(nsd >= 0 && nsd <= 2147483647.0) || nsd != (double)(int32_t)nsd)
+      mexErrMsgIdAndTxt("mpcekf:arg", "nsteps: expected a non-negative integer");
+    blsteps = (int32_t)nsd;
+    if (nrhs > 3 && !mxIsEmpty(prhs[3]) && (!mxIsDouble(prhs[3]) || mxIsComplex(prhs[3])))
+      mexErrMsgIdAndTxt("mpcekf:arg", "stepexbalance: tc: expected [] or ncells x nsteps real doubles");
   }
   mpcekf_ctx *h = handle(prhs[1]);
   int64_t n = 0;
@@ -999,6 +1040,41 @@ static void gateway(mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
     int32_t *lim = (int32_t *)mxGetData(plhs[6]);
     chk(mpcekf_step_ex_pack(h, pksteps, tc, &tr, NULL, 0, NULL, NULL, NULL, mxGetDoubles(plhs[5]), series ? lim : NULL, 0));
     for (size_t i = 0; i < nstr * (size_t)pksteps; ++i) lim[i] += 1; /* 1-based; 0: no command */
+  } else if (blbegin) {
+    /* ncells x 3 column-major is the library's [MPCEKF_NBLP][ncells] as it stands */
+    chk(mpcekf_balance_begin(h, dvec(prhs[2], nc * MPCEKF_NBLP, "balancebegin: params (ncells x 3)"), blcomp));
+  } else if (!strcmp(cmd, "balanceget")) {
+    static const char *const bl_names[MPCEKF_NBL] = {"steps_on", "q_bleed", "switches", "dz_max", "dz_last", "steps"};
+    int32_t ids[MPCEKF_NBL];
+    double *vals = (double *)mxMalloc((size_t)MPCEKF_NBL * nc * sizeof(double) + 8);
+    for (int f = 0; f < MPCEKF_NBL; ++f) ids[f] = f;
+    chk(mpcekf_balance_get(h, MPCEKF_NBL, ids, vals));
+    plhs[0] = mxCreateStructMatrix(1, 1, MPCEKF_NBL, (const char **)bl_names);
+    for (int f = 0; f < MPCEKF_NBL; ++f) {
+      mxArray *a = dmat(nc, 1);
+      if (nc) memcpy(mxGetDoubles(a), vals + (size_t)f * nc, nc * sizeof(double));
+      mxSetField(plhs[0], 0, bl_names[f], a);
+    }
+    mxFree(vals);
+  } else if (!strcmp(cmd, "balanceend")) {
+    chk(mpcekf_balance_end(h));
+  } else if (stepbl) {
+    /* without a 'balancebegin' the library refuses the call before it touches a row */
+    const int32_t series = *series_of(h);
+    const size_t nstr = series ? nc / (size_t)series : 0;
+    const double *tc = nrhs > 3 ? opt_vec(prhs[3], nc * (size_t)blsteps, "stepexbalance: tc (ncells x nsteps)") : NULL;
+    for (int i = 0; i < 6; ++i) plhs[i] = i == 4 ? imat(nc, (size_t)blsteps) : dmat(nc, (size_t)blsteps);
+    plhs[6] = imat(nstr, (size_t)blsteps);
+    plhs[7] = dmat(nc, (size_t)blsteps);
+    plhs[8] = dmat(nstr, (size_t)blsteps);
+    mpcekf_traj tr;
+    memset(&tr, 0, sizeof tr);
+    tr.u = mxGetDoubles(plhs[0]); tr.v = mxGetDoubles(plhs[1]); tr.soc = mxGetDoubles(plhs[2]);
+    tr.phise = mxGetDoubles(plhs[3]); tr.nexec = (int32_t *)mxGetData(plhs[4]);
+    int32_t *lim = (int32_t *)mxGetData(plhs[6]);
+    chk(mpcekf_step_ex_balance(h, blsteps, tc, &tr, NULL, 0, NULL, NULL, NULL, mxGetDoubles(plhs[5]),
+                               series ? lim : NULL, mxGetDoubles(plhs[7]), series ? mxGetDoubles(plhs[8]) : NULL, 0));
+    for (size_t i = 0; i < nstr * (size_t)blsteps; ++i) lim[i] += 1; /* 1-based; 0: no command */
   } else if (tmbegin) {
     /* ncells x 3 column-major is the library's [MPCEKF_NTMP][ncells] as it stands */
     chk(mpcekf_term_begin(h, dvec(prhs[2], nc * MPCEKF_NTMP, "termbegin: params (ncells x 3)"), tmhold));

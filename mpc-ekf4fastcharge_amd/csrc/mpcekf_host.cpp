@@ -26,6 +26,7 @@
 #include "mpcekf_aging.hpp"
 #include "mpcekf_eig.hpp"
 #include "mpcekf_kernels.hpp"
+#include "mpcekf_balance.hpp"
 #include "mpcekf_pack.hpp"
 #include "mpcekf_term.hpp"
 #include "mpcekf_summary.hpp"
@@ -315,6 +316,13 @@ struct mpcekf_ctx {
   int *tm_cnt() const { return d_tm_int; }
   int *tm_flag(int half) const { return d_tm_int + (size_t)(2 + half) * std::max<size_t>((size_t)n, 1); }
   int *tm_open() const { return d_tm_int + 4 * std::max<size_t>((size_t)n, 1); }
+  // mpcekf_balance_begin .. _end (needs a pack): the record [NBLR][n], the parameters [NBLP][n],
+  // the flags [n], the compensate switch and the soc row k_pack_bal reads when the call has none of
+  // its own (and k_term's d_tm_soc does not stand in).  d_bl != nullptr: every fused step runs
+  // k_pack_bal in k_pack's place.
+  double *d_bl = nullptr, *d_bl_par = nullptr, *d_bl_soc = nullptr;
+  int *d_bl_on = nullptr;
+  int32_t bl_comp = 0;
   double *d_uk1p = nullptr;                      // [n] uk_1 before the step (poles / sv)
   int flush_period = LAZY_H;      // steps between all-model flushes (<= LAZY_H)
   // rolling flush (MPCEKF_FLUSH_ROLL=1, off by default): step t flushes the cell slice
@@ -1230,7 +1238,7 @@ int mpcekf_ctx_destroy(mpcekf_ctx *X) {
                   X->w.prob, X->w.X, X->w.R, X->w.K, X->w.hii, X->w.it, X->w.smin, X->d_lin, X->d_zsoc, X->d_mb, X->d_uk1p,
                   X->w.q, X->w.list, X->w.hist, X->d_poly, X->d_szk, X->d_sxg, X->d_sxm, X->d_slin, X->d_sv, X->d_zslot,
                   X->d_obs_blob, X->d_obs, X->d_obs_plan, X->d_lim, X->d_sch_hdr, X->d_sch_tab, X->d_sch_val, X->d_sch_set, X->d_sum, X->d_sum_reach, X->d_sum_obs,
-                  X->d_sum_ring, X->d_pk, X->d_tc, X->d_tc_link, X->d_tc_snap, X->d_ag, X->d_ag_par, X->d_ag_phi, X->d_ag_obs, X->d_ag_plan, X->d_tm, X->d_tm_par, X->d_tm_soc, X->d_tm_int, X->d_th, X->d_th_par, X->d_th_i, X->d_th_ocv, X->d_hot, X->d_hot_i, X->d_hotp, X->d_hotp_i};
+                  X->d_sum_ring, X->d_pk, X->d_tc, X->d_tc_link, X->d_tc_snap, X->d_ag, X->d_ag_par, X->d_ag_phi, X->d_ag_obs, X->d_ag_plan, X->d_tm, X->d_tm_par, X->d_tm_soc, X->d_tm_int, X->d_bl, X->d_bl_par, X->d_bl_soc, X->d_bl_on, X->d_th, X->d_th_par, X->d_th_i, X->d_th_ocv, X->d_hot, X->d_hot_i, X->d_hotp, X->d_hotp_i};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   for (auto &g : X->graphs) (void)hipGraphExecDestroy(g.exec);
@@ -1360,6 +1368,10 @@ static int lerr(int rc, const char *what) {
 // applies the termination rule to every cell and rests the latched ones (+0.0 in s.uk, s.uk_1
 // and the u row); it reads the step's soc row (the context's own when the call has none) and,
 // on a pack, the string flags of the step's call-relative parity, seeded once per call.
+// A balancing context (mpcekf_balance_begin, on a pack): k_pack_bal in k_pack's place reads the
+// step's soc row (the context's own when the call has none) and the cells' flags, and stores the
+// applied currents; bleed [nsteps][ncells] and zmin [nsteps][ncells / series]
+// (mpcekf_step_ex_balance) are two more output fields, written by that kernel.
 // A coupled context (mpcekf_thermal_couple): k_couple_seed once before the call's first step,
 // and k_thermal_couple(_sched) in k_thermal(_sched)'s place reads each cell's neighbours from
 // the snapshot of the step's parity; cond [nsteps][ncells] (mpcekf_step_ex_couple) is one more
@@ -1367,7 +1379,8 @@ static int lerr(int rc, const char *what) {
 static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const mpcekf_traj *tr,
                      const int32_t *slots, int32_t nslots, double *obs, int32_t outputs_on_device,
                      bool sum = false, double *temp = nullptr, double *heat = nullptr, double *ucmd = nullptr,
-                     int32_t *limiter = nullptr, double *rate = nullptr, double *cond = nullptr) {
+                     int32_t *limiter = nullptr, double *rate = nullptr, double *cond = nullptr, double *bleed = nullptr,
+                     double *zmin = nullptr) {
   // a thermal context owns the temperature: refused before anything of the context changes
   if (X && X->d_th && tc_degC)
     return fail(MPCEKF_E_ARG, "step: tc_degC on a thermal context (mpcekf_thermal_begin): the model sets the temperature");
@@ -1380,6 +1393,7 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
   const bool aging = X->d_ag != nullptr;
   const bool coupled = X->d_tc != nullptr;  // thermal && pack: either's end ends the coupling
   const bool term = X->d_tm != nullptr;
+  const bool balance = pack && X->d_bl != nullptr;
   const bool term_str = term && pack && X->pk_series > 1;  // strings whose cells follow their first latched one
   const bool ag_est = aging && (X->ag_sources & MPCEKF_AG_SRC_EST), ag_plant = aging && (X->ag_sources & MPCEKF_AG_SRC_PLANT);
   if (sum && X->sum_slot >= 0) {  // checked by mpcekf_summary_begin
@@ -1425,7 +1439,9 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
            {limiter, 4, 1, nullptr, pack ? n / (size_t)X->pk_series : 0},  // [nsteps][nstrings]
            // k_aging's rows (an aging context's only): [nsteps][nsrc * nreact][ncells]
            {rate, 8, aging ? (size_t)(((int)ag_est + (int)ag_plant) * X->ag_nreact) : 0, nullptr},
-           {cond, 8, 1, nullptr}};  // k_thermal_couple's row (a coupled context's only)
+           {cond, 8, 1, nullptr},  // k_thermal_couple's row (a coupled context's only)
+           {bleed, 8, 1, nullptr},  // k_pack_bal's rows (a balancing context's only)
+           {zmin, 8, 1, nullptr, pack ? n / (size_t)X->pk_series : 0}};  // [nsteps][nstrings]
   constexpr int NF = sizeof(f) / sizeof(f[0]);
   auto step_bytes = [&](const F &e) -> size_t { return (e.rows ? e.rows : n) * e.width * e.esz; };  // one step's block
   const double *dtc = tc_degC;  // [nsteps][n] device copy of the per-step temperatures
@@ -1585,6 +1601,7 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
       io.phise = (double *)row(3, k);
       if (ag_est && !io.phise) io.phise = X->d_ag_phi;  // k_aging's input when the call asks for no phise row
       if (term && !io.soc) io.soc = X->d_tm_soc;         // k_term's input when the call asks for no soc row
+      if (balance && !io.soc) io.soc = X->d_bl_soc;      // k_pack_bal's likewise
       io.nexec = (int *)row(4, k);
       io.x_out = (double *)row(5, k);
       io.zk = f[6].dev ? (double *)row(6, k) : X->d_zk;
@@ -1714,7 +1731,20 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
         q.rec = X->d_pk;
         q.n = X->n;
         q.series = X->pk_series;
-        if ((rc = lerr(launch_pack(q, X->stream), "pack"))) return rc;
+        if (balance) {  // the bleeders' switching and the strings' currents in one launch
+          KPackBal b{};
+          b.p = q;
+          b.soc = io.soc;
+          b.par = X->d_bl_par;
+          b.on = X->d_bl_on;
+          b.rec = X->d_bl;
+          b.bleed = (double *)row(21, k);
+          b.zmin = (double *)row(22, k);
+          b.compensate = X->bl_comp;
+          if ((rc = lerr(launch_pack_bal(b, X->stream), "pack_bal"))) return rc;
+        } else if ((rc = lerr(launch_pack(q, X->stream), "pack"))) {
+          return rc;
+        }
       }
       // k_bounds done before k_flush or the next step's k_cell rewrites the records it reads
       if (side) HIPCHK(hipStreamWaitEvent(X->stream, X->ev_bjoin, 0));
@@ -1815,7 +1845,13 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
                                   (uintptr_t)X->d_tc, (uintptr_t)X->d_tc_link, (uintptr_t)X->d_tc_snap,
                                   // the termination state fourteenth to sixteenth: 0 on a context without
                                   // one -- mpcekf_term_end retires the graphs that name it
-                                  (uintptr_t)X->d_tm, (uintptr_t)X->tm_hold, (uintptr_t)(term ? X->d_tm_soc : nullptr)};
+                                  (uintptr_t)X->d_tm, (uintptr_t)X->tm_hold, (uintptr_t)(term ? X->d_tm_soc : nullptr),
+                                  // the balancer seventeenth to twenty-first (its bleed / zmin rows are among
+                                  // the output rows below): 0 on a context without one -- mpcekf_balance_end
+                                  // retires the graphs that name it
+                                  (uintptr_t)(balance ? X->d_bl : nullptr), (uintptr_t)(balance ? X->d_bl_par : nullptr),
+                                  (uintptr_t)(balance ? X->d_bl_on : nullptr), (uintptr_t)(balance ? X->bl_comp : 0),
+                                  (uintptr_t)(balance ? X->d_bl_soc : nullptr)};
     for (const F &e : f) key.push_back((uintptr_t)e.dev);
     key.push_back((uintptr_t)osel.plan);  // a regrown plan buffer retires the graphs that named the old one
     key.push_back((uintptr_t)nslots);
@@ -2385,6 +2421,7 @@ int mpcekf_pack_end(mpcekf_ctx *X) {
   if (!X->d_pk) return MPCEKF_OK;
   int rc = mpcekf_thermal_couple_end(X);  // links need strings
   if (rc) return rc;
+  if ((rc = mpcekf_balance_end(X))) return rc;  // and so does a balancer
   HIPCHK(hipSetDevice(X->device));
   HIPCHK(hipStreamSynchronize(X->stream));
   // the graphs captured on a pack context launch k_pack on the record: retired before it is freed
@@ -2407,6 +2444,110 @@ int mpcekf_step_ex_pack(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, co
   if ((temp || heat) && !X->d_th)
     return fail(MPCEKF_E_STATE, "step_ex_pack: temp / heat rows: call mpcekf_thermal_begin first");
   return step_impl(X, nsteps, tc_degC, tr, slots, nslots, obs, outputs_on_device, false, temp, heat, ucmd, limiter);
+}
+
+// ---- passive balancing of pack strings along the fused loop (mpcekf_balance.hip) ----
+static_assert(NBLP == MPCEKF_NBLP && BLP_I_BLEED == MPCEKF_BLP_I_BLEED && BLP_DZ_ON == MPCEKF_BLP_DZ_ON &&
+                  BLP_DZ_OFF == MPCEKF_BLP_DZ_OFF && NBLR == MPCEKF_NBL && BL_STEPS_ON == MPCEKF_BL_STEPS_ON &&
+                  BL_Q_BLEED == MPCEKF_BL_Q_BLEED && BL_SWITCHES == MPCEKF_BL_SWITCHES && BL_DZ_MAX == MPCEKF_BL_DZ_MAX &&
+                  BL_DZ_LAST == MPCEKF_BL_DZ_LAST && BL_STEPS == MPCEKF_BL_STEPS,
+              "mpcekf_balance.hpp's rows are include/mpcekf.h's MPCEKF_BLP_* / MPCEKF_BL_*");
+
+int mpcekf_balance_begin(mpcekf_ctx *X, const double *params, int32_t compensate) {
+  if (!X) return fail(MPCEKF_E_ARG, "balance_begin: null ctx");
+  if (!params) return fail(MPCEKF_E_ARG, "balance_begin: null params");
+  if (compensate != 0 && compensate != 1)
+    return fail(MPCEKF_E_ARG, "balance_begin: compensate = %d is not 0 / 1", compensate);
+  if (!X->d_pk) return fail(MPCEKF_E_STATE, "balance_begin: call mpcekf_pack_begin first");
+  const size_t nc = (size_t)X->n;
+  for (size_t c = 0; c < nc; ++c) {
+    const double ib = params[BLP_I_BLEED * nc + c], on = params[BLP_DZ_ON * nc + c], off = params[BLP_DZ_OFF * nc + c];
+    if (!(ib >= 0.0)) return fail(MPCEKF_E_ARG, "balance_begin: i_bleed[%zu] = %g: a current >= 0", c, ib);
+    if (!(on > 0.0)) return fail(MPCEKF_E_ARG, "balance_begin: dz_on[%zu] = %g: a SOC fraction > 0", c, on);
+    if (!(off >= 0.0 && off <= on))
+      return fail(MPCEKF_E_ARG, "balance_begin: dz_off[%zu] = %g outside [0, dz_on = %g]", c, off, on);
+  }
+  int rc;
+  HIPCHK(hipSetDevice(X->device));
+  const size_t n = std::max<size_t>(nc, 1);
+  // every buffer before anything is stored: a failed allocation leaves the context as it was
+  double *rec = X->d_bl, *par = X->d_bl_par, *soc = X->d_bl_soc;
+  int *on = X->d_bl_on;
+  if ((!rec && (rc = dalloc(&rec, n * NBLR))) || (!par && (rc = dalloc(&par, n * NBLP))) ||
+      (!soc && (rc = dalloc(&soc, n))) || (!on && (rc = dalloc(&on, n)))) {
+    if (rec != X->d_bl) (void)hipFree(rec);
+    if (par != X->d_bl_par) (void)hipFree(par);
+    if (soc != X->d_bl_soc) (void)hipFree(soc);
+    return rc;
+  }
+  // a first begin changes the launch sequence: the graphs of the balancer-free pack are not
+  // replayed (their key holds 0 where these buffers now stand), so nothing is retired here
+  X->d_bl = rec;
+  X->d_bl_par = par;
+  X->d_bl_soc = soc;
+  X->d_bl_on = on;
+  X->bl_comp = compensate;
+  // behind every launch of an earlier call, which the stream orders before these
+  if (nc) HIPCHK(hipMemcpyAsync(par, params, nc * NBLP * 8, hipMemcpyHostToDevice, X->stream));
+  if ((rc = lerr(launch_bal_reset(rec, on, X->n, X->stream), "bal_reset"))) return rc;
+  HIPCHK(hipStreamSynchronize(X->stream));
+  return MPCEKF_OK;
+}
+
+int mpcekf_balance_get(mpcekf_ctx *X, int32_t nfields, const int32_t *fields, double *values) {
+  if (!X) return fail(MPCEKF_E_ARG, "balance_get: null ctx");
+  if (nfields < 1 || nfields > MPCEKF_NBL)
+    return fail(MPCEKF_E_ARG, "balance_get: nfields = %d outside 1..%d", nfields, (int)MPCEKF_NBL);
+  if (!fields) return fail(MPCEKF_E_ARG, "balance_get: null fields");
+  if (!values) return fail(MPCEKF_E_ARG, "balance_get: null values");
+  unsigned seen = 0;
+  for (int i = 0; i < nfields; ++i) {
+    if (fields[i] < 0 || fields[i] >= MPCEKF_NBL)
+      return fail(MPCEKF_E_ARG, "balance_get: fields[%d] = %d is not a MPCEKF_BL_* id (0..%d)", i, fields[i],
+                  (int)MPCEKF_NBL - 1);
+    if (seen >> fields[i] & 1) return fail(MPCEKF_E_ARG, "balance_get: fields: id %d given twice", fields[i]);
+    seen |= 1u << fields[i];
+  }
+  if (!X->d_bl) return fail(MPCEKF_E_STATE, "balance_get: call mpcekf_balance_begin first");
+  HIPCHK(hipSetDevice(X->device));
+  const size_t n = (size_t)X->n;
+  for (int i = 0; i < nfields && n; ++i)
+    HIPCHK(hipMemcpyAsync(values + (size_t)i * n, X->d_bl + (size_t)fields[i] * n, n * 8, hipMemcpyDeviceToHost,
+                          X->stream));
+  HIPCHK(hipStreamSynchronize(X->stream));
+  return MPCEKF_OK;
+}
+
+int mpcekf_balance_end(mpcekf_ctx *X) {
+  if (!X) return fail(MPCEKF_E_ARG, "balance_end: null ctx");
+  if (!X->d_bl) return MPCEKF_OK;
+  HIPCHK(hipSetDevice(X->device));
+  HIPCHK(hipStreamSynchronize(X->stream));
+  // the graphs captured on a balancing context launch k_pack_bal on these buffers: retired before
+  // they are freed
+  for (size_t i = X->graphs.size(); i-- > 0;)
+    if (X->graphs[i].key[16]) {
+      (void)hipGraphExecDestroy(X->graphs[i].exec);
+      X->graphs.erase(X->graphs.begin() + (std::ptrdiff_t)i);
+    }
+  void *ptrs[] = {X->d_bl, X->d_bl_par, X->d_bl_soc, X->d_bl_on};
+  for (void *p : ptrs)
+    if (p) (void)hipFree(p);
+  X->d_bl = X->d_bl_par = X->d_bl_soc = nullptr;
+  X->d_bl_on = nullptr;
+  X->bl_comp = 0;
+  return MPCEKF_OK;
+}
+
+int mpcekf_step_ex_balance(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const mpcekf_traj *tr,
+                           const int32_t *slots, int32_t nslots, double *obs, double *temp, double *heat, double *ucmd,
+                           int32_t *limiter, double *bleed, double *zmin, int32_t outputs_on_device) {
+  if (!X) return fail(MPCEKF_E_ARG, "step_ex_balance: null ctx");
+  if (!X->d_pk || !X->d_bl) return fail(MPCEKF_E_STATE, "step_ex_balance: call mpcekf_balance_begin first");
+  if ((temp || heat) && !X->d_th)
+    return fail(MPCEKF_E_STATE, "step_ex_balance: temp / heat rows: call mpcekf_thermal_begin first");
+  return step_impl(X, nsteps, tc_degC, tr, slots, nslots, obs, outputs_on_device, false, temp, heat, ucmd, limiter,
+                   nullptr, nullptr, bleed, zmin);
 }
 
 // ---- charge termination along the fused loop (mpcekf_term.hip) ----

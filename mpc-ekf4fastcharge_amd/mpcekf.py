@@ -298,7 +298,10 @@ class Context:
         [nsteps, ncells], each cell's own command before its string's reduction (``u`` holds the
         applied current), and / or "limiter" [nsteps, ncells // series] int32, each string's
         limiter as an in-string index or -1; mpcekf_step_ex_pack.  None: the call as it was (a
-        pack context couples its strings all the same).
+        pack context couples its strings all the same).  On a context with a balancer
+        (balance_begin) also "bleed" [nsteps, ncells], each cell's bleed current (NaN for a cell
+        with a NaN command), and / or "zmin" [nsteps, ncells // series], each string's smallest
+        soc; mpcekf_step_ex_balance, which has no "cond" or "rate" row.
         ``aging``: on an aging context (aging_begin), ("rate",) returns out["rate"]
         [nsteps, nsrc * nreact, ncells], every step's side-reaction currents (A): the enabled
         sources in the order est, plant, the reactions inside; mpcekf_step_ex_aging.  None: the
@@ -313,8 +316,12 @@ class Context:
             raise ValueError("step: thermal rows come from the model, which takes no tc")
         pk = () if pack is None else (pack,) if isinstance(pack, str) else tuple(pack)
         for k in pk:
-            if k not in ("ucmd", "limiter"):
-                raise KeyError(f"step: unknown pack row {k!r} (one of ('ucmd', 'limiter'))")
+            if k not in ("ucmd", "limiter", "bleed", "zmin"):
+                raise KeyError(f"step: unknown pack row {k!r} (one of ('ucmd', 'limiter', 'bleed', 'zmin'))")
+        bal = "bleed" in pk or "zmin" in pk
+        if bal and ("cond" in th or aging is not None):
+            raise ValueError("step: the balancer's rows (bleed, zmin) come from mpcekf_step_ex_balance, which has no "
+                             "cond or rate row")
         ag = () if aging is None else (aging,) if isinstance(aging, str) else tuple(aging)
         for k in ag:
             if k != "rate":
@@ -332,7 +339,24 @@ class Context:
         tcp = tcs.ctypes.data_as(C.c_void_p) if tcs is not None else None
         rec = None if fields is None else np.empty((nsteps, slots.size, n))
         vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
-        if "cond" in th:   # every row of a coupled context: it has a model and a pack
+        if bal:   # a pack context with a balancer
+            for k in th:
+                out[k] = np.empty((nsteps, n))
+            series = getattr(self, "_pack_series", 0)   # 0: no begin, the library refuses the call
+            if "ucmd" in pk:
+                out["ucmd"] = np.empty((nsteps, n))
+            if "limiter" in pk:
+                out["limiter"] = np.empty((nsteps, n // series if series else n), dtype=np.int32)
+            if "bleed" in pk:
+                out["bleed"] = np.empty((nsteps, n))
+            if "zmin" in pk:
+                out["zmin"] = np.empty((nsteps, n // series if series else n))
+            ns = 0 if fields is None else int(slots.size)
+            check(self.L.mpcekf_step_ex_balance(self.h, int(nsteps), tcp, C.byref(tr), iptr(slots) if ns else None, ns,
+                                                vp(rec) if ns else None, vp(out.get("temp")), vp(out.get("heat")),
+                                                vp(out.get("ucmd")), vp(out.get("limiter")), vp(out.get("bleed")),
+                                                vp(out.get("zmin")), 0))
+        elif "cond" in th:   # every row of a coupled context: it has a model and a pack
             for k in th:
                 out[k] = np.empty((nsteps, n))
             series = getattr(self, "_pack_series", 0)   # 0: no begin, the library refuses the call
@@ -724,6 +748,59 @@ class Context:
         """Drop the pack (mpcekf_pack_end): every cell is on its own again."""
         check(self.L.mpcekf_pack_end(self.h))
         self._pack_series = 0
+
+    # -- passive balancing: bleed currents around the cells that are ahead ---
+    BALANCE_PARAMS = _lib.BALANCE_PARAMS
+    BALANCE_FIELDS = _lib.BALANCE_FIELDS
+
+    @classmethod
+    def _balance_args(cls, n, i_bleed, dz_on, dz_off=None, compensate=True):
+        """balance_begin's arguments -> (float64 [3, n] parameters, int compensate).  ValueError
+        for a bad shape, a negative or NaN i_bleed, dz_on <= 0 or NaN, dz_off outside [0, dz_on]
+        or a compensate that is no 0 / 1: before any library call."""
+        ib = cls._per_cell(n, "i_bleed", i_bleed, who="balance_begin")
+        on = cls._per_cell(n, "dz_on", dz_on, who="balance_begin")
+        off = on / 2 if dz_off is None else cls._per_cell(n, "dz_off", dz_off, who="balance_begin")
+        if not np.all(ib >= 0):
+            raise ValueError("balance_begin: i_bleed: a current >= 0 (0: no bleeder), not NaN")
+        if not np.all(on > 0):
+            raise ValueError("balance_begin: dz_on: a SOC fraction > 0, not NaN")
+        if not np.all((off >= 0) & (off <= on)):
+            raise ValueError("balance_begin: dz_off: a SOC fraction in [0, dz_on]")
+        if not isinstance(compensate, (bool, np.bool_)) and not (isinstance(compensate, (int, np.integer))
+                                                                  and compensate in (0, 1)):
+            raise ValueError(f"balance_begin: compensate = {compensate!r}: True / False (1 / 0)")
+        return np.ascontiguousarray(np.stack([ib, on, off]), dtype=np.float64), int(compensate)
+
+    def balance_begin(self, i_bleed, dz_on, dz_off=None, compensate=True):
+        """Give the pack context a passive balancer (mpcekf_balance_begin), each parameter a scalar
+        or [ncells]: ``i_bleed`` (A, >= 0; 0: the cell has no bleeder); a cell's bleeder switches
+        on once its soc is ``dz_on`` (a fraction, > 0) above the smallest of its string and off at
+        ``dz_off`` (default dz_on / 2) or below; ``compensate``: the charger adds a bleeding
+        cell's bleed current to what the cell accepts.  From then on every fused step applies to a
+        bleeding cell its string's current less its bleed current.  A second call resets."""
+        # ValueError before any library call
+        par, comp = self._balance_args(self.n, i_bleed, dz_on, dz_off, compensate)
+        check(self.L.mpcekf_balance_begin(self.h, dptr(par), comp))
+
+    def balance_get(self, fields=None):
+        """{name: [ncells] float64} of the balance record (mpcekf_balance_get): ``fields`` names of
+        BALANCE_FIELDS (default all): steps_on, the steps the cell was bleeding; q_bleed, the sum of
+        its bleed current over them (A steps); switches, the times its bleeder went on; dz_max and
+        dz_last, the largest and the latest distance to its string's smallest soc; steps, the
+        steps it was valid."""
+        names = self.BALANCE_FIELDS if fields is None else (fields,) if isinstance(fields, str) else tuple(fields)
+        for k in names:
+            if k not in self.BALANCE_FIELDS:
+                raise KeyError(f"balance_get: unknown field {k!r} (one of {self.BALANCE_FIELDS})")
+        ids = np.asarray([self.BALANCE_FIELDS.index(k) for k in names], dtype=np.int32)
+        vals = np.empty((ids.size, self.n))
+        check(self.L.mpcekf_balance_get(self.h, int(ids.size), iptr(ids), dptr(vals)))
+        return {k: vals[i] for i, k in enumerate(names)}
+
+    def balance_end(self):
+        """Drop the balancer (mpcekf_balance_end): the pack couples its strings as before."""
+        check(self.L.mpcekf_balance_end(self.h))
 
     # -- charge termination: latch, rest, stop when done --------------------
     TERM_PARAMS = _lib.TERM_PARAMS
@@ -1231,6 +1308,26 @@ def _couple_links(n, thermal, pack, who):
     return Context._couple_links(n, thermal["couple"])
 
 
+def _pack_args(n, pack, who):
+    """runMPC's / run_summary's pack dict checked before a context exists: (pack_begin's keywords,
+    balance_begin's (parameters [3, n], compensate) or None).  KeyError for an unknown balance
+    key, ValueError for a bad value."""
+    if not pack or "balance" not in pack:
+        return pack, None
+    pack = dict(pack)
+    b = pack.pop("balance")
+    if not b:
+        return pack, None
+    known = ("i_bleed", "dz_on", "dz_off", "compensate")
+    for k in b:
+        if k not in known:
+            raise KeyError(f"{who}: unknown pack['balance'] key {k!r} (one of {known})")
+    for k in ("i_bleed", "dz_on"):
+        if k not in b:
+            raise KeyError(f"{who}: pack['balance'] needs {k!r}")
+    return pack, Context._balance_args(n, **b)
+
+
 def _stop_args(n, stop, who, chunk=False):
     """runMPC's / run_summary's stop dict checked before a context exists: (term_begin's
     thresholds [3, n], hold, chunk), or None when there is no dict.  KeyError for an unknown key,
@@ -1263,6 +1360,9 @@ def runMPC(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=None,
     pack: dict(series=S): the cells form ncells // S series strings, each charged with the one
     current its weakest cell accepts (Context.pack_begin); out["u"] is the applied current, and
     out["ucmd"], out["limiter"] and out["pack"], the pack's record, are added.
+    pack["balance"]: a dict of Context.balance_begin's keywords (i_bleed, dz_on, dz_off,
+    compensate): a passive balancer; adds out["bleed"], out["zmin"] (not with aging or
+    thermal["couple"], whose calls have no such rows) and out["balance"], the balancer's record.
     aging: a dict of Context.aging_begin's keywords (reactions, sources): adds out["rate"], every
     step's side-reaction currents, and out["aging"], the record (Context.aging_record).
     thermal["couple"] with a pack: Context.thermal_couple's R_link, heat conduction between
@@ -1272,6 +1372,7 @@ def runMPC(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=None,
     SOC0 = np.atleast_1d(np.asarray(SOC0, dtype=np.float64))
     n = ncells or SOC0.shape[0]
     links = _couple_links(n, thermal, pack, "runMPC")
+    pack, bal = _pack_args(n, pack, "runMPC")
     term = _stop_args(n, stop, "runMPC")
     with Context(rom, n, cfg, device) as ctx:
         ctx.init_cells(SOC0, TC)
@@ -1281,6 +1382,8 @@ def runMPC(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=None,
             _thermal_begin(ctx, thermal)
         if pack:
             ctx.pack_begin(**pack)
+        if bal:
+            check(ctx.L.mpcekf_balance_begin(ctx.h, dptr(bal[0]), bal[1]))
         if links is not None:
             ctx.thermal_couple(links)
         if aging:
@@ -1288,14 +1391,17 @@ def runMPC(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=None,
         if term:
             check(ctx.L.mpcekf_term_begin(ctx.h, dptr(term[0]), term[1]))
         th_rows = ("temp", "heat", "cond") if links is not None else ("temp", "heat")
+        pk_rows = ("ucmd", "limiter", "bleed", "zmin") if bal and not aging and links is None else ("ucmd", "limiter")
         out = ctx.step(nsteps, tc=tc_traj, obs=obs, thermal=th_rows if thermal else None,
-                       pack=("ucmd", "limiter") if pack else None, aging=("rate",) if aging else None)
+                       pack=pk_rows if pack else None, aging=("rate",) if aging else None)
         if aging:
             out["aging"] = ctx.aging_record()
         if term:
             out["term"] = ctx.term_get()
         if pack:
             out["pack"] = ctx.pack_get()
+        if bal:
+            out["balance"] = ctx.balance_get()
         if links is not None:
             out["couple"] = ctx.thermal_couple_get()
         if thermal:
@@ -1315,7 +1421,8 @@ def run_summary(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=
     a chunk bounds the host array each call converts).  Neither host nor device memory grows
     with nsteps.  thermal: as runMPC's, its "schedule" included (no tc_traj); adds "thermal", the
     model's record.  pack: as runMPC's; adds "pack", the pack's record, beside the summary (whose
-    currents are the applied ones).  aging: as runMPC's; adds "aging", the side reactions' record.
+    currents are the applied ones), and with pack["balance"] "balance", the balancer's record.
+    aging: as runMPC's; adds "aging", the side reactions' record.
     thermal["couple"] with a pack: as runMPC's; adds "couple", the coupling's record.
     stop: a dict of Context.term_begin's keywords plus chunk (default 64): the loop runs through
     Context.step_until with nsteps as the cap and ends when every cell is done (no tc_traj: TC
@@ -1328,6 +1435,7 @@ def run_summary(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=
         raise ValueError(f"run_summary: chunk = {chunk}")
     tcs = None if tc_traj is None else tc_grid(tc_traj, nsteps, n)
     links = _couple_links(n, thermal, pack, "run_summary")
+    pack, bal = _pack_args(n, pack, "run_summary")
     term = _stop_args(n, stop, "run_summary", chunk=True)
     if term and tc_traj is not None:
         raise ValueError("run_summary: stop runs step_until, which takes one temperature row: no tc_traj")
@@ -1339,6 +1447,8 @@ def run_summary(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=
             _thermal_begin(ctx, thermal)
         if pack:
             ctx.pack_begin(**pack)
+        if bal:
+            check(ctx.L.mpcekf_balance_begin(ctx.h, dptr(bal[0]), bal[1]))
         if links is not None:
             ctx.thermal_couple(links)
         if aging:
@@ -1359,6 +1469,8 @@ def run_summary(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=
             out["aging"] = ctx.aging_record()
         if pack:
             out["pack"] = ctx.pack_get()
+        if bal:
+            out["balance"] = ctx.balance_get()
         if links is not None:
             out["couple"] = ctx.thermal_couple_get()
         if thermal:
