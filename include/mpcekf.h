@@ -779,6 +779,100 @@ int mpcekf_step_ex_balance(mpcekf_ctx *ctx, int32_t nsteps, const double *tc_deg
                            const int32_t *slots, int32_t nslots, double *obs, double *temp, double *heat, double *ucmd,
                            int32_t *limiter, double *bleed, double *zmin, int32_t outputs_on_device);
 
+/* ---- charger limits on pack strings: string voltage, current and power caps (not part of the reference interface) ----
+ * A string's current is bounded by its cells; a real charger adds a current and a power rating
+ * of its own.  At low SOC a long string asks for more power than any charger delivers, and the
+ * power-limited phase is the interesting part of a fast charge.  A charger is a property of a
+ * pack context (mpcekf_pack_begin first; a balancer may or may not be present).  On such a
+ * context the rule below runs once per fused step, after k_term, in the launch that couples the
+ * strings (k_charger in k_pack's or k_pack_bal's place): the charger adds no launch.
+ * Parameters, [nstrings] each (nstrings = ncells / series):
+ *   i_max   A, >= 0, or NaN: no current cap.  +inf is allowed and never binds.
+ *   p_max   W, > 0, or NaN: no power cap.  +inf is allowed and never binds.
+ * At fused step t, for string g = cells [g*S, (g+1)*S):
+ * 1. Terms.  v_i is the cell's s.vk (MPCEKF_S_VK), the plant voltage this step measured.  When
+ *    the cell's command in s.uk and v_i are both not NaN, x_i = v_i + 0.0 (one rounded addition,
+ *    which turns a -0.0 into +0.0) and the cell contributed.  Otherwise x_i = +0.0.  nvalid_g
+ *    counts the cells that contributed.
+ * 2. String voltage, a fixed tree over the in-string index i = 0 .. S-1:
+ *      for level j = 0, 1, ... while 2^j < S:
+ *        for every i that is a multiple of 2^(j+1) with i + 2^j < S:
+ *          x_i <- x_i + x_(i + 2^j)          (one rounded addition)
+ *      V_g = x_0
+ *    A partner at or beyond S is skipped.  No term is -0.0, so no partial sum is, and skipping
+ *    equals adding +0.0.  The shape depends on S only, never on the block, the wave or the lane a
+ *    cell sits in.  A floating-point sum is not associative: another order gives other bits.
+ * 3. String current before the charger.  m_g and the limiter come from the pack's rule, or, with
+ *    a balancer, from steps 1 to 4 of the balance rule (m_g = e_lim).  A string with no non-NaN
+ *    command writes nothing to s.uk, s.uk_1 and the u row: limiter = -1, capby = -1, istr = NaN,
+ *    and the charger record counts nothing.  vstr is still V_g.
+ * 4. Caps.  Charging current is negative, so a cap is a lower bound.
+ *      cap_i = -i_max                when i_max is not NaN
+ *      cap_p = -(p_max / V_g)        when p_max is not NaN and V_g > 0 (one rounded division, an
+ *                                    exact negation)
+ *    cap is the larger of the two by value; on a tie the current cap wins.  If a cap exists and
+ *    cap > m_g by value, then m'_g = cap bit for bit, capby = 1 (current) or 2 (power), and the
+ *    step's limiter entry is -2: no cell set the current.  Otherwise m'_g = m_g bit for bit,
+ *    capby = 0 and the limiter is unchanged.  A resting string (m_g = +0.0) and a discharging one
+ *    are never capped.
+ * 5. Applied current: the pack's rule, or step 5 of the balance rule, with m'_g in m_g's place.
+ *    a_c = m'_g + b_c (one rounded addition) for a bleeding cell, else a_c = m'_g.  s.uk, s.uk_1
+ *    and the step's u row get a_c; a cell with a NaN command is untouched.  The plant, k_summary,
+ *    k_aging, k_thermal, the next step's uk_1 and k_cl_diag read these locations, so they see
+ *    the capped current with no change of their own.
+ * 6. Records.  The pack record keeps its fields with m'_g in m_g's place: HEADROOM += m'_g - e_c
+ *    (e_c = u_c without a balancer), and NLIM counts nothing on a capped step.  The balance record
+ *    is unchanged.  The charger record, [nstrings] each, every value a double, counts exact
+ *    integers, sums sequential in step order from +0 with only finite terms added, accumulated
+ *    over any number of calls and reset by begin; a step counts when the string has a current:
+ *      STEPS       the steps with a string current
+ *      NCAP_I      the steps the current cap set the current
+ *      NCAP_P      the steps the power cap set the current
+ *      Q           the sum of m'_g, A*steps
+ *      E           the sum of V_g * m'_g (one rounded product), W*steps: the charger's own
+ *                  estimate, from the voltage measured under the previous step's current
+ *      CURTAIL     the sum of m'_g - m_g (one rounded subtraction), A*steps
+ *      P_MIN       the smallest product V_g * m'_g seen (the largest charging power); NaN: none
+ *      V_PEAK      the largest V_g seen; NaN: none
+ *      NVALID_MIN  the smallest nvalid_g seen; NaN: none
+ * 7. Identities.  Both parameters NaN (or +inf) everywhere leaves every bit of the same pack or
+ *    balancer context without a charger: u, ucmd, limiter, bleed, zmin, both older records and
+ *    the final state.  S = 1 works, with V_g = v + 0.0.
+ * The charger is a property of the context, like the pack: mpcekf_step, every _step_ex_*,
+ * _step_summary and _step_until run it, graph replay included, at both horizons and on every
+ * route of the fused step.  The kernel is not one of mpcekf_set_timing's five slots.
+ * Not modelled: a pack voltage limit or CV loop, charger efficiency, the stage route
+ * (mpcekf_mpc_step(_ex) neither couples nor caps), mpcekf_get_state / mpcekf_set_state carrying
+ * the record. */
+enum { MPCEKF_CHP_I_MAX = 0, MPCEKF_CHP_P_MAX, MPCEKF_NCHP };
+enum {
+  MPCEKF_CH_STEPS = 0, MPCEKF_CH_NCAP_I, MPCEKF_CH_NCAP_P, MPCEKF_CH_Q, MPCEKF_CH_E, MPCEKF_CH_CURTAIL,
+  MPCEKF_CH_P_MIN, MPCEKF_CH_V_PEAK, MPCEKF_CH_NVALID_MIN, MPCEKF_NCH
+};
+/* Gives the pack context a charger: params [MPCEKF_NCHP][nstrings].  Allocates the charger's
+ * device buffers (first call) and resets the record; a second begin replaces the first and
+ * resets likewise.  May be called before mpcekf_init_cells.  A later mpcekf_pack_begin with
+ * another series ends the charger (its arrays are per string); mpcekf_pack_end ends it.
+ * MPCEKF_E_STATE (nothing changed): no pack.  MPCEKF_E_ARG (nothing changed): a NULL pointer, a
+ * negative i_max, p_max <= 0. */
+int mpcekf_charger_begin(mpcekf_ctx *ctx, const double *params);
+/* values [nfields][nstrings]: row i = field fields[i] (distinct MPCEKF_CH_* ids).
+ * MPCEKF_E_STATE without a begin; MPCEKF_E_ARG: a NULL pointer, nfields outside
+ * 1..MPCEKF_NCH, an unknown or repeated id. */
+int mpcekf_charger_get(mpcekf_ctx *ctx, int32_t nfields, const int32_t *fields, double *values);
+/* Frees the charger; the cells keep their state and the context then behaves as a pack that
+ * never had one.  A no-op without a begin. */
+int mpcekf_charger_end(mpcekf_ctx *ctx);
+/* mpcekf_step_ex_balance's arguments (bleed / zmin must be NULL without a balancer --
+ * MPCEKF_E_STATE) plus the charger's rows (host, or device when outputs_on_device != 0), each
+ * may be NULL, [nsteps][ncells / series] each: vstr, V_g; istr, m'_g (NaN for a string without
+ * a current); capby, int32: -1 / 0 / 1 / 2.  MPCEKF_E_STATE without a charger; a refused call
+ * leaves the context and the records as they were. */
+int mpcekf_step_ex_charger(mpcekf_ctx *ctx, int32_t nsteps, const double *tc_degC, const mpcekf_traj *traj,
+                           const int32_t *slots, int32_t nslots, double *obs, double *temp, double *heat, double *ucmd,
+                           int32_t *limiter, double *bleed, double *zmin, double *vstr, double *istr, int32_t *capby,
+                           int32_t outputs_on_device);
+
 /* ---- side-reaction losses per cell along the fused loop (not part of the reference interface) ----
  * runMPC.m keeps phise_store above mpcData.const.phise_min so that lithium does not plate.  How
  * much a protocol plated, or how much SEI (the solid-electrolyte interphase film on the negative

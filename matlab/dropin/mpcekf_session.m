@@ -21,13 +21,23 @@ function [S, out] = mpcekf_session(op, name, value)
 %   [S, out] = mpcekf_session('stepuntil', max_steps, chunk)
 %     fused steps in calls of chunk (default 64) until no cell is open or max_steps are run
 %     (mpcekf_step_until): out.steps_run, out.open.
+%   mpcekf_session('chargerbegin', params)
+%     a charger's ratings on the session's pack context (mpcekf_charger_begin): params nstrings x 2,
+%     columns i_max (A) and p_max (W), NaN: that cap off.  Without params the session's optional
+%     field `charger` (mpcekf_session('set', 'charger', params)) is used; a begin stores its params there.
+%   [S, out] = mpcekf_session('chargerget')  out: the record, a struct of nstrings x 1 vectors (steps,
+%     ncap_i, ncap_p, q, e, curtail, p_min, v_peak, nvalid_min)
+%   mpcekf_session('chargerend')
+%   [S, out] = mpcekf_session('stepexcharger', nsteps)
+%     out.u .. out.limiter as 'stepexpack' gives them, out.bal (bleed, zmin; [] without a balancer)
+%     and out.chg (vstr, istr, capby), nstrings x nsteps each.
   persistent P
   % zk_last / ekf_tick: the zk the last iterEKF returned and a counter of iterEKF calls, so
   % EKFmatsHandler knows when the library's device copies of zk and Xind are the caller's
   % xhat_dev: the xhat the device-resident linearisation records hold (EKFmatsHandler's, or
   % the xk an iterMPC call wrote over it)
   if isempty(P), P = struct('h', [], 'kf', [], 'mpc', [], 'device', 0, 'zk_last', [], 'ekf_tick', 0, ...
-                            'xhat_dev', []); end
+                            'xhat_dev', [], 'charger', []); end
   out = [];
   switch op
     case 'set'
@@ -97,6 +107,22 @@ function [S, out] = mpcekf_session(op, name, value)
           mpcekf_mex('balanceend', P.h);
         case 'stepexbalance'
           [o.u, o.v, o.soc, o.phise, o.nexec, o.ucmd, o.limiter, o.bleed, o.zmin] = mpcekf_mex('stepexbalance', P.h, name);
+          out = o;
+      end
+    case {'chargerbegin', 'chargerget', 'chargerend', 'stepexcharger'}
+      if isempty(P.h), error('mpcekf_session: %s before the first OB_step call created the context', op); end
+      switch op
+        case 'chargerbegin'
+          if nargin < 2 || isempty(name), name = P.charger; end
+          if isempty(name), error('mpcekf_session: chargerbegin: no params and no charger field set'); end
+          mpcekf_mex('chargerbegin', P.h, name);
+          P.charger = name;
+        case 'chargerget'
+          out = mpcekf_mex('chargerget', P.h);
+        case 'chargerend'
+          mpcekf_mex('chargerend', P.h);
+        case 'stepexcharger'
+          [o.u, o.v, o.soc, o.phise, o.nexec, o.ucmd, o.limiter, o.bal, o.chg] = mpcekf_mex('stepexcharger', P.h, name);
           out = o;
       end
     otherwise

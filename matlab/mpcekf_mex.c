@@ -138,6 +138,22 @@
  *                       mpcekf_step_ex_balance:
  *                       'stepexpack' on a context with a balancer, plus each cell's bleed current,
  *                       ncells x nsteps, and each string's smallest soc, nstrings x nsteps
+ *                       mpcekf_mex('chargerbegin', h, params)          mpcekf_charger_begin
+ *                       a charger's ratings on a pack ('packbegin' first; with or without a balancer):
+ *                       params nstrings x 2, columns i_max (A, >= 0) and p_max (W, > 0), NaN: that cap
+ *                       is off.  From then on every fused step adds up each string's voltage and
+ *                       raises its charging current to -i_max and -p_max / V where those are larger
+ *   s                 = mpcekf_mex('chargerget', h)                    mpcekf_charger_get
+ *                       struct of nstrings x 1 column vectors: steps, ncap_i, ncap_p, q, e, curtail,
+ *                       p_min, v_peak, nvalid_min (MPCEKF_CH_*)
+ *                       mpcekf_mex('chargerend', h)                    mpcekf_charger_end
+ *   [u,v,soc,phise,nexec,ucmd,limiter,bal,chg] = mpcekf_mex('stepexcharger', h, nsteps[, tc])
+ *                       mpcekf_step_ex_charger:
+ *                       'stepexpack' on a context with a charger (limiter: 1-based, 0 no command, -1 a
+ *                       cap set the current), plus two structs: bal with bleed (ncells x nsteps) and
+ *                       zmin (nstrings x nsteps), both [] on a context without a balancer; chg with
+ *                       vstr, istr (nstrings x nsteps) and capby (int32: -1 no current, 0 not capped,
+ *                       1 the current cap, 2 the power cap)
  *   [steps_run, open] = mpcekf_mex('stepuntil', h, max_steps, chunk[, tc])   mpcekf_step_until
  *                       fused steps in calls of `chunk` until no cell is open or max_steps are
  *                       run; tc: [] or ncells temperatures, the same for every step
@@ -480,7 +496,8 @@ static void gateway(mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
                                             "packbegin", "packget", "packend", "stepexpack",
                                             "agingbegin", "agingget", "agingend", "stepexaging",
                                             "termbegin", "termget", "termend", "stepuntil",
-                                            "balancebegin", "balanceget", "balanceend", "stepexbalance"};
+                                            "balancebegin", "balanceget", "balanceend", "stepexbalance",
+                                            "chargerbegin", "chargerget", "chargerend", "stepexcharger"};
   int known = 0;
   for (size_t i = 0; i < sizeof with_handle / sizeof *with_handle; ++i) known = known || !strcmp(cmd, with_handle[i]);
   if (!known) mexErrMsgIdAndTxt("mpcekf:arg", "unknown command %s", cmd);
@@ -756,6 +773,29 @@ static void gateway(mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
     blsteps = (int32_t)nsd;
     if (nrhs > 3 && !mxIsEmpty(prhs[3]) && (!mxIsDouble(prhs[3]) || mxIsComplex(prhs[3])))
       mexErrMsgIdAndTxt("mpcekf:arg", "stepexbalance: tc: expected [] or ncells x nsteps real doubles");
+  }
+  /* the charger commands likewise: output count, params that are no real doubles, an nsteps that
+     is no non-negative integer, a tc of the wrong class */
+  const int chbegin = !strcmp(cmd, "chargerbegin"), stepch = !strcmp(cmd, "stepexcharger");
+  int32_t chsteps = 0;
+  if ((chbegin || !strcmp(cmd, "chargerend")) && g_nlhs > 0) mexErrMsgIdAndTxt("mpcekf:arg", "%s: no output", cmd);
+  if (!strcmp(cmd, "chargerget") && g_nlhs > 1) mexErrMsgIdAndTxt("mpcekf:arg", "chargerget: at most 1 output");
+  if (stepch && g_nlhs > 9)
+    mexErrMsgIdAndTxt("mpcekf:arg",
+                      "stepexcharger: at most 9 outputs [u, v, soc, phise, nexec, ucmd, limiter, bal, chg]");
+  if (chbegin) {
+    need(nrhs, 3, "'chargerbegin', h, params");
+    if (!mxIsDouble(prhs[2]) || mxIsComplex(prhs[2]))
+      mexErrMsgIdAndTxt("mpcekf:arg", "chargerbegin: params: expected nstrings x 2 real doubles");
+  }
+  if (stepch) {
+    need(nrhs, 3, "'stepexcharger', h, nsteps[, tc]");
+    const double nsd = scalar(prhs[2], "nsteps");
+    if (!(nsd >= 0 && nsd <= 2147483647.0) || nsd != (double)(int32_t)nsd)
+      mexErrMsgIdAndTxt("mpcekf:arg", "nsteps: expected a non-negative integer");
+    chsteps = (int32_t)nsd;
+    if (nrhs > 3 && !mxIsEmpty(prhs[3]) && (!mxIsDouble(prhs[3]) || mxIsComplex(prhs[3])))
+      mexErrMsgIdAndTxt("mpcekf:arg", "stepexcharger: tc: expected [] or ncells x nsteps real doubles");
   }
   mpcekf_ctx *h = handle(prhs[1]);
   int64_t n = 0;
@@ -1075,6 +1115,64 @@ static void gateway(mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
     chk(mpcekf_step_ex_balance(h, blsteps, tc, &tr, NULL, 0, NULL, NULL, NULL, mxGetDoubles(plhs[5]),
                                series ? lim : NULL, mxGetDoubles(plhs[7]), series ? mxGetDoubles(plhs[8]) : NULL, 0));
     for (size_t i = 0; i < nstr * (size_t)blsteps; ++i) lim[i] += 1; /* 1-based; 0: no command */
+  } else if (chbegin) {
+    /* nstrings x 2 column-major is the library's [MPCEKF_NCHP][nstrings] as it stands; without a
+       'packbegin' the library refuses the call whatever the size */
+    const int32_t series = *series_of(h);
+    const size_t nstr = series ? nc / (size_t)series : nc;
+    chk(mpcekf_charger_begin(h, dvec(prhs[2], nstr * MPCEKF_NCHP, "chargerbegin: params (nstrings x 2)")));
+  } else if (!strcmp(cmd, "chargerget")) {
+    static const char *const ch_names[MPCEKF_NCH] = {"steps", "ncap_i", "ncap_p", "q", "e", "curtail",
+                                                     "p_min", "v_peak", "nvalid_min"};
+    const int32_t series = *series_of(h);
+    const size_t nstr = series ? nc / (size_t)series : nc;
+    int32_t ids[MPCEKF_NCH];
+    double *vals = (double *)mxMalloc((size_t)MPCEKF_NCH * nstr * sizeof(double) + 8);
+    for (int f = 0; f < MPCEKF_NCH; ++f) ids[f] = f;
+    chk(mpcekf_charger_get(h, MPCEKF_NCH, ids, vals));
+    plhs[0] = mxCreateStructMatrix(1, 1, MPCEKF_NCH, (const char **)ch_names);
+    for (int f = 0; f < MPCEKF_NCH; ++f) {
+      mxArray *a = dmat(nstr, 1);
+      if (nstr) memcpy(mxGetDoubles(a), vals + (size_t)f * nstr, nstr * sizeof(double));
+      mxSetField(plhs[0], 0, ch_names[f], a);
+    }
+    mxFree(vals);
+  } else if (!strcmp(cmd, "chargerend")) {
+    chk(mpcekf_charger_end(h));
+  } else if (stepch) {
+    /* without a 'chargerbegin' the library refuses the call before it touches a row */
+    static const char *const bal_names[2] = {"bleed", "zmin"};
+    static const char *const chg_names[3] = {"vstr", "istr", "capby"};
+    const int32_t series = *series_of(h);
+    const size_t nstr = series ? nc / (size_t)series : 0;
+    const double *tc = nrhs > 3 ? opt_vec(prhs[3], nc * (size_t)chsteps, "stepexcharger: tc (ncells x nsteps)") : NULL;
+    /* a balancer's rows only where there is one: a refused one-field get changes nothing */
+    int32_t id0 = 0;
+    double *probe = (double *)mxMalloc(nc * sizeof(double) + 8);
+    const int has_bal = mpcekf_balance_get(h, 1, &id0, probe) == MPCEKF_OK;
+    mxFree(probe);
+    for (int i = 0; i < 6; ++i) plhs[i] = i == 4 ? imat(nc, (size_t)chsteps) : dmat(nc, (size_t)chsteps);
+    plhs[6] = imat(nstr, (size_t)chsteps);
+    mxArray *bleed = has_bal ? dmat(nc, (size_t)chsteps) : dmat(0, 0);
+    mxArray *zmin = has_bal ? dmat(nstr, (size_t)chsteps) : dmat(0, 0);
+    mxArray *vstr = dmat(nstr, (size_t)chsteps), *istr = dmat(nstr, (size_t)chsteps), *capby = imat(nstr, (size_t)chsteps);
+    plhs[7] = mxCreateStructMatrix(1, 1, 2, (const char **)bal_names);
+    mxSetField(plhs[7], 0, "bleed", bleed);
+    mxSetField(plhs[7], 0, "zmin", zmin);
+    plhs[8] = mxCreateStructMatrix(1, 1, 3, (const char **)chg_names);
+    mxSetField(plhs[8], 0, "vstr", vstr);
+    mxSetField(plhs[8], 0, "istr", istr);
+    mxSetField(plhs[8], 0, "capby", capby);
+    mpcekf_traj tr;
+    memset(&tr, 0, sizeof tr);
+    tr.u = mxGetDoubles(plhs[0]); tr.v = mxGetDoubles(plhs[1]); tr.soc = mxGetDoubles(plhs[2]);
+    tr.phise = mxGetDoubles(plhs[3]); tr.nexec = (int32_t *)mxGetData(plhs[4]);
+    int32_t *lim = (int32_t *)mxGetData(plhs[6]);
+    chk(mpcekf_step_ex_charger(h, chsteps, tc, &tr, NULL, 0, NULL, NULL, NULL, mxGetDoubles(plhs[5]), series ? lim : NULL,
+                               has_bal ? mxGetDoubles(bleed) : NULL, has_bal && series ? mxGetDoubles(zmin) : NULL,
+                               series ? mxGetDoubles(vstr) : NULL, series ? mxGetDoubles(istr) : NULL,
+                               series ? (int32_t *)mxGetData(capby) : NULL, 0));
+    for (size_t i = 0; i < nstr * (size_t)chsteps; ++i) lim[i] += 1; /* 1-based; 0: no command, -1: capped */
   } else if (tmbegin) {
     /* ncells x 3 column-major is the library's [MPCEKF_NTMP][ncells] as it stands */
     chk(mpcekf_term_begin(h, dvec(prhs[2], nc * MPCEKF_NTMP, "termbegin: params (ncells x 3)"), tmhold));

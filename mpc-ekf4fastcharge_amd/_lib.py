@@ -45,6 +45,9 @@ TERM_OPEN, TERM_LATCHED, TERM_DEAD = range(3)
 # MPCEKF_BLP_* / MPCEKF_BL_*: the balancer's per-cell parameters and record (mpcekf_balance_begin / _get)
 BALANCE_PARAMS = ("i_bleed", "dz_on", "dz_off")
 BALANCE_FIELDS = ("steps_on", "q_bleed", "switches", "dz_max", "dz_last", "steps")
+# MPCEKF_CHP_* / MPCEKF_CH_*: the charger's per-string parameters and record (mpcekf_charger_begin / _get)
+CHARGER_PARAMS = ("i_max", "p_max")
+CHARGER_FIELDS = ("steps", "ncap_i", "ncap_p", "q", "e", "curtail", "p_min", "v_peak", "nvalid_min")
 # MPCEKF_AG_* / MPCEKF_AGR_*: one side reaction's parameters and the aging record's fields
 # (mpcekf_aging_begin / _get); MPCEKF_AG_SRC_*: the sources' bits
 AGING_PARAMS = ("i0", "U", "alpha", "Ea", "gate")
@@ -118,6 +121,7 @@ EXPORTS = [
     "mpcekf_thermal_schedule", "mpcekf_thermal_schedule_end",
     "mpcekf_term_begin", "mpcekf_term_get", "mpcekf_term_open", "mpcekf_term_end", "mpcekf_step_until",
     "mpcekf_balance_begin", "mpcekf_balance_get", "mpcekf_balance_end", "mpcekf_step_ex_balance",
+    "mpcekf_charger_begin", "mpcekf_charger_get", "mpcekf_charger_end", "mpcekf_step_ex_charger",
     "mpcekf_thermal_couple", "mpcekf_thermal_couple_get", "mpcekf_thermal_couple_end", "mpcekf_step_ex_couple",
     # the _async stage twins (include/mpcekf.h)
     "mpcekf_plant_step_async", "mpcekf_ekf_step_async", "mpcekf_linearize_async", "mpcekf_lin_fields_async",
@@ -215,6 +219,11 @@ def load():
     L.mpcekf_balance_get.argtypes = [vp, C.c_int32, _ip, _dp]
     L.mpcekf_balance_end.argtypes = [vp]
     L.mpcekf_step_ex_balance.argtypes = [vp, C.c_int32, vp, C.POINTER(Traj), _ip, C.c_int32, vp, vp, vp, vp, vp, vp, vp, C.c_int32]
+    L.mpcekf_charger_begin.argtypes = [vp, _dp]
+    L.mpcekf_charger_get.argtypes = [vp, C.c_int32, _ip, _dp]
+    L.mpcekf_charger_end.argtypes = [vp]
+    L.mpcekf_step_ex_charger.argtypes = [vp, C.c_int32, vp, C.POINTER(Traj), _ip, C.c_int32, vp, vp, vp, vp, vp, vp, vp,
+                                         vp, vp, vp, C.c_int32]
     L.mpcekf_thermal_couple.argtypes = [vp, _dp]
     L.mpcekf_thermal_couple_get.argtypes = [vp, C.c_int32, _ip, _dp]
     L.mpcekf_thermal_couple_end.argtypes = [vp]

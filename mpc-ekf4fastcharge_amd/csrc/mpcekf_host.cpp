@@ -27,6 +27,7 @@
 #include "mpcekf_eig.hpp"
 #include "mpcekf_kernels.hpp"
 #include "mpcekf_balance.hpp"
+#include "mpcekf_charger.hpp"
 #include "mpcekf_pack.hpp"
 #include "mpcekf_term.hpp"
 #include "mpcekf_summary.hpp"
@@ -323,6 +324,10 @@ struct mpcekf_ctx {
   double *d_bl = nullptr, *d_bl_par = nullptr, *d_bl_soc = nullptr;
   int *d_bl_on = nullptr;
   int32_t bl_comp = 0;
+  // mpcekf_charger_begin .. _end (needs a pack): the record [NCHR][nstrings] and the parameters
+  // [NCHP][nstrings], for the pk_series the begin found (a pack_begin with another ends the
+  // charger).  d_ch != nullptr: every fused step runs k_charger in k_pack's / k_pack_bal's place.
+  double *d_ch = nullptr, *d_ch_par = nullptr;
   double *d_uk1p = nullptr;                      // [n] uk_1 before the step (poles / sv)
   int flush_period = LAZY_H;      // steps between all-model flushes (<= LAZY_H)
   // rolling flush (MPCEKF_FLUSH_ROLL=1, off by default): step t flushes the cell slice
@@ -1238,7 +1243,7 @@ int mpcekf_ctx_destroy(mpcekf_ctx *X) {
                   X->w.prob, X->w.X, X->w.R, X->w.K, X->w.hii, X->w.it, X->w.smin, X->d_lin, X->d_zsoc, X->d_mb, X->d_uk1p,
                   X->w.q, X->w.list, X->w.hist, X->d_poly, X->d_szk, X->d_sxg, X->d_sxm, X->d_slin, X->d_sv, X->d_zslot,
                   X->d_obs_blob, X->d_obs, X->d_obs_plan, X->d_lim, X->d_sch_hdr, X->d_sch_tab, X->d_sch_val, X->d_sch_set, X->d_sum, X->d_sum_reach, X->d_sum_obs,
-                  X->d_sum_ring, X->d_pk, X->d_tc, X->d_tc_link, X->d_tc_snap, X->d_ag, X->d_ag_par, X->d_ag_phi, X->d_ag_obs, X->d_ag_plan, X->d_tm, X->d_tm_par, X->d_tm_soc, X->d_tm_int, X->d_bl, X->d_bl_par, X->d_bl_soc, X->d_bl_on, X->d_th, X->d_th_par, X->d_th_i, X->d_th_ocv, X->d_hot, X->d_hot_i, X->d_hotp, X->d_hotp_i};
+                  X->d_sum_ring, X->d_pk, X->d_tc, X->d_tc_link, X->d_tc_snap, X->d_ag, X->d_ag_par, X->d_ag_phi, X->d_ag_obs, X->d_ag_plan, X->d_tm, X->d_tm_par, X->d_tm_soc, X->d_tm_int, X->d_bl, X->d_bl_par, X->d_bl_soc, X->d_bl_on, X->d_ch, X->d_ch_par, X->d_th, X->d_th_par, X->d_th_i, X->d_th_ocv, X->d_hot, X->d_hot_i, X->d_hotp, X->d_hotp_i};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   for (auto &g : X->graphs) (void)hipGraphExecDestroy(g.exec);
@@ -1372,6 +1377,10 @@ static int lerr(int rc, const char *what) {
 // step's soc row (the context's own when the call has none) and the cells' flags, and stores the
 // applied currents; bleed [nsteps][ncells] and zmin [nsteps][ncells / series]
 // (mpcekf_step_ex_balance) are two more output fields, written by that kernel.
+// A charger context (mpcekf_charger_begin, on a pack): k_charger in k_pack's or k_pack_bal's place
+// also reads s.vk and stores the applied currents after the charger's caps; vstr, istr
+// [nsteps][ncells / series] and capby likewise (mpcekf_step_ex_charger) are three more output
+// fields, written by that kernel.
 // A coupled context (mpcekf_thermal_couple): k_couple_seed once before the call's first step,
 // and k_thermal_couple(_sched) in k_thermal(_sched)'s place reads each cell's neighbours from
 // the snapshot of the step's parity; cond [nsteps][ncells] (mpcekf_step_ex_couple) is one more
@@ -1380,7 +1389,7 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
                      const int32_t *slots, int32_t nslots, double *obs, int32_t outputs_on_device,
                      bool sum = false, double *temp = nullptr, double *heat = nullptr, double *ucmd = nullptr,
                      int32_t *limiter = nullptr, double *rate = nullptr, double *cond = nullptr, double *bleed = nullptr,
-                     double *zmin = nullptr) {
+                     double *zmin = nullptr, double *vstr = nullptr, double *istr = nullptr, int32_t *capby = nullptr) {
   // a thermal context owns the temperature: refused before anything of the context changes
   if (X && X->d_th && tc_degC)
     return fail(MPCEKF_E_ARG, "step: tc_degC on a thermal context (mpcekf_thermal_begin): the model sets the temperature");
@@ -1394,6 +1403,7 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
   const bool coupled = X->d_tc != nullptr;  // thermal && pack: either's end ends the coupling
   const bool term = X->d_tm != nullptr;
   const bool balance = pack && X->d_bl != nullptr;
+  const bool charger = pack && X->d_ch != nullptr;
   const bool term_str = term && pack && X->pk_series > 1;  // strings whose cells follow their first latched one
   const bool ag_est = aging && (X->ag_sources & MPCEKF_AG_SRC_EST), ag_plant = aging && (X->ag_sources & MPCEKF_AG_SRC_PLANT);
   if (sum && X->sum_slot >= 0) {  // checked by mpcekf_summary_begin
@@ -1441,7 +1451,11 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
            {rate, 8, aging ? (size_t)(((int)ag_est + (int)ag_plant) * X->ag_nreact) : 0, nullptr},
            {cond, 8, 1, nullptr},  // k_thermal_couple's row (a coupled context's only)
            {bleed, 8, 1, nullptr},  // k_pack_bal's rows (a balancing context's only)
-           {zmin, 8, 1, nullptr, pack ? n / (size_t)X->pk_series : 0}};  // [nsteps][nstrings]
+           {zmin, 8, 1, nullptr, pack ? n / (size_t)X->pk_series : 0},  // [nsteps][nstrings]
+           // k_charger's rows (a charger context's only): [nsteps][nstrings] each
+           {vstr, 8, 1, nullptr, pack ? n / (size_t)X->pk_series : 0},
+           {istr, 8, 1, nullptr, pack ? n / (size_t)X->pk_series : 0},
+           {capby, 4, 1, nullptr, pack ? n / (size_t)X->pk_series : 0}};
   constexpr int NF = sizeof(f) / sizeof(f[0]);
   auto step_bytes = [&](const F &e) -> size_t { return (e.rows ? e.rows : n) * e.width * e.esz; };  // one step's block
   const double *dtc = tc_degC;  // [nsteps][n] device copy of the per-step temperatures
@@ -1731,9 +1745,9 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
         q.rec = X->d_pk;
         q.n = X->n;
         q.series = X->pk_series;
-        if (balance) {  // the bleeders' switching and the strings' currents in one launch
-          KPackBal b{};
-          b.p = q;
+        KPackBal b{};
+        b.p = q;
+        if (balance) {
           b.soc = io.soc;
           b.par = X->d_bl_par;
           b.on = X->d_bl_on;
@@ -1741,6 +1755,18 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
           b.bleed = (double *)row(21, k);
           b.zmin = (double *)row(22, k);
           b.compensate = X->bl_comp;
+        }
+        if (charger) {  // the strings' voltages and caps, the bleeders' switching and the currents in one launch
+          KCharger h{};
+          h.b = b;
+          h.vk = X->s.vk;
+          h.par = X->d_ch_par;
+          h.rec = X->d_ch;
+          h.vstr = (double *)row(23, k);
+          h.istr = (double *)row(24, k);
+          h.capby = (int *)row(25, k);
+          if ((rc = lerr(launch_charger(h, X->stream), "charger"))) return rc;
+        } else if (balance) {  // the bleeders' switching and the strings' currents in one launch
           if ((rc = lerr(launch_pack_bal(b, X->stream), "pack_bal"))) return rc;
         } else if ((rc = lerr(launch_pack(q, X->stream), "pack"))) {
           return rc;
@@ -1851,7 +1877,11 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
                                   // retires the graphs that name it
                                   (uintptr_t)(balance ? X->d_bl : nullptr), (uintptr_t)(balance ? X->d_bl_par : nullptr),
                                   (uintptr_t)(balance ? X->d_bl_on : nullptr), (uintptr_t)(balance ? X->bl_comp : 0),
-                                  (uintptr_t)(balance ? X->d_bl_soc : nullptr)};
+                                  (uintptr_t)(balance ? X->d_bl_soc : nullptr),
+                                  // the charger twenty-second and twenty-third (its vstr / istr / capby rows
+                                  // are among the output rows below): 0 on a context without one --
+                                  // mpcekf_charger_end retires the graphs that name it
+                                  (uintptr_t)(charger ? X->d_ch : nullptr), (uintptr_t)(charger ? X->d_ch_par : nullptr)};
     for (const F &e : f) key.push_back((uintptr_t)e.dev);
     key.push_back((uintptr_t)osel.plan);  // a regrown plan buffer retires the graphs that named the old one
     key.push_back((uintptr_t)nslots);
@@ -2380,6 +2410,8 @@ int mpcekf_pack_begin(mpcekf_ctx *X, int32_t series) {
   if (X->n % series)
     return fail(MPCEKF_E_ARG, "pack_begin: series = %d does not divide ncells = %lld", series, (long long)X->n);
   int rc;
+  // the charger's arrays are per string: another string length ends it
+  if (X->d_ch && series != X->pk_series && (rc = mpcekf_charger_end(X))) return rc;
   HIPCHK(hipSetDevice(X->device));
   const size_t n = std::max<size_t>((size_t)X->n, 1);
   double *rec = X->d_pk;
@@ -2422,6 +2454,7 @@ int mpcekf_pack_end(mpcekf_ctx *X) {
   int rc = mpcekf_thermal_couple_end(X);  // links need strings
   if (rc) return rc;
   if ((rc = mpcekf_balance_end(X))) return rc;  // and so does a balancer
+  if ((rc = mpcekf_charger_end(X))) return rc;  // and a charger
   HIPCHK(hipSetDevice(X->device));
   HIPCHK(hipStreamSynchronize(X->stream));
   // the graphs captured on a pack context launch k_pack on the record: retired before it is freed
@@ -2548,6 +2581,100 @@ int mpcekf_step_ex_balance(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC,
     return fail(MPCEKF_E_STATE, "step_ex_balance: temp / heat rows: call mpcekf_thermal_begin first");
   return step_impl(X, nsteps, tc_degC, tr, slots, nslots, obs, outputs_on_device, false, temp, heat, ucmd, limiter,
                    nullptr, nullptr, bleed, zmin);
+}
+
+// ---- charger limits on pack strings along the fused loop (mpcekf_charger.hip) ----
+static_assert(NCHP == MPCEKF_NCHP && CHP_I_MAX == MPCEKF_CHP_I_MAX && CHP_P_MAX == MPCEKF_CHP_P_MAX &&
+                  NCHR == MPCEKF_NCH && CH_STEPS == MPCEKF_CH_STEPS && CH_NCAP_I == MPCEKF_CH_NCAP_I &&
+                  CH_NCAP_P == MPCEKF_CH_NCAP_P && CH_Q == MPCEKF_CH_Q && CH_E == MPCEKF_CH_E &&
+                  CH_CURTAIL == MPCEKF_CH_CURTAIL && CH_P_MIN == MPCEKF_CH_P_MIN && CH_V_PEAK == MPCEKF_CH_V_PEAK &&
+                  CH_NVALID_MIN == MPCEKF_CH_NVALID_MIN,
+              "mpcekf_charger.hpp's rows are include/mpcekf.h's MPCEKF_CHP_* / MPCEKF_CH_*");
+
+int mpcekf_charger_begin(mpcekf_ctx *X, const double *params) {
+  if (!X) return fail(MPCEKF_E_ARG, "charger_begin: null ctx");
+  if (!params) return fail(MPCEKF_E_ARG, "charger_begin: null params");
+  if (!X->d_pk) return fail(MPCEKF_E_STATE, "charger_begin: call mpcekf_pack_begin first");
+  const size_t ns = (size_t)X->n / (size_t)X->pk_series;
+  for (size_t g = 0; g < ns; ++g) {
+    const double im = params[CHP_I_MAX * ns + g], pm = params[CHP_P_MAX * ns + g];
+    if (im == im && !(im >= 0.0)) return fail(MPCEKF_E_ARG, "charger_begin: i_max[%zu] = %g: a current >= 0, or NaN", g, im);
+    if (pm == pm && !(pm > 0.0)) return fail(MPCEKF_E_ARG, "charger_begin: p_max[%zu] = %g: a power > 0, or NaN", g, pm);
+  }
+  int rc;
+  HIPCHK(hipSetDevice(X->device));
+  const size_t n = std::max<size_t>(ns, 1);
+  // every buffer before anything is stored: a failed allocation leaves the context as it was
+  double *rec = X->d_ch, *par = X->d_ch_par;
+  if ((!rec && (rc = dalloc(&rec, n * NCHR))) || (!par && (rc = dalloc(&par, n * NCHP)))) {
+    if (rec != X->d_ch) (void)hipFree(rec);
+    return rc;
+  }
+  // a first begin changes the launch sequence: the graphs of the charger-free pack are not
+  // replayed (their key holds 0 where these buffers now stand), so nothing is retired here
+  X->d_ch = rec;
+  X->d_ch_par = par;
+  // behind every launch of an earlier call, which the stream orders before these
+  if (ns) HIPCHK(hipMemcpyAsync(par, params, ns * NCHP * 8, hipMemcpyHostToDevice, X->stream));
+  if ((rc = lerr(launch_charger_reset(rec, (int64_t)ns, X->stream), "charger_reset"))) return rc;
+  HIPCHK(hipStreamSynchronize(X->stream));
+  return MPCEKF_OK;
+}
+
+int mpcekf_charger_get(mpcekf_ctx *X, int32_t nfields, const int32_t *fields, double *values) {
+  if (!X) return fail(MPCEKF_E_ARG, "charger_get: null ctx");
+  if (nfields < 1 || nfields > MPCEKF_NCH)
+    return fail(MPCEKF_E_ARG, "charger_get: nfields = %d outside 1..%d", nfields, (int)MPCEKF_NCH);
+  if (!fields) return fail(MPCEKF_E_ARG, "charger_get: null fields");
+  if (!values) return fail(MPCEKF_E_ARG, "charger_get: null values");
+  unsigned seen = 0;
+  for (int i = 0; i < nfields; ++i) {
+    if (fields[i] < 0 || fields[i] >= MPCEKF_NCH)
+      return fail(MPCEKF_E_ARG, "charger_get: fields[%d] = %d is not a MPCEKF_CH_* id (0..%d)", i, fields[i],
+                  (int)MPCEKF_NCH - 1);
+    if (seen >> fields[i] & 1) return fail(MPCEKF_E_ARG, "charger_get: fields: id %d given twice", fields[i]);
+    seen |= 1u << fields[i];
+  }
+  if (!X->d_pk || !X->d_ch) return fail(MPCEKF_E_STATE, "charger_get: call mpcekf_charger_begin first");
+  HIPCHK(hipSetDevice(X->device));
+  const size_t ns = (size_t)X->n / (size_t)X->pk_series;
+  for (int i = 0; i < nfields && ns; ++i)
+    HIPCHK(hipMemcpyAsync(values + (size_t)i * ns, X->d_ch + (size_t)fields[i] * ns, ns * 8, hipMemcpyDeviceToHost,
+                          X->stream));
+  HIPCHK(hipStreamSynchronize(X->stream));
+  return MPCEKF_OK;
+}
+
+int mpcekf_charger_end(mpcekf_ctx *X) {
+  if (!X) return fail(MPCEKF_E_ARG, "charger_end: null ctx");
+  if (!X->d_ch) return MPCEKF_OK;
+  HIPCHK(hipSetDevice(X->device));
+  HIPCHK(hipStreamSynchronize(X->stream));
+  // the graphs captured on a charger context launch k_charger on these buffers: retired before
+  // they are freed
+  for (size_t i = X->graphs.size(); i-- > 0;)
+    if (X->graphs[i].key[21]) {
+      (void)hipGraphExecDestroy(X->graphs[i].exec);
+      X->graphs.erase(X->graphs.begin() + (std::ptrdiff_t)i);
+    }
+  (void)hipFree(X->d_ch);
+  if (X->d_ch_par) (void)hipFree(X->d_ch_par);
+  X->d_ch = X->d_ch_par = nullptr;
+  return MPCEKF_OK;
+}
+
+int mpcekf_step_ex_charger(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const mpcekf_traj *tr,
+                           const int32_t *slots, int32_t nslots, double *obs, double *temp, double *heat, double *ucmd,
+                           int32_t *limiter, double *bleed, double *zmin, double *vstr, double *istr, int32_t *capby,
+                           int32_t outputs_on_device) {
+  if (!X) return fail(MPCEKF_E_ARG, "step_ex_charger: null ctx");
+  if (!X->d_pk || !X->d_ch) return fail(MPCEKF_E_STATE, "step_ex_charger: call mpcekf_charger_begin first");
+  if ((bleed || zmin) && !X->d_bl)
+    return fail(MPCEKF_E_STATE, "step_ex_charger: bleed / zmin rows: call mpcekf_balance_begin first");
+  if ((temp || heat) && !X->d_th)
+    return fail(MPCEKF_E_STATE, "step_ex_charger: temp / heat rows: call mpcekf_thermal_begin first");
+  return step_impl(X, nsteps, tc_degC, tr, slots, nslots, obs, outputs_on_device, false, temp, heat, ucmd, limiter,
+                   nullptr, nullptr, bleed, zmin, vstr, istr, capby);
 }
 
 // ---- charge termination along the fused loop (mpcekf_term.hip) ----

@@ -301,7 +301,11 @@ class Context:
         pack context couples its strings all the same).  On a context with a balancer
         (balance_begin) also "bleed" [nsteps, ncells], each cell's bleed current (NaN for a cell
         with a NaN command), and / or "zmin" [nsteps, ncells // series], each string's smallest
-        soc; mpcekf_step_ex_balance, which has no "cond" or "rate" row.
+        soc; mpcekf_step_ex_balance, which has no "cond" or "rate" row.  On a context with a charger
+        (charger_begin) also "vstr", "istr" [nsteps, ncells // series], each string's voltage and
+        its current after the charger's caps, and / or "capby" (int32: -1 no current, 0 not capped,
+        1 the current cap, 2 the power cap); mpcekf_step_ex_charger, which has no "cond" or "rate"
+        row either.
         ``aging``: on an aging context (aging_begin), ("rate",) returns out["rate"]
         [nsteps, nsrc * nreact, ncells], every step's side-reaction currents (A): the enabled
         sources in the order est, plant, the reactions inside; mpcekf_step_ex_aging.  None: the
@@ -316,12 +320,17 @@ class Context:
             raise ValueError("step: thermal rows come from the model, which takes no tc")
         pk = () if pack is None else (pack,) if isinstance(pack, str) else tuple(pack)
         for k in pk:
-            if k not in ("ucmd", "limiter", "bleed", "zmin"):
-                raise KeyError(f"step: unknown pack row {k!r} (one of ('ucmd', 'limiter', 'bleed', 'zmin'))")
+            if k not in ("ucmd", "limiter", "bleed", "zmin", "vstr", "istr", "capby"):
+                raise KeyError(f"step: unknown pack row {k!r} (one of ('ucmd', 'limiter', 'bleed', 'zmin', 'vstr', "
+                               "'istr', 'capby'))")
         bal = "bleed" in pk or "zmin" in pk
-        if bal and ("cond" in th or aging is not None):
+        chg = "vstr" in pk or "istr" in pk or "capby" in pk
+        if bal and not chg and ("cond" in th or aging is not None):
             raise ValueError("step: the balancer's rows (bleed, zmin) come from mpcekf_step_ex_balance, which has no "
                              "cond or rate row")
+        if chg and ("cond" in th or aging is not None):
+            raise ValueError("step: the charger's rows (vstr, istr, capby) come from mpcekf_step_ex_charger, which has "
+                             "no cond or rate row")
         ag = () if aging is None else (aging,) if isinstance(aging, str) else tuple(aging)
         for k in ag:
             if k != "rate":
@@ -339,7 +348,27 @@ class Context:
         tcp = tcs.ctypes.data_as(C.c_void_p) if tcs is not None else None
         rec = None if fields is None else np.empty((nsteps, slots.size, n))
         vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
-        if bal:   # a pack context with a balancer
+        if chg:   # a pack context with a charger (and a balancer, for bleed / zmin)
+            for k in th:
+                out[k] = np.empty((nsteps, n))
+            series = getattr(self, "_pack_series", 0)   # 0: no begin, the library refuses the call
+            nstr = n // series if series else n
+            for k in ("ucmd", "bleed"):
+                if k in pk:
+                    out[k] = np.empty((nsteps, n))
+            for k in ("zmin", "vstr", "istr"):
+                if k in pk:
+                    out[k] = np.empty((nsteps, nstr))
+            for k in ("limiter", "capby"):
+                if k in pk:
+                    out[k] = np.empty((nsteps, nstr), dtype=np.int32)
+            ns = 0 if fields is None else int(slots.size)
+            check(self.L.mpcekf_step_ex_charger(self.h, int(nsteps), tcp, C.byref(tr), iptr(slots) if ns else None, ns,
+                                                vp(rec) if ns else None, vp(out.get("temp")), vp(out.get("heat")),
+                                                vp(out.get("ucmd")), vp(out.get("limiter")), vp(out.get("bleed")),
+                                                vp(out.get("zmin")), vp(out.get("vstr")), vp(out.get("istr")),
+                                                vp(out.get("capby")), 0))
+        elif bal:   # a pack context with a balancer
             for k in th:
                 out[k] = np.empty((nsteps, n))
             series = getattr(self, "_pack_series", 0)   # 0: no begin, the library refuses the call
@@ -801,6 +830,61 @@ class Context:
     def balance_end(self):
         """Drop the balancer (mpcekf_balance_end): the pack couples its strings as before."""
         check(self.L.mpcekf_balance_end(self.h))
+
+    # -- charger limits: string voltage, current and power caps ---------------
+    CHARGER_PARAMS = _lib.CHARGER_PARAMS
+    CHARGER_FIELDS = _lib.CHARGER_FIELDS
+
+    @staticmethod
+    def _charger_args(nstr, i_max=None, p_max=None):
+        """charger_begin's arguments -> float64 [2, nstrings] parameters (None: NaN, the cap is
+        off).  ValueError for a bad shape, a negative i_max or p_max <= 0: before any library
+        call."""
+        rows = []
+        for name, a in (("i_max", i_max), ("p_max", p_max)):
+            a = np.nan if a is None else a
+            a = np.asarray(a, dtype=np.float64)
+            if a.ndim > 1 or (a.ndim == 1 and a.shape[0] != nstr):
+                raise ValueError(f"charger_begin: {name}: a scalar or [nstrings = {nstr}], not {a.shape}")
+            rows.append(np.broadcast_to(a, (nstr,)))
+        im, pm = rows
+        if not np.all(np.isnan(im) | (im >= 0)):
+            raise ValueError("charger_begin: i_max: a current >= 0 (A), or NaN / None for no current cap")
+        if not np.all(np.isnan(pm) | (pm > 0)):
+            raise ValueError("charger_begin: p_max: a power > 0 (W), or NaN / None for no power cap")
+        return np.ascontiguousarray(np.stack([im, pm]), dtype=np.float64)
+
+    def charger_begin(self, i_max=None, p_max=None):
+        """Give the pack context a charger (mpcekf_charger_begin), each parameter a scalar or
+        [nstrings]: ``i_max`` (A, >= 0) and ``p_max`` (W, > 0) bound every string's charging
+        current and power; None or NaN: that cap is off, np.inf never binds.  From then on every
+        fused step adds up each string's voltage and raises the string's (negative) current to
+        -i_max and -p_max / V where those are larger.  A second call resets the record."""
+        series = getattr(self, "_pack_series", 0)
+        par = self._charger_args(self.n // series if series else self.n, i_max, p_max)   # ValueError before any library call
+        check(self.L.mpcekf_charger_begin(self.h, dptr(par)))
+
+    def charger_get(self, fields=None):
+        """{name: [nstrings] float64} of the charger record (mpcekf_charger_get): ``fields`` names
+        of CHARGER_FIELDS (default all): steps, the steps with a string current; ncap_i / ncap_p,
+        the steps the current / power cap set it; q, the sum of the string current (A steps); e, the
+        sum of voltage times current (W steps); curtail, the sum of capped minus uncapped current;
+        p_min, the smallest (most charging) power; v_peak, the largest string voltage; nvalid_min,
+        the smallest number of cells that contributed to a string voltage."""
+        names = self.CHARGER_FIELDS if fields is None else (fields,) if isinstance(fields, str) else tuple(fields)
+        for k in names:
+            if k not in self.CHARGER_FIELDS:
+                raise KeyError(f"charger_get: unknown field {k!r} (one of {self.CHARGER_FIELDS})")
+        ids = np.asarray([self.CHARGER_FIELDS.index(k) for k in names], dtype=np.int32)
+        series = getattr(self, "_pack_series", 0)
+        vals = np.empty((ids.size, self.n // series if series else self.n))
+        check(self.L.mpcekf_charger_get(self.h, int(ids.size), iptr(ids), dptr(vals)))
+        return {k: vals[i] for i, k in enumerate(names)}
+
+    def charger_end(self):
+        """Drop the charger (mpcekf_charger_end): the pack's strings are bounded by their cells
+        alone, as before."""
+        check(self.L.mpcekf_charger_end(self.h))
 
     # -- charge termination: latch, rest, stop when done --------------------
     TERM_PARAMS = _lib.TERM_PARAMS
@@ -1308,6 +1392,24 @@ def _couple_links(n, thermal, pack, who):
     return Context._couple_links(n, thermal["couple"])
 
 
+def _charger_args(n, pack, who):
+    """pack["charger"] checked before a context exists: (the pack dict without it, charger_begin's
+    parameters [2, nstrings] or None).  KeyError for an unknown key, ValueError for a bad value."""
+    if not pack or "charger" not in pack:
+        return pack, None
+    pack = dict(pack)
+    c = pack.pop("charger")
+    if not c:
+        return pack, None
+    for k in c:
+        if k not in ("i_max", "p_max"):
+            raise KeyError(f"{who}: unknown pack['charger'] key {k!r} (one of ('i_max', 'p_max'))")
+    series = int(pack.get("series", 0))
+    if series < 1 or n % series:
+        raise ValueError(f"{who}: pack['charger'] needs a series that divides ncells = {n}, not {pack.get('series')!r}")
+    return pack, Context._charger_args(n // series, **c)
+
+
 def _pack_args(n, pack, who):
     """runMPC's / run_summary's pack dict checked before a context exists: (pack_begin's keywords,
     balance_begin's (parameters [3, n], compensate) or None).  KeyError for an unknown balance
@@ -1363,6 +1465,9 @@ def runMPC(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=None,
     pack["balance"]: a dict of Context.balance_begin's keywords (i_bleed, dz_on, dz_off,
     compensate): a passive balancer; adds out["bleed"], out["zmin"] (not with aging or
     thermal["couple"], whose calls have no such rows) and out["balance"], the balancer's record.
+    pack["charger"]: a dict of Context.charger_begin's keywords (i_max, p_max): a charger's current
+    and power rating per string; adds out["vstr"], out["istr"], out["capby"] (not with aging or
+    thermal["couple"] either) and out["charger"], the charger's record.
     aging: a dict of Context.aging_begin's keywords (reactions, sources): adds out["rate"], every
     step's side-reaction currents, and out["aging"], the record (Context.aging_record).
     thermal["couple"] with a pack: Context.thermal_couple's R_link, heat conduction between
@@ -1372,6 +1477,7 @@ def runMPC(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=None,
     SOC0 = np.atleast_1d(np.asarray(SOC0, dtype=np.float64))
     n = ncells or SOC0.shape[0]
     links = _couple_links(n, thermal, pack, "runMPC")
+    pack, chg = _charger_args(n, pack, "runMPC")
     pack, bal = _pack_args(n, pack, "runMPC")
     term = _stop_args(n, stop, "runMPC")
     with Context(rom, n, cfg, device) as ctx:
@@ -1384,6 +1490,8 @@ def runMPC(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=None,
             ctx.pack_begin(**pack)
         if bal:
             check(ctx.L.mpcekf_balance_begin(ctx.h, dptr(bal[0]), bal[1]))
+        if chg is not None:
+            check(ctx.L.mpcekf_charger_begin(ctx.h, dptr(chg)))
         if links is not None:
             ctx.thermal_couple(links)
         if aging:
@@ -1392,6 +1500,8 @@ def runMPC(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=None,
             check(ctx.L.mpcekf_term_begin(ctx.h, dptr(term[0]), term[1]))
         th_rows = ("temp", "heat", "cond") if links is not None else ("temp", "heat")
         pk_rows = ("ucmd", "limiter", "bleed", "zmin") if bal and not aging and links is None else ("ucmd", "limiter")
+        if chg is not None and not aging and links is None:
+            pk_rows += ("vstr", "istr", "capby")
         out = ctx.step(nsteps, tc=tc_traj, obs=obs, thermal=th_rows if thermal else None,
                        pack=pk_rows if pack else None, aging=("rate",) if aging else None)
         if aging:
@@ -1402,6 +1512,8 @@ def runMPC(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=None,
             out["pack"] = ctx.pack_get()
         if bal:
             out["balance"] = ctx.balance_get()
+        if chg is not None:
+            out["charger"] = ctx.charger_get()
         if links is not None:
             out["couple"] = ctx.thermal_couple_get()
         if thermal:
@@ -1421,7 +1533,8 @@ def run_summary(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=
     a chunk bounds the host array each call converts).  Neither host nor device memory grows
     with nsteps.  thermal: as runMPC's, its "schedule" included (no tc_traj); adds "thermal", the
     model's record.  pack: as runMPC's; adds "pack", the pack's record, beside the summary (whose
-    currents are the applied ones), and with pack["balance"] "balance", the balancer's record.
+    currents are the applied ones), with pack["balance"] "balance", the balancer's record, and with
+    pack["charger"] "charger", the charger's record.
     aging: as runMPC's; adds "aging", the side reactions' record.
     thermal["couple"] with a pack: as runMPC's; adds "couple", the coupling's record.
     stop: a dict of Context.term_begin's keywords plus chunk (default 64): the loop runs through
@@ -1435,6 +1548,7 @@ def run_summary(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=
         raise ValueError(f"run_summary: chunk = {chunk}")
     tcs = None if tc_traj is None else tc_grid(tc_traj, nsteps, n)
     links = _couple_links(n, thermal, pack, "run_summary")
+    pack, chg = _charger_args(n, pack, "run_summary")
     pack, bal = _pack_args(n, pack, "run_summary")
     term = _stop_args(n, stop, "run_summary", chunk=True)
     if term and tc_traj is not None:
@@ -1449,6 +1563,8 @@ def run_summary(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=
             ctx.pack_begin(**pack)
         if bal:
             check(ctx.L.mpcekf_balance_begin(ctx.h, dptr(bal[0]), bal[1]))
+        if chg is not None:
+            check(ctx.L.mpcekf_charger_begin(ctx.h, dptr(chg)))
         if links is not None:
             ctx.thermal_couple(links)
         if aging:
@@ -1471,6 +1587,8 @@ def run_summary(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=
             out["pack"] = ctx.pack_get()
         if bal:
             out["balance"] = ctx.balance_get()
+        if chg is not None:
+            out["charger"] = ctx.charger_get()
         if links is not None:
             out["couple"] = ctx.thermal_couple_get()
         if thermal:
