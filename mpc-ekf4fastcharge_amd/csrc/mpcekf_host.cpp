@@ -20,6 +20,7 @@
 #include <new>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/mpcekf.h"
@@ -184,6 +185,52 @@ int copy_threads() {
   if (sched_getaffinity(0, sizeof set, &set) == 0) n = CPU_COUNT(&set);
   return std::max(1, std::min(16, n));
 }
+
+// The output fields of a fused call, in the order of step_impl's f[]: the order of the staging
+// blocks in d_tmp and of the device-to-host copies.
+enum {
+  F_U, F_V, F_SOC, F_PHISE, F_NEXEC, F_X, F_ZK, F_ZBK, F_JUNC, F_JFIN, F_NORMDU, F_NVIOL, F_POLES, F_SV, F_OBS,
+  F_TEMP, F_HEAT,                          // k_thermal's rows
+  F_UCMD, F_LIMITER,                       // k_pack's
+  F_RATE,                                  // k_aging's
+  F_COND,                                  // k_thermal_couple's
+  F_BLEED, F_ZMIN,                         // k_pack_bal's
+  F_VSTR, F_ISTR, F_CAPBY,                 // k_charger's
+  NF
+};
+
+// What the launches of a captured fused call depend on (mpcekf_set_graph): kernel arguments are
+// call-relative (lazy_t = 1..nsteps, the flush schedule, the output rows), so a call whose key
+// equals a cached one replays that graph.  `call` is the call's shape; every other part belongs
+// to one context extension and is all 0 for a call that runs without it, so the extension's
+// _end retires the graphs that name its buffers by asking for its part (retire_graphs).  Every
+// member is one word, so the parts compare as bytes.
+struct GraphParts {
+  using W = uintptr_t;
+  struct {
+    W nsteps, dtc, diag, bounds;
+    W rows[NF];   // the device rows of the output fields
+    W obs_plan;   // a regrown plan buffer: the graphs that named the old one are not replayed
+    W nslots;
+    W lim;        // set / clear change the launch sequence: graphs of the other one are not replayed
+    W hot, hotp;  // the corner window and the plant window the captured kernels name (null: none)
+  } call;
+  struct { W rec, series; } pack;
+  struct { W rec, shape, phi, obs; } aging;    // shape: nreact and sources, which a second begin may change
+  struct { W rec, link, snap; } couple;
+  struct { W rec, hold, soc; } term;
+  struct { W rec, par, on, comp, soc; } balance;
+  struct { W rec, par; } charger;
+  struct { W hdr, tab; } sched;                // mpcekf_thermal_schedule may regrow the tables
+  struct { W ocv, nocv, rec; } thermal;
+  struct { W reach, rec; } summary;
+};
+static_assert(std::has_unique_object_representations_v<GraphParts>, "GraphKey compares the parts as bytes");
+struct GraphKey {
+  GraphParts p{};
+  std::vector<int32_t> slots;  // the call's obs slots
+  bool operator==(const GraphKey &o) const { return !std::memcmp(&p, &o.p, sizeof p) && slots == o.slots; }
+};
 
 }  // namespace
 
@@ -395,12 +442,22 @@ struct mpcekf_ctx {
   // mpcekf_set_graph: fused calls captured into hipGraphs, keyed by the call shape
   bool graph = false;
   struct GraphEntry {
-    std::vector<uintptr_t> key;
+    GraphKey key;
     hipGraphExec_t exec;
   };
   std::vector<GraphEntry> graphs;
+  // the graphs whose key's parts `pred` selects are destroyed: they name buffers about to be
+  // freed or replaced.  The caller has waited for the stream.
+  template <class Pred>
+  void retire_graphs(Pred &&pred) {
+    for (size_t i = graphs.size(); i-- > 0;)
+      if (pred(graphs[i].key.p)) {
+        (void)hipGraphExecDestroy(graphs[i].exec);
+        graphs.erase(graphs.begin() + (std::ptrdiff_t)i);
+      }
+  }
   template <class Fn>
-  int graph_launch(const std::vector<uintptr_t> &key, Fn &&launch) {
+  int graph_launch(const GraphKey &key, Fn &&launch) {
     for (const GraphEntry &g : graphs)
       if (g.key == key) {
         HIPCHK(hipGraphLaunch(g.exec, stream));
@@ -1347,6 +1404,16 @@ static int lerr(int rc, const char *what) {
   return MPCEKF_OK;
 }
 
+// What a fused call returns beyond mpcekf_traj and the obs rows: every entry point fills the
+// members it has, by name.
+struct StepOut {
+  bool sum = false;  // mpcekf_step_summary's call: the rows go to the context's window
+  double *temp = nullptr, *heat = nullptr, *ucmd = nullptr;
+  int32_t *limiter = nullptr;
+  double *rate = nullptr, *cond = nullptr, *bleed = nullptr, *zmin = nullptr, *vstr = nullptr, *istr = nullptr;
+  int32_t *capby = nullptr;
+};
+
 // runMPC.m:84-111, nsteps times: OB_step -> (all-model advance + EKF time
 // update) -> iterEKF measurement update -> EKFmatsHandler -> iterMPC.
 // nslots > 0 (mpcekf_step_ex_obs): k_obs_traj first in every step, its rows one more output
@@ -1387,9 +1454,8 @@ static int lerr(int rc, const char *what) {
 // output field, written by that kernel.
 static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const mpcekf_traj *tr,
                      const int32_t *slots, int32_t nslots, double *obs, int32_t outputs_on_device,
-                     bool sum = false, double *temp = nullptr, double *heat = nullptr, double *ucmd = nullptr,
-                     int32_t *limiter = nullptr, double *rate = nullptr, double *cond = nullptr, double *bleed = nullptr,
-                     double *zmin = nullptr, double *vstr = nullptr, double *istr = nullptr, int32_t *capby = nullptr) {
+                     const StepOut &o = StepOut()) {
+  const bool sum = o.sum;
   // a thermal context owns the temperature: refused before anything of the context changes
   if (X && X->d_th && tc_degC)
     return fail(MPCEKF_E_ARG, "step: tc_degC on a thermal context (mpcekf_thermal_begin): the model sets the temperature");
@@ -1431,8 +1497,9 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
   // a constraint block off, or per-cell limits at Np = 5: the split route of mpcekf_switch.hip
   const bool switched = X->sw != 7 || (lim && !X->wide);
   const size_t n = (size_t)X->n, per = n * (size_t)nsteps, nzz = (size_t)X->nz + 2;
-  // the output fields, their element size and elements per cell-step (rows: elements of
+  // the output fields (F_*), their element size and elements per cell-step (rows: elements of
   // `width` per step where that is not ncells)
+  const size_t nstr = pack ? n / (size_t)X->pk_series : 0;  // a string field has one element per string and step
   struct F {
     void *host;
     size_t esz, width;
@@ -1444,28 +1511,28 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
            {tr->J_fin, 8, 1, nullptr},   {tr->norm_du, 8, 1, nullptr}, {tr->nviol, 4, 1, nullptr},
            {tr->poles, 8, 2 * NA, nullptr}, {tr->sv, 8, NA, nullptr},
            {nslots ? obs : nullptr, 8, (size_t)nslots, nullptr},  // [nsteps][nslots][ncells]
-           {temp, 8, 1, nullptr},        {heat, 8, 1, nullptr},   // k_thermal's rows (a thermal context's only)
-           {ucmd, 8, 1, nullptr},                                 // k_pack's rows (a pack context's only)
-           {limiter, 4, 1, nullptr, pack ? n / (size_t)X->pk_series : 0},  // [nsteps][nstrings]
-           // k_aging's rows (an aging context's only): [nsteps][nsrc * nreact][ncells]
-           {rate, 8, aging ? (size_t)(((int)ag_est + (int)ag_plant) * X->ag_nreact) : 0, nullptr},
-           {cond, 8, 1, nullptr},  // k_thermal_couple's row (a coupled context's only)
-           {bleed, 8, 1, nullptr},  // k_pack_bal's rows (a balancing context's only)
-           {zmin, 8, 1, nullptr, pack ? n / (size_t)X->pk_series : 0},  // [nsteps][nstrings]
-           // k_charger's rows (a charger context's only): [nsteps][nstrings] each
-           {vstr, 8, 1, nullptr, pack ? n / (size_t)X->pk_series : 0},
-           {istr, 8, 1, nullptr, pack ? n / (size_t)X->pk_series : 0},
-           {capby, 4, 1, nullptr, pack ? n / (size_t)X->pk_series : 0}};
-  constexpr int NF = sizeof(f) / sizeof(f[0]);
+           {o.temp, 8, 1, nullptr},      {o.heat, 8, 1, nullptr},  // a thermal context's only
+           {o.ucmd, 8, 1, nullptr},                                // a pack context's only
+           {o.limiter, 4, 1, nullptr, nstr},
+           // an aging context's only: [nsteps][nsrc * nreact][ncells]
+           {o.rate, 8, aging ? (size_t)(((int)ag_est + (int)ag_plant) * X->ag_nreact) : 0, nullptr},
+           {o.cond, 8, 1, nullptr},   // a coupled context's only
+           {o.bleed, 8, 1, nullptr},  // a balancing context's only
+           {o.zmin, 8, 1, nullptr, nstr},
+           // a charger context's only
+           {o.vstr, 8, 1, nullptr, nstr},
+           {o.istr, 8, 1, nullptr, nstr},
+           {o.capby, 4, 1, nullptr, nstr}};
+  static_assert(sizeof(f) / sizeof(F) == NF, "f[] has one entry per F_* name, in that order");
   auto step_bytes = [&](const F &e) -> size_t { return (e.rows ? e.rows : n) * e.width * e.esz; };  // one step's block
   const double *dtc = tc_degC;  // [nsteps][n] device copy of the per-step temperatures
   // sum: rows of the window instead of rows of a trajectory, for outputs and temperatures alike
   const size_t ring = sum ? (size_t)SUM_WIN : 0;
   const bool tc_windows = sum && tc_degC && (size_t)nsteps > ring;  // uploaded window by window
   if (sum) {
-    f[14].host = nullptr;  // the obs rows stay on the device
-    for (int i = 0; i < 5; ++i) f[i].dev = X->d_sum_ring + (size_t)i * X->sum_row();
-    f[14].dev = nslots ? (char *)obs : nullptr;
+    f[F_OBS].host = nullptr;  // the obs rows stay on the device
+    for (int i = F_U; i <= F_NEXEC; ++i) f[i].dev = X->d_sum_ring + (size_t)(i - F_U) * X->sum_row();  // u .. nexec
+    f[F_OBS].dev = nslots ? (char *)obs : nullptr;
     if (tc_degC) {
       const size_t rows = std::min((size_t)nsteps, ring);
       if ((rc = X->tmp(rows * n * 8 + 256))) return rc;
@@ -1494,7 +1561,7 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
   };
   // iterMPC.m:53-60 diagnostics: k_cl_diag after the step from its linearisation records
   // and the uk_1 the step's iterMPC used
-  const bool diag = f[12].dev || f[13].dev;
+  const bool diag = f[F_POLES].dev || f[F_SV].dev;
   if (diag && (rc = X->diag_bufs())) return rc;
   // the obs selection: each position's source and the shared values some position reads,
   // uploaded on the step's stream before the loop (and before a graph replay)
@@ -1589,7 +1656,7 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
       if (thermal && k == 0) HIPCHK(hipMemcpyAsync(X->d_th_i, X->s.uk, n * 8, hipMemcpyDeviceToDevice, X->stream));
       if (nslots) {  // the plant's observables of step t, before anything advances the plant
         KObsSel ok = osel;
-        ok.out = (double *)row(14, k);
+        ok.out = (double *)row(F_OBS, k);
         if ((rc = lerr(launch_obs_traj(X->r, X->s, X->ko, ok, t, tc_row(k), X->stream), "obs_traj"))) return rc;
       }
       if (ag_plant && ag_pos < 0) {  // the plant's negPhise0 of step t for k_aging, into the context's row
@@ -1609,23 +1676,23 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
       io.plant = plant_in_cell;
       io.tc_in = plant_in_cell ? tc_row(k) : nullptr;
       io.stamps = X->d_stamps;
-      io.u = (double *)row(0, k);
-      io.v = (double *)row(1, k);
-      io.soc = (double *)row(2, k);
-      io.phise = (double *)row(3, k);
+      io.u = (double *)row(F_U, k);
+      io.v = (double *)row(F_V, k);
+      io.soc = (double *)row(F_SOC, k);
+      io.phise = (double *)row(F_PHISE, k);
       if (ag_est && !io.phise) io.phise = X->d_ag_phi;  // k_aging's input when the call asks for no phise row
       if (term && !io.soc) io.soc = X->d_tm_soc;         // k_term's input when the call asks for no soc row
       if (balance && !io.soc) io.soc = X->d_bl_soc;      // k_pack_bal's likewise
-      io.nexec = (int *)row(4, k);
-      io.x_out = (double *)row(5, k);
-      io.zk = f[6].dev ? (double *)row(6, k) : X->d_zk;
-      double *zbk_k = f[7].dev ? (double *)row(7, k) : X->d_zbk;
+      io.nexec = (int *)row(F_NEXEC, k);
+      io.x_out = (double *)row(F_X, k);
+      io.zk = f[F_ZK].dev ? (double *)row(F_ZK, k) : X->d_zk;
+      double *zbk_k = f[F_ZBK].dev ? (double *)row(F_ZBK, k) : X->d_zbk;
       io.zbk = bounds ? zbk_k : nullptr;
       io.bnd = bnd_kernel ? X->d_bnd : nullptr;
-      io.junc_out = (double *)row(8, k);
-      io.jfin_out = (double *)row(9, k);
-      io.normdu_out = (double *)row(10, k);
-      io.nviol_out = (int *)row(11, k);
+      io.junc_out = (double *)row(F_JUNC, k);
+      io.jfin_out = (double *)row(F_JFIN, k);
+      io.normdu_out = (double *)row(F_NORMDU, k);
+      io.nviol_out = (int *)row(F_NVIOL, k);
       if (diag) io.lin_out = X->d_lin;
       // wide horizons, or a constraint switch off: iterMPC in mpcekf_wide.hip / mpcekf_switch.hip
       // from the linearisation record
@@ -1711,7 +1778,7 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
         return rc;
       }
       if (diag) {
-        double *pk = (double *)row(12, k), *sk = (double *)row(13, k);
+        double *pk = (double *)row(F_POLES, k), *sk = (double *)row(F_SV, k);
         rc = X->wide ? launch_cl_diag_wide(X->k, X->n, X->d_lin, X->d_uk1p, pk, sk, X->stream, lim)
                      : launch_cl_diag(X->k, X->n, X->d_lin, X->d_uk1p, pk, sk, X->stream, lim);
         if ((rc = lerr(rc, "cl_diag"))) return rc;
@@ -1721,7 +1788,7 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
         KTerm q{};
         q.uk = X->s.uk;
         q.uk_1 = X->s.uk_1;
-        q.u = (double *)row(0, k);
+        q.u = (double *)row(F_U, k);
         q.soc = io.soc;
         q.Tc = X->s.Tc;
         q.par = X->d_tm_par;
@@ -1739,9 +1806,9 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
         KPack q{};
         q.uk = X->s.uk;
         q.uk_1 = X->s.uk_1;
-        q.u = (double *)row(0, k);
-        q.ucmd = (double *)row(17, k);
-        q.limiter = (int *)row(18, k);
+        q.u = (double *)row(F_U, k);
+        q.ucmd = (double *)row(F_UCMD, k);
+        q.limiter = (int *)row(F_LIMITER, k);
         q.rec = X->d_pk;
         q.n = X->n;
         q.series = X->pk_series;
@@ -1752,8 +1819,8 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
           b.par = X->d_bl_par;
           b.on = X->d_bl_on;
           b.rec = X->d_bl;
-          b.bleed = (double *)row(21, k);
-          b.zmin = (double *)row(22, k);
+          b.bleed = (double *)row(F_BLEED, k);
+          b.zmin = (double *)row(F_ZMIN, k);
           b.compensate = X->bl_comp;
         }
         if (charger) {  // the strings' voltages and caps, the bleeders' switching and the currents in one launch
@@ -1762,9 +1829,9 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
           h.vk = X->s.vk;
           h.par = X->d_ch_par;
           h.rec = X->d_ch;
-          h.vstr = (double *)row(23, k);
-          h.istr = (double *)row(24, k);
-          h.capby = (int *)row(25, k);
+          h.vstr = (double *)row(F_VSTR, k);
+          h.istr = (double *)row(F_ISTR, k);
+          h.capby = (int *)row(F_CAPBY, k);
           if ((rc = lerr(launch_charger(h, X->stream), "charger"))) return rc;
         } else if (balance) {  // the bleeders' switching and the strings' currents in one launch
           if ((rc = lerr(launch_pack_bal(b, X->stream), "pack_bal"))) return rc;
@@ -1786,12 +1853,12 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
         KSum q{};
         q.rec = X->d_sum;
         q.reach = X->d_sum_reach;
-        q.u = (const double *)f[0].dev;
-        q.v = (const double *)f[1].dev;
-        q.soc = (const double *)f[2].dev;
-        q.phise = (const double *)f[3].dev;
-        q.nexec = (const int *)f[4].dev;
-        q.obs = (const double *)f[14].dev;
+        q.u = (const double *)f[F_U].dev;
+        q.v = (const double *)f[F_V].dev;
+        q.soc = (const double *)f[F_SOC].dev;
+        q.phise = (const double *)f[F_PHISE].dev;
+        q.nexec = (const int *)f[F_NEXEC].dev;
+        q.obs = (const double *)f[F_OBS].dev;
         q.n = X->n;
         q.nrows = (int)((size_t)k % ring) + 1;
         q.max_hild = X->cfg.max_hild;
@@ -1801,10 +1868,10 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
         KAging q{};
         q.Tc = X->s.Tc;
         q.phi[AG_SRC_EST] = ag_est ? io.phise : nullptr;
-        q.phi[AG_SRC_PLANT] = !ag_plant ? nullptr : ag_pos < 0 ? X->d_ag_obs : (const double *)row(14, k) + (size_t)ag_pos * n;
+        q.phi[AG_SRC_PLANT] = !ag_plant ? nullptr : ag_pos < 0 ? X->d_ag_obs : (const double *)row(F_OBS, k) + (size_t)ag_pos * n;
         q.par = X->d_ag_par;
         q.rec = X->d_ag;
-        q.rate = (double *)row(19, k);
+        q.rate = (double *)row(F_RATE, k);
         q.n = X->n;
         q.nreact = X->ag_nreact;
         q.F = X->r.F;
@@ -1823,8 +1890,8 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
         q.par = X->d_th_par;
         q.ocv = X->d_th_ocv;
         q.rec = X->d_th;
-        q.temp = (double *)row(15, k);
-        q.heat = (double *)row(16, k);
+        q.temp = (double *)row(F_TEMP, k);
+        q.heat = (double *)row(F_HEAT, k);
         q.n = X->n;
         q.nocv = X->th_nocv;
         q.th0n = X->r.th0n;
@@ -1838,7 +1905,7 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
           h.rec = X->d_tc;
           h.snap_in = X->d_tc_snap + (size_t)(k & 1) * n;
           h.snap_out = X->d_tc_snap + (size_t)((k + 1) & 1) * n;
-          h.cond = (double *)row(20, k);
+          h.cond = (double *)row(F_COND, k);
           h.series = X->pk_series;
           rc = sched && k + 1 < nsteps ? lerr(launch_thermal_couple_sched(q, h, ksch, X->stream), "thermal_couple_sched")
                                        : lerr(launch_thermal_couple(q, h, X->stream), "thermal_couple");
@@ -1853,56 +1920,33 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
     return MPCEKF_OK;
   };
   if (capturing) {
-    // the call's launches depend only on these (kernel arguments are call-relative:
-    // lazy_t = 1..nsteps, the flush schedule, the output rows), so a repeated call shape
-    // replays one instantiated graph instead of 5-7 launches per step
-    // the pack state fifth and sixth (its ucmd / limiter rows are among the output rows below):
-    // 0 on a context without a pack -- mpcekf_pack_end retires the graphs that name one
-    std::vector<uintptr_t> key = {(uintptr_t)nsteps, (uintptr_t)dtc, (uintptr_t)diag, (uintptr_t)bounds,
-                                  (uintptr_t)X->d_pk, (uintptr_t)X->pk_series,
-                                  // the aging state seventh to tenth (its rate rows are among the output
-                                  // rows below): 0 on a context without one -- mpcekf_aging_end, and a
-                                  // begin that changes nreact or sources, retire the graphs that name one
-                                  (uintptr_t)X->d_ag, (uintptr_t)(X->ag_nreact | X->ag_sources << 8),
-                                  (uintptr_t)(aging ? X->d_ag_phi : nullptr), (uintptr_t)(aging ? X->d_ag_obs : nullptr),
-                                  // the coupling's buffers eleventh to thirteenth (its cond rows are among
-                                  // the output rows below): 0 on a context without links --
-                                  // mpcekf_thermal_couple_end retires the graphs that name them
-                                  (uintptr_t)X->d_tc, (uintptr_t)X->d_tc_link, (uintptr_t)X->d_tc_snap,
-                                  // the termination state fourteenth to sixteenth: 0 on a context without
-                                  // one -- mpcekf_term_end retires the graphs that name it
-                                  (uintptr_t)X->d_tm, (uintptr_t)X->tm_hold, (uintptr_t)(term ? X->d_tm_soc : nullptr),
-                                  // the balancer seventeenth to twenty-first (its bleed / zmin rows are among
-                                  // the output rows below): 0 on a context without one -- mpcekf_balance_end
-                                  // retires the graphs that name it
-                                  (uintptr_t)(balance ? X->d_bl : nullptr), (uintptr_t)(balance ? X->d_bl_par : nullptr),
-                                  (uintptr_t)(balance ? X->d_bl_on : nullptr), (uintptr_t)(balance ? X->bl_comp : 0),
-                                  (uintptr_t)(balance ? X->d_bl_soc : nullptr),
-                                  // the charger twenty-second and twenty-third (its vstr / istr / capby rows
-                                  // are among the output rows below): 0 on a context without one --
-                                  // mpcekf_charger_end retires the graphs that name it
-                                  (uintptr_t)(charger ? X->d_ch : nullptr), (uintptr_t)(charger ? X->d_ch_par : nullptr)};
-    for (const F &e : f) key.push_back((uintptr_t)e.dev);
-    key.push_back((uintptr_t)osel.plan);  // a regrown plan buffer retires the graphs that named the old one
-    key.push_back((uintptr_t)nslots);
-    key.push_back((uintptr_t)lim);  // set / clear change the launch sequence: graphs of the other one are not replayed
-    key.push_back((uintptr_t)X->s.hot_rec);  // the corner window the captured kernels name (null: none)
-    key.push_back((uintptr_t)X->s.hotp_x);   // and the plant window
-    for (int i = 0; i < nslots; ++i) key.push_back((uintptr_t)slots[i]);
-    // the schedule's launches are part of the graph: its header (0 without a schedule) and its
-    // tables, which mpcekf_thermal_schedule may regrow
-    key.push_back((uintptr_t)(sched ? X->d_sch_hdr : nullptr));
-    key.push_back((uintptr_t)(sched ? X->d_sch_tab : nullptr));
-    // the thermal state (its temp / heat rows are among the output rows above): third from the
-    // end, 0 on a context without a model -- mpcekf_thermal_end retires the graphs that name one
-    key.push_back((uintptr_t)X->d_th_ocv);
-    key.push_back((uintptr_t)X->th_nocv);
-    key.push_back((uintptr_t)X->d_th);
-    // the summary state: its launches are part of the graph (the window's rows are already
-    // among the output rows above); the record last, 0 for a call that is no summary call --
-    // mpcekf_summary_end retires the graphs that name one
-    key.push_back((uintptr_t)(sum ? X->d_sum_reach : nullptr));
-    key.push_back((uintptr_t)(sum ? X->d_sum : nullptr));
+    // a repeated call shape replays one instantiated graph instead of 5-7 launches per step.
+    // An extension's rows (ucmd, rate, cond, ...) are among call.rows; its part holds the
+    // context's own buffers and switches that the launches name
+    using W = GraphParts::W;
+    GraphKey key;
+    GraphParts &p = key.p;
+    p.call.nsteps = (W)nsteps;
+    p.call.dtc = (W)dtc;
+    p.call.diag = (W)diag;
+    p.call.bounds = (W)bounds;
+    for (int i = 0; i < NF; ++i) p.call.rows[i] = (W)f[i].dev;
+    p.call.obs_plan = (W)osel.plan;
+    p.call.nslots = (W)nslots;
+    p.call.lim = (W)lim;
+    p.call.hot = (W)X->s.hot_rec;
+    p.call.hotp = (W)X->s.hotp_x;
+    key.slots.assign(slots, slots + nslots);
+    p.pack = {(W)X->d_pk, (W)X->pk_series};
+    p.aging = {(W)X->d_ag, (W)(X->ag_nreact | X->ag_sources << 8), (W)(aging ? X->d_ag_phi : nullptr),
+               (W)(aging ? X->d_ag_obs : nullptr)};
+    p.couple = {(W)X->d_tc, (W)X->d_tc_link, (W)X->d_tc_snap};
+    p.term = {(W)X->d_tm, (W)X->tm_hold, (W)(term ? X->d_tm_soc : nullptr)};
+    if (balance) p.balance = {(W)X->d_bl, (W)X->d_bl_par, (W)X->d_bl_on, (W)X->bl_comp, (W)X->d_bl_soc};
+    if (charger) p.charger = {(W)X->d_ch, (W)X->d_ch_par};
+    if (sched) p.sched = {(W)X->d_sch_hdr, (W)X->d_sch_tab};  // the schedule's launches are part of the graph
+    p.thermal = {(W)X->d_th_ocv, (W)X->th_nocv, (W)X->d_th};
+    if (sum) p.summary = {(W)X->d_sum_reach, (W)X->d_sum};  // the fold's launches are part of the graph
     if ((rc = X->graph_launch(key, run_steps))) return rc;
   } else if ((rc = run_steps())) {
     return rc;
@@ -1912,10 +1956,10 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
       if (f[i].host)
         HIPCHK(hipMemcpyAsync(f[i].host, f[i].dev, (size_t)nsteps * step_bytes(f[i]), hipMemcpyDeviceToHost, X->stream));
   // mpcekf_get_zk returns the last step's zk / boundzk whichever buffers the steps wrote
-  if (nsteps > 0 && f[6].dev)
-    HIPCHK(hipMemcpyAsync(X->d_zk, row(6, nsteps - 1), n * nzz * 8, hipMemcpyDeviceToDevice, X->stream));
-  if (nsteps > 0 && f[7].dev)
-    HIPCHK(hipMemcpyAsync(X->d_zbk, row(7, nsteps - 1), n * nzz * 8, hipMemcpyDeviceToDevice, X->stream));
+  if (nsteps > 0 && f[F_ZK].dev)
+    HIPCHK(hipMemcpyAsync(X->d_zk, row(F_ZK, nsteps - 1), n * nzz * 8, hipMemcpyDeviceToDevice, X->stream));
+  if (nsteps > 0 && f[F_ZBK].dev)
+    HIPCHK(hipMemcpyAsync(X->d_zbk, row(F_ZBK, nsteps - 1), n * nzz * 8, hipMemcpyDeviceToDevice, X->stream));
   HIPCHK(hipStreamSynchronize(X->stream));
   if (X->timing) {
     // (start, end) events of plant, cell, bounds, hild, flush
@@ -2100,6 +2144,39 @@ int mpcekf_clear_limits(mpcekf_ctx *X) {
   return MPCEKF_OK;
 }
 
+// ---- the record getters (mpcekf_get_summary and every extension's _get) ----
+// Their arguments, in the order every getter refuses them, before any HIP call: the context,
+// nfields in 1..nrows, fields, values, every id in 0..nrows-1 (the MPCEKF_<ids>_* of the header)
+// and given once.  who: the getter's short name.  The getter's own state check follows.
+static int check_rows(const mpcekf_ctx *X, const char *who, const char *ids, int nrows, int32_t nfields,
+                      const int32_t *fields, const double *values) {
+  if (!X) return fail(MPCEKF_E_ARG, "%s: null ctx", who);
+  if (nfields < 1 || nfields > nrows) return fail(MPCEKF_E_ARG, "%s: nfields = %d outside 1..%d", who, nfields, nrows);
+  if (!fields) return fail(MPCEKF_E_ARG, "%s: null fields", who);
+  if (!values) return fail(MPCEKF_E_ARG, "%s: null values", who);
+  unsigned seen = 0;
+  for (int i = 0; i < nfields; ++i) {
+    if (fields[i] < 0 || fields[i] >= nrows)
+      return fail(MPCEKF_E_ARG, "%s: fields[%d] = %d is not a MPCEKF_%s_* id (0..%d)", who, i, fields[i], ids, nrows - 1);
+    if (seen >> fields[i] & 1) return fail(MPCEKF_E_ARG, "%s: fields: id %d given twice", who, fields[i]);
+    seen |= 1u << fields[i];
+  }
+  return MPCEKF_OK;
+}
+
+// values [nfields][len] = rows fields[i] of the slot-major record at rec, each of len doubles; row
+// `alt_id`, if any, lives at `alt` instead.  Waits for the copies.
+static int get_rows(mpcekf_ctx *X, const double *rec, size_t len, int32_t nfields, const int32_t *fields, double *values,
+                    int alt_id = -1, const double *alt = nullptr) {
+  HIPCHK(hipSetDevice(X->device));
+  for (int i = 0; i < nfields && len; ++i) {
+    const double *src = fields[i] == alt_id ? alt : rec + (size_t)fields[i] * len;
+    HIPCHK(hipMemcpyAsync(values + (size_t)i * len, src, len * 8, hipMemcpyDeviceToHost, X->stream));
+  }
+  HIPCHK(hipStreamSynchronize(X->stream));
+  return MPCEKF_OK;
+}
+
 // ---- per-cell charge summary along the fused loop (mpcekf_summary.hip) ----
 static_assert(NSUM == MPCEKF_NSUM && SUM_WIN == MPCEKF_SUM_WIN && SUM_SEEN == MPCEKF_SUM_SEEN &&
                   SUM_T_REACH == MPCEKF_SUM_T_REACH && SUM_U_MAX == MPCEKF_SUM_U_MAX && SUM_V_MIN == MPCEKF_SUM_V_MIN &&
@@ -2137,31 +2214,16 @@ int mpcekf_summary_begin(mpcekf_ctx *X, const double *soc_reach, int32_t obs_slo
 int mpcekf_step_summary(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC) {
   if (!X) return fail(MPCEKF_E_ARG, "step_summary: null ctx");
   if (!X->d_sum) return fail(MPCEKF_E_STATE, "step_summary: call mpcekf_summary_begin first");
-  return step_impl(X, nsteps, tc_degC, nullptr, nullptr, 0, nullptr, 0, true);
+  StepOut o;
+  o.sum = true;
+  return step_impl(X, nsteps, tc_degC, nullptr, nullptr, 0, nullptr, 0, o);
 }
 
 int mpcekf_get_summary(mpcekf_ctx *X, int32_t nfields, const int32_t *fields, double *values) {
-  if (!X) return fail(MPCEKF_E_ARG, "get_summary: null ctx");
-  if (nfields < 1 || nfields > MPCEKF_NSUM)
-    return fail(MPCEKF_E_ARG, "get_summary: nfields = %d outside 1..%d", nfields, (int)MPCEKF_NSUM);
-  if (!fields) return fail(MPCEKF_E_ARG, "get_summary: null fields");
-  if (!values) return fail(MPCEKF_E_ARG, "get_summary: null values");
-  unsigned seen = 0;
-  for (int i = 0; i < nfields; ++i) {
-    if (fields[i] < 0 || fields[i] >= MPCEKF_NSUM)
-      return fail(MPCEKF_E_ARG, "get_summary: fields[%d] = %d is not a MPCEKF_SUM_* id (0..%d)", i, fields[i],
-                  (int)MPCEKF_NSUM - 1);
-    if (seen >> fields[i] & 1) return fail(MPCEKF_E_ARG, "get_summary: fields: id %d given twice", fields[i]);
-    seen |= 1u << fields[i];
-  }
+  int rc = check_rows(X, "get_summary", "SUM", MPCEKF_NSUM, nfields, fields, values);
+  if (rc) return rc;
   if (!X->d_sum) return fail(MPCEKF_E_STATE, "get_summary: call mpcekf_summary_begin first");
-  HIPCHK(hipSetDevice(X->device));
-  const size_t n = (size_t)X->n;
-  for (int i = 0; i < nfields && n; ++i)
-    HIPCHK(hipMemcpyAsync(values + (size_t)i * n, X->d_sum + (size_t)fields[i] * n, n * 8, hipMemcpyDeviceToHost,
-                          X->stream));
-  HIPCHK(hipStreamSynchronize(X->stream));
-  return MPCEKF_OK;
+  return get_rows(X, X->d_sum, (size_t)X->n, nfields, fields, values);
 }
 
 int mpcekf_summary_end(mpcekf_ctx *X) {
@@ -2170,11 +2232,7 @@ int mpcekf_summary_end(mpcekf_ctx *X) {
   HIPCHK(hipSetDevice(X->device));
   HIPCHK(hipStreamSynchronize(X->stream));
   // the graphs captured from summary calls name the buffers freed below
-  for (size_t i = X->graphs.size(); i-- > 0;)
-    if (X->graphs[i].key.back()) {
-      (void)hipGraphExecDestroy(X->graphs[i].exec);
-      X->graphs.erase(X->graphs.begin() + (std::ptrdiff_t)i);
-    }
+  X->retire_graphs([](const GraphParts &k) { return k.summary.rec != 0; });
   void *ptrs[] = {X->d_sum, X->d_sum_reach, X->d_sum_obs, X->d_sum_ring};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
@@ -2195,11 +2253,7 @@ static_assert(NTH == MPCEKF_NTH && TH_CTH == MPCEKF_TH_CTH && TH_RTH == MPCEKF_T
 // the graphs captured on a thermal context launch k_thermal on the model's buffers: retired
 // before any of those buffers is freed
 static void retire_thermal_graphs(mpcekf_ctx *X) {
-  for (size_t i = X->graphs.size(); i-- > 0;)
-    if (X->graphs[i].key[X->graphs[i].key.size() - 3]) {
-      (void)hipGraphExecDestroy(X->graphs[i].exec);
-      X->graphs.erase(X->graphs.begin() + (std::ptrdiff_t)i);
-    }
+  X->retire_graphs([](const GraphParts &k) { return k.thermal.rec != 0; });
 }
 
 int mpcekf_thermal_begin(mpcekf_ctx *X, const double *params, int32_t nocv, const double *ocv, const double *t0_degC) {
@@ -2259,28 +2313,10 @@ int mpcekf_thermal_begin(mpcekf_ctx *X, const double *params, int32_t nocv, cons
 }
 
 int mpcekf_thermal_get(mpcekf_ctx *X, int32_t nfields, const int32_t *fields, double *values) {
-  if (!X) return fail(MPCEKF_E_ARG, "thermal_get: null ctx");
-  if (nfields < 1 || nfields > MPCEKF_NTHR)
-    return fail(MPCEKF_E_ARG, "thermal_get: nfields = %d outside 1..%d", nfields, (int)MPCEKF_NTHR);
-  if (!fields) return fail(MPCEKF_E_ARG, "thermal_get: null fields");
-  if (!values) return fail(MPCEKF_E_ARG, "thermal_get: null values");
-  unsigned seen = 0;
-  for (int i = 0; i < nfields; ++i) {
-    if (fields[i] < 0 || fields[i] >= MPCEKF_NTHR)
-      return fail(MPCEKF_E_ARG, "thermal_get: fields[%d] = %d is not a MPCEKF_THR_* id (0..%d)", i, fields[i],
-                  (int)MPCEKF_NTHR - 1);
-    if (seen >> fields[i] & 1) return fail(MPCEKF_E_ARG, "thermal_get: fields: id %d given twice", fields[i]);
-    seen |= 1u << fields[i];
-  }
+  int rc = check_rows(X, "thermal_get", "THR", MPCEKF_NTHR, nfields, fields, values);
+  if (rc) return rc;
   if (!X->d_th) return fail(MPCEKF_E_STATE, "thermal_get: call mpcekf_thermal_begin first");
-  HIPCHK(hipSetDevice(X->device));
-  const size_t n = (size_t)X->n;
-  for (int i = 0; i < nfields && n; ++i) {
-    const double *src = fields[i] == MPCEKF_THR_T ? X->s.Tc : X->d_th + (size_t)fields[i] * n;
-    HIPCHK(hipMemcpyAsync(values + (size_t)i * n, src, n * 8, hipMemcpyDeviceToHost, X->stream));
-  }
-  HIPCHK(hipStreamSynchronize(X->stream));
-  return MPCEKF_OK;
+  return get_rows(X, X->d_th, (size_t)X->n, nfields, fields, values, MPCEKF_THR_T, X->s.Tc);  // the temperature is the state's
 }
 
 int mpcekf_thermal_end(mpcekf_ctx *X) {
@@ -2396,7 +2432,10 @@ int mpcekf_step_ex_thermal(mpcekf_ctx *X, int32_t nsteps, const mpcekf_traj *tr,
                            double *obs, double *temp, double *heat, int32_t outputs_on_device) {
   if (!X) return fail(MPCEKF_E_ARG, "step_ex_thermal: null ctx");
   if (!X->d_th) return fail(MPCEKF_E_STATE, "step_ex_thermal: call mpcekf_thermal_begin first");
-  return step_impl(X, nsteps, nullptr, tr, slots, nslots, obs, outputs_on_device, false, temp, heat);
+  StepOut o;
+  o.temp = temp;
+  o.heat = heat;
+  return step_impl(X, nsteps, nullptr, tr, slots, nslots, obs, outputs_on_device, o);
 }
 
 // ---- series strings along the fused loop (mpcekf_pack.hip) ----
@@ -2425,27 +2464,10 @@ int mpcekf_pack_begin(mpcekf_ctx *X, int32_t series) {
 }
 
 int mpcekf_pack_get(mpcekf_ctx *X, int32_t nfields, const int32_t *fields, double *values) {
-  if (!X) return fail(MPCEKF_E_ARG, "pack_get: null ctx");
-  if (nfields < 1 || nfields > MPCEKF_NPK)
-    return fail(MPCEKF_E_ARG, "pack_get: nfields = %d outside 1..%d", nfields, (int)MPCEKF_NPK);
-  if (!fields) return fail(MPCEKF_E_ARG, "pack_get: null fields");
-  if (!values) return fail(MPCEKF_E_ARG, "pack_get: null values");
-  unsigned seen = 0;
-  for (int i = 0; i < nfields; ++i) {
-    if (fields[i] < 0 || fields[i] >= MPCEKF_NPK)
-      return fail(MPCEKF_E_ARG, "pack_get: fields[%d] = %d is not a MPCEKF_PK_* id (0..%d)", i, fields[i],
-                  (int)MPCEKF_NPK - 1);
-    if (seen >> fields[i] & 1) return fail(MPCEKF_E_ARG, "pack_get: fields: id %d given twice", fields[i]);
-    seen |= 1u << fields[i];
-  }
+  int rc = check_rows(X, "pack_get", "PK", MPCEKF_NPK, nfields, fields, values);
+  if (rc) return rc;
   if (!X->d_pk) return fail(MPCEKF_E_STATE, "pack_get: call mpcekf_pack_begin first");
-  HIPCHK(hipSetDevice(X->device));
-  const size_t n = (size_t)X->n;
-  for (int i = 0; i < nfields && n; ++i)
-    HIPCHK(hipMemcpyAsync(values + (size_t)i * n, X->d_pk + (size_t)fields[i] * n, n * 8, hipMemcpyDeviceToHost,
-                          X->stream));
-  HIPCHK(hipStreamSynchronize(X->stream));
-  return MPCEKF_OK;
+  return get_rows(X, X->d_pk, (size_t)X->n, nfields, fields, values);
 }
 
 int mpcekf_pack_end(mpcekf_ctx *X) {
@@ -2458,11 +2480,7 @@ int mpcekf_pack_end(mpcekf_ctx *X) {
   HIPCHK(hipSetDevice(X->device));
   HIPCHK(hipStreamSynchronize(X->stream));
   // the graphs captured on a pack context launch k_pack on the record: retired before it is freed
-  for (size_t i = X->graphs.size(); i-- > 0;)
-    if (X->graphs[i].key[4]) {
-      (void)hipGraphExecDestroy(X->graphs[i].exec);
-      X->graphs.erase(X->graphs.begin() + (std::ptrdiff_t)i);
-    }
+  X->retire_graphs([](const GraphParts &k) { return k.pack.rec != 0; });
   (void)hipFree(X->d_pk);
   X->d_pk = nullptr;
   X->pk_series = 0;
@@ -2476,7 +2494,12 @@ int mpcekf_step_ex_pack(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, co
   if (!X->d_pk) return fail(MPCEKF_E_STATE, "step_ex_pack: call mpcekf_pack_begin first");
   if ((temp || heat) && !X->d_th)
     return fail(MPCEKF_E_STATE, "step_ex_pack: temp / heat rows: call mpcekf_thermal_begin first");
-  return step_impl(X, nsteps, tc_degC, tr, slots, nslots, obs, outputs_on_device, false, temp, heat, ucmd, limiter);
+  StepOut o;
+  o.temp = temp;
+  o.heat = heat;
+  o.ucmd = ucmd;
+  o.limiter = limiter;
+  return step_impl(X, nsteps, tc_degC, tr, slots, nslots, obs, outputs_on_device, o);
 }
 
 // ---- passive balancing of pack strings along the fused loop (mpcekf_balance.hip) ----
@@ -2528,27 +2551,10 @@ int mpcekf_balance_begin(mpcekf_ctx *X, const double *params, int32_t compensate
 }
 
 int mpcekf_balance_get(mpcekf_ctx *X, int32_t nfields, const int32_t *fields, double *values) {
-  if (!X) return fail(MPCEKF_E_ARG, "balance_get: null ctx");
-  if (nfields < 1 || nfields > MPCEKF_NBL)
-    return fail(MPCEKF_E_ARG, "balance_get: nfields = %d outside 1..%d", nfields, (int)MPCEKF_NBL);
-  if (!fields) return fail(MPCEKF_E_ARG, "balance_get: null fields");
-  if (!values) return fail(MPCEKF_E_ARG, "balance_get: null values");
-  unsigned seen = 0;
-  for (int i = 0; i < nfields; ++i) {
-    if (fields[i] < 0 || fields[i] >= MPCEKF_NBL)
-      return fail(MPCEKF_E_ARG, "balance_get: fields[%d] = %d is not a MPCEKF_BL_* id (0..%d)", i, fields[i],
-                  (int)MPCEKF_NBL - 1);
-    if (seen >> fields[i] & 1) return fail(MPCEKF_E_ARG, "balance_get: fields: id %d given twice", fields[i]);
-    seen |= 1u << fields[i];
-  }
+  int rc = check_rows(X, "balance_get", "BL", MPCEKF_NBL, nfields, fields, values);
+  if (rc) return rc;
   if (!X->d_bl) return fail(MPCEKF_E_STATE, "balance_get: call mpcekf_balance_begin first");
-  HIPCHK(hipSetDevice(X->device));
-  const size_t n = (size_t)X->n;
-  for (int i = 0; i < nfields && n; ++i)
-    HIPCHK(hipMemcpyAsync(values + (size_t)i * n, X->d_bl + (size_t)fields[i] * n, n * 8, hipMemcpyDeviceToHost,
-                          X->stream));
-  HIPCHK(hipStreamSynchronize(X->stream));
-  return MPCEKF_OK;
+  return get_rows(X, X->d_bl, (size_t)X->n, nfields, fields, values);
 }
 
 int mpcekf_balance_end(mpcekf_ctx *X) {
@@ -2558,11 +2564,7 @@ int mpcekf_balance_end(mpcekf_ctx *X) {
   HIPCHK(hipStreamSynchronize(X->stream));
   // the graphs captured on a balancing context launch k_pack_bal on these buffers: retired before
   // they are freed
-  for (size_t i = X->graphs.size(); i-- > 0;)
-    if (X->graphs[i].key[16]) {
-      (void)hipGraphExecDestroy(X->graphs[i].exec);
-      X->graphs.erase(X->graphs.begin() + (std::ptrdiff_t)i);
-    }
+  X->retire_graphs([](const GraphParts &k) { return k.balance.rec != 0; });
   void *ptrs[] = {X->d_bl, X->d_bl_par, X->d_bl_soc, X->d_bl_on};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
@@ -2579,8 +2581,14 @@ int mpcekf_step_ex_balance(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC,
   if (!X->d_pk || !X->d_bl) return fail(MPCEKF_E_STATE, "step_ex_balance: call mpcekf_balance_begin first");
   if ((temp || heat) && !X->d_th)
     return fail(MPCEKF_E_STATE, "step_ex_balance: temp / heat rows: call mpcekf_thermal_begin first");
-  return step_impl(X, nsteps, tc_degC, tr, slots, nslots, obs, outputs_on_device, false, temp, heat, ucmd, limiter,
-                   nullptr, nullptr, bleed, zmin);
+  StepOut o;
+  o.temp = temp;
+  o.heat = heat;
+  o.ucmd = ucmd;
+  o.limiter = limiter;
+  o.bleed = bleed;
+  o.zmin = zmin;
+  return step_impl(X, nsteps, tc_degC, tr, slots, nslots, obs, outputs_on_device, o);
 }
 
 // ---- charger limits on pack strings along the fused loop (mpcekf_charger.hip) ----
@@ -2622,27 +2630,10 @@ int mpcekf_charger_begin(mpcekf_ctx *X, const double *params) {
 }
 
 int mpcekf_charger_get(mpcekf_ctx *X, int32_t nfields, const int32_t *fields, double *values) {
-  if (!X) return fail(MPCEKF_E_ARG, "charger_get: null ctx");
-  if (nfields < 1 || nfields > MPCEKF_NCH)
-    return fail(MPCEKF_E_ARG, "charger_get: nfields = %d outside 1..%d", nfields, (int)MPCEKF_NCH);
-  if (!fields) return fail(MPCEKF_E_ARG, "charger_get: null fields");
-  if (!values) return fail(MPCEKF_E_ARG, "charger_get: null values");
-  unsigned seen = 0;
-  for (int i = 0; i < nfields; ++i) {
-    if (fields[i] < 0 || fields[i] >= MPCEKF_NCH)
-      return fail(MPCEKF_E_ARG, "charger_get: fields[%d] = %d is not a MPCEKF_CH_* id (0..%d)", i, fields[i],
-                  (int)MPCEKF_NCH - 1);
-    if (seen >> fields[i] & 1) return fail(MPCEKF_E_ARG, "charger_get: fields: id %d given twice", fields[i]);
-    seen |= 1u << fields[i];
-  }
+  int rc = check_rows(X, "charger_get", "CH", MPCEKF_NCH, nfields, fields, values);
+  if (rc) return rc;
   if (!X->d_pk || !X->d_ch) return fail(MPCEKF_E_STATE, "charger_get: call mpcekf_charger_begin first");
-  HIPCHK(hipSetDevice(X->device));
-  const size_t ns = (size_t)X->n / (size_t)X->pk_series;
-  for (int i = 0; i < nfields && ns; ++i)
-    HIPCHK(hipMemcpyAsync(values + (size_t)i * ns, X->d_ch + (size_t)fields[i] * ns, ns * 8, hipMemcpyDeviceToHost,
-                          X->stream));
-  HIPCHK(hipStreamSynchronize(X->stream));
-  return MPCEKF_OK;
+  return get_rows(X, X->d_ch, (size_t)X->n / (size_t)X->pk_series, nfields, fields, values);  // a row per string
 }
 
 int mpcekf_charger_end(mpcekf_ctx *X) {
@@ -2652,11 +2643,7 @@ int mpcekf_charger_end(mpcekf_ctx *X) {
   HIPCHK(hipStreamSynchronize(X->stream));
   // the graphs captured on a charger context launch k_charger on these buffers: retired before
   // they are freed
-  for (size_t i = X->graphs.size(); i-- > 0;)
-    if (X->graphs[i].key[21]) {
-      (void)hipGraphExecDestroy(X->graphs[i].exec);
-      X->graphs.erase(X->graphs.begin() + (std::ptrdiff_t)i);
-    }
+  X->retire_graphs([](const GraphParts &k) { return k.charger.rec != 0; });
   (void)hipFree(X->d_ch);
   if (X->d_ch_par) (void)hipFree(X->d_ch_par);
   X->d_ch = X->d_ch_par = nullptr;
@@ -2673,8 +2660,17 @@ int mpcekf_step_ex_charger(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC,
     return fail(MPCEKF_E_STATE, "step_ex_charger: bleed / zmin rows: call mpcekf_balance_begin first");
   if ((temp || heat) && !X->d_th)
     return fail(MPCEKF_E_STATE, "step_ex_charger: temp / heat rows: call mpcekf_thermal_begin first");
-  return step_impl(X, nsteps, tc_degC, tr, slots, nslots, obs, outputs_on_device, false, temp, heat, ucmd, limiter,
-                   nullptr, nullptr, bleed, zmin, vstr, istr, capby);
+  StepOut o;
+  o.temp = temp;
+  o.heat = heat;
+  o.ucmd = ucmd;
+  o.limiter = limiter;
+  o.bleed = bleed;
+  o.zmin = zmin;
+  o.vstr = vstr;
+  o.istr = istr;
+  o.capby = capby;
+  return step_impl(X, nsteps, tc_degC, tr, slots, nslots, obs, outputs_on_device, o);
 }
 
 // ---- charge termination along the fused loop (mpcekf_term.hip) ----
@@ -2717,27 +2713,10 @@ int mpcekf_term_begin(mpcekf_ctx *X, const double *params, int32_t hold) {
 }
 
 int mpcekf_term_get(mpcekf_ctx *X, int32_t nfields, const int32_t *fields, double *values) {
-  if (!X) return fail(MPCEKF_E_ARG, "term_get: null ctx");
-  if (nfields < 1 || nfields > MPCEKF_NTM)
-    return fail(MPCEKF_E_ARG, "term_get: nfields = %d outside 1..%d", nfields, (int)MPCEKF_NTM);
-  if (!fields) return fail(MPCEKF_E_ARG, "term_get: null fields");
-  if (!values) return fail(MPCEKF_E_ARG, "term_get: null values");
-  unsigned seen = 0;
-  for (int i = 0; i < nfields; ++i) {
-    if (fields[i] < 0 || fields[i] >= MPCEKF_NTM)
-      return fail(MPCEKF_E_ARG, "term_get: fields[%d] = %d is not a MPCEKF_TM_* id (0..%d)", i, fields[i],
-                  (int)MPCEKF_NTM - 1);
-    if (seen >> fields[i] & 1) return fail(MPCEKF_E_ARG, "term_get: fields: id %d given twice", fields[i]);
-    seen |= 1u << fields[i];
-  }
+  int rc = check_rows(X, "term_get", "TM", MPCEKF_NTM, nfields, fields, values);
+  if (rc) return rc;
   if (!X->d_tm) return fail(MPCEKF_E_STATE, "term_get: call mpcekf_term_begin first");
-  HIPCHK(hipSetDevice(X->device));
-  const size_t n = (size_t)X->n;
-  for (int i = 0; i < nfields && n; ++i)
-    HIPCHK(hipMemcpyAsync(values + (size_t)i * n, X->d_tm + (size_t)fields[i] * n, n * 8, hipMemcpyDeviceToHost,
-                          X->stream));
-  HIPCHK(hipStreamSynchronize(X->stream));
-  return MPCEKF_OK;
+  return get_rows(X, X->d_tm, (size_t)X->n, nfields, fields, values);
 }
 
 int mpcekf_term_open(mpcekf_ctx *X, int64_t *open_cells) {
@@ -2759,11 +2738,7 @@ int mpcekf_term_end(mpcekf_ctx *X) {
   HIPCHK(hipStreamSynchronize(X->stream));
   // the graphs captured on a terminating context launch k_term on these buffers: retired before
   // they are freed
-  for (size_t i = X->graphs.size(); i-- > 0;)
-    if (X->graphs[i].key[13]) {
-      (void)hipGraphExecDestroy(X->graphs[i].exec);
-      X->graphs.erase(X->graphs.begin() + (std::ptrdiff_t)i);
-    }
+  X->retire_graphs([](const GraphParts &k) { return k.term.rec != 0; });
   void *ptrs[] = {X->d_tm, X->d_tm_par, X->d_tm_soc, X->d_tm_int};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
@@ -2793,11 +2768,11 @@ int mpcekf_step_until(mpcekf_ctx *X, int32_t max_steps, int32_t chunk, const dou
   int32_t run = 0;
   int64_t open = 0;
   if ((rc = mpcekf_term_open(X, &open))) return rc;
+  StepOut o;
+  o.sum = X->d_sum != nullptr;  // with a summary begun the record folds as in mpcekf_step_summary
   while (run < max_steps) {
     const int32_t m = std::min(chunk, max_steps - run);
-    rc = X->d_sum ? step_impl(X, m, tcp, nullptr, nullptr, 0, nullptr, 0, true)
-                  : step_impl(X, m, tcp, nullptr, nullptr, 0, nullptr, 0);
-    if (rc) return rc;
+    if ((rc = step_impl(X, m, tcp, nullptr, nullptr, 0, nullptr, 0, o))) return rc;
     run += m;
     if ((rc = mpcekf_term_open(X, &open))) return rc;  // one 4-byte copy
     if (open == 0) break;
@@ -2819,11 +2794,7 @@ static_assert(NAGP == MPCEKF_NAGP && AG_I0 == MPCEKF_AG_I0 && AG_U == MPCEKF_AG_
 // the graphs captured on an aging context launch k_aging on the record and the rows: retired
 // before any of them is freed, or when the launches they hold no longer fit nreact / sources
 static void retire_aging_graphs(mpcekf_ctx *X) {
-  for (size_t i = X->graphs.size(); i-- > 0;)
-    if (X->graphs[i].key[6]) {
-      (void)hipGraphExecDestroy(X->graphs[i].exec);
-      X->graphs.erase(X->graphs.begin() + (std::ptrdiff_t)i);
-    }
+  X->retire_graphs([](const GraphParts &k) { return k.aging.rec != 0; });
 }
 
 int mpcekf_aging_begin(mpcekf_ctx *X, int32_t nreact, int32_t sources, const double *params) {
@@ -2909,33 +2880,18 @@ int mpcekf_aging_begin(mpcekf_ctx *X, int32_t nreact, int32_t sources, const dou
 
 int mpcekf_aging_get(mpcekf_ctx *X, int32_t source, int32_t react, int32_t nfields, const int32_t *fields,
                      double *values) {
-  if (!X) return fail(MPCEKF_E_ARG, "aging_get: null ctx");
-  if (nfields < 1 || nfields > MPCEKF_NAGR)
-    return fail(MPCEKF_E_ARG, "aging_get: nfields = %d outside 1..%d", nfields, (int)MPCEKF_NAGR);
-  if (!fields) return fail(MPCEKF_E_ARG, "aging_get: null fields");
-  if (!values) return fail(MPCEKF_E_ARG, "aging_get: null values");
-  unsigned seen = 0;
-  for (int i = 0; i < nfields; ++i) {
-    if (fields[i] < 0 || fields[i] >= MPCEKF_NAGR)
-      return fail(MPCEKF_E_ARG, "aging_get: fields[%d] = %d is not a MPCEKF_AGR_* id (0..%d)", i, fields[i],
-                  (int)MPCEKF_NAGR - 1);
-    if (seen >> fields[i] & 1) return fail(MPCEKF_E_ARG, "aging_get: fields: id %d given twice", fields[i]);
-    seen |= 1u << fields[i];
-  }
+  int rc = check_rows(X, "aging_get", "AGR", MPCEKF_NAGR, nfields, fields, values);
+  if (rc) return rc;
   if (!X->d_ag) return fail(MPCEKF_E_STATE, "aging_get: call mpcekf_aging_begin first");
   if ((source != MPCEKF_AG_SRC_EST && source != MPCEKF_AG_SRC_PLANT) || !(X->ag_sources & source))
     return fail(MPCEKF_E_ARG, "aging_get: source = %d is not a source this context's begin enabled (mask %d)", source,
                 X->ag_sources);
   if (react < 0 || react >= X->ag_nreact)
     return fail(MPCEKF_E_ARG, "aging_get: react = %d outside 0..%d", react, X->ag_nreact - 1);
-  HIPCHK(hipSetDevice(X->device));
-  const size_t n = (size_t)X->n;
   const int s = source == MPCEKF_AG_SRC_EST ? AG_SRC_EST : AG_SRC_PLANT;
-  for (int i = 0; i < nfields && n; ++i)
-    HIPCHK(hipMemcpyAsync(values + (size_t)i * n, X->d_ag + (size_t)ag_row(s, react, fields[i]) * n, n * 8,
-                          hipMemcpyDeviceToHost, X->stream));
-  HIPCHK(hipStreamSynchronize(X->stream));
-  return MPCEKF_OK;
+  int32_t rows[MPCEKF_NAGR];  // the record rows of this source's and reaction's fields
+  for (int i = 0; i < nfields; ++i) rows[i] = ag_row(s, react, fields[i]);
+  return get_rows(X, X->d_ag, (size_t)X->n, nfields, rows, values);
 }
 
 int mpcekf_aging_end(mpcekf_ctx *X) {
@@ -2963,7 +2919,13 @@ int mpcekf_step_ex_aging(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, c
     return fail(MPCEKF_E_STATE, "step_ex_aging: temp / heat rows: call mpcekf_thermal_begin first");
   if ((ucmd || limiter) && !X->d_pk)
     return fail(MPCEKF_E_STATE, "step_ex_aging: ucmd / limiter rows: call mpcekf_pack_begin first");
-  return step_impl(X, nsteps, tc_degC, tr, slots, nslots, obs, outputs_on_device, false, temp, heat, ucmd, limiter, rate);
+  StepOut o;
+  o.temp = temp;
+  o.heat = heat;
+  o.ucmd = ucmd;
+  o.limiter = limiter;
+  o.rate = rate;
+  return step_impl(X, nsteps, tc_degC, tr, slots, nslots, obs, outputs_on_device, o);
 }
 
 // ---- heat conduction between neighbouring cells of a pack string (mpcekf_thermal_couple.hip) ----
@@ -3008,27 +2970,10 @@ int mpcekf_thermal_couple(mpcekf_ctx *X, const double *r_link) {
 }
 
 int mpcekf_thermal_couple_get(mpcekf_ctx *X, int32_t nfields, const int32_t *fields, double *values) {
-  if (!X) return fail(MPCEKF_E_ARG, "thermal_couple_get: null ctx");
-  if (nfields < 1 || nfields > MPCEKF_NTCR)
-    return fail(MPCEKF_E_ARG, "thermal_couple_get: nfields = %d outside 1..%d", nfields, (int)MPCEKF_NTCR);
-  if (!fields) return fail(MPCEKF_E_ARG, "thermal_couple_get: null fields");
-  if (!values) return fail(MPCEKF_E_ARG, "thermal_couple_get: null values");
-  unsigned seen = 0;
-  for (int i = 0; i < nfields; ++i) {
-    if (fields[i] < 0 || fields[i] >= MPCEKF_NTCR)
-      return fail(MPCEKF_E_ARG, "thermal_couple_get: fields[%d] = %d is not a MPCEKF_TCR_* id (0..%d)", i, fields[i],
-                  (int)MPCEKF_NTCR - 1);
-    if (seen >> fields[i] & 1) return fail(MPCEKF_E_ARG, "thermal_couple_get: fields: id %d given twice", fields[i]);
-    seen |= 1u << fields[i];
-  }
+  int rc = check_rows(X, "thermal_couple_get", "TCR", MPCEKF_NTCR, nfields, fields, values);
+  if (rc) return rc;
   if (!X->d_tc) return fail(MPCEKF_E_STATE, "thermal_couple_get: call mpcekf_thermal_couple first");
-  HIPCHK(hipSetDevice(X->device));
-  const size_t n = (size_t)X->n;
-  for (int i = 0; i < nfields && n; ++i)
-    HIPCHK(hipMemcpyAsync(values + (size_t)i * n, X->d_tc + (size_t)fields[i] * n, n * 8, hipMemcpyDeviceToHost,
-                          X->stream));
-  HIPCHK(hipStreamSynchronize(X->stream));
-  return MPCEKF_OK;
+  return get_rows(X, X->d_tc, (size_t)X->n, nfields, fields, values);
 }
 
 int mpcekf_thermal_couple_end(mpcekf_ctx *X) {
@@ -3038,11 +2983,7 @@ int mpcekf_thermal_couple_end(mpcekf_ctx *X) {
   HIPCHK(hipStreamSynchronize(X->stream));
   // the graphs captured on a coupled context launch its kernels on these buffers: retired before
   // they are freed
-  for (size_t i = X->graphs.size(); i-- > 0;)
-    if (X->graphs[i].key[10]) {
-      (void)hipGraphExecDestroy(X->graphs[i].exec);
-      X->graphs.erase(X->graphs.begin() + (std::ptrdiff_t)i);
-    }
+  X->retire_graphs([](const GraphParts &k) { return k.couple.rec != 0; });
   void *ptrs[] = {X->d_tc, X->d_tc_link, X->d_tc_snap};
   for (void *p : ptrs) (void)hipFree(p);
   X->d_tc = X->d_tc_link = X->d_tc_snap = nullptr;
@@ -3055,8 +2996,14 @@ int mpcekf_step_ex_couple(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, 
   if (!X) return fail(MPCEKF_E_ARG, "step_ex_couple: null ctx");
   if (!X->d_tc) return fail(MPCEKF_E_STATE, "step_ex_couple: call mpcekf_thermal_couple first");
   if (rate && !X->d_ag) return fail(MPCEKF_E_STATE, "step_ex_couple: rate rows: call mpcekf_aging_begin first");
-  return step_impl(X, nsteps, tc_degC, tr, slots, nslots, obs, outputs_on_device, false, temp, heat, ucmd, limiter, rate,
-                   cond);
+  StepOut o;
+  o.temp = temp;
+  o.heat = heat;
+  o.ucmd = ucmd;
+  o.limiter = limiter;
+  o.rate = rate;
+  o.cond = cond;
+  return step_impl(X, nsteps, tc_degC, tr, slots, nslots, obs, outputs_on_device, o);
 }
 
 int mpcekf_set_timing(mpcekf_ctx *X, int32_t enable) {

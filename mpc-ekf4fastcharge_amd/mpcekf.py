@@ -274,6 +274,12 @@ class Context:
                        zbk=(np.float64, None), J_unc=(np.float64, ()), J_fin=(np.float64, ()),
                        norm_du=(np.float64, ()), nviol=(np.int32, ()), poles=(np.float64, (7, 2)),
                        sv=(np.float64, (7,)))
+    # the optional per-step rows of step(thermal=..., pack=...): name -> (one element per string and
+    # step instead of per cell and step, dtype)
+    STEP_ROWS = dict(temp=(False, np.float64), heat=(False, np.float64), cond=(False, np.float64),
+                     ucmd=(False, np.float64), bleed=(False, np.float64), zmin=(True, np.float64),
+                     vstr=(True, np.float64), istr=(True, np.float64), limiter=(True, np.int32),
+                     capby=(True, np.int32))
 
     def step(self, nsteps, outputs=("u", "v", "soc", "phise", "nexec"), tc=None, obs=None, thermal=None, pack=None,
              aging=None):
@@ -348,92 +354,32 @@ class Context:
         tcp = tcs.ctypes.data_as(C.c_void_p) if tcs is not None else None
         rec = None if fields is None else np.empty((nsteps, slots.size, n))
         vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
-        if chg:   # a pack context with a charger (and a balancer, for bleed / zmin)
-            for k in th:
-                out[k] = np.empty((nsteps, n))
-            series = getattr(self, "_pack_series", 0)   # 0: no begin, the library refuses the call
-            nstr = n // series if series else n
-            for k in ("ucmd", "bleed"):
-                if k in pk:
-                    out[k] = np.empty((nsteps, n))
-            for k in ("zmin", "vstr", "istr"):
-                if k in pk:
-                    out[k] = np.empty((nsteps, nstr))
-            for k in ("limiter", "capby"):
-                if k in pk:
-                    out[k] = np.empty((nsteps, nstr), dtype=np.int32)
-            ns = 0 if fields is None else int(slots.size)
-            check(self.L.mpcekf_step_ex_charger(self.h, int(nsteps), tcp, C.byref(tr), iptr(slots) if ns else None, ns,
-                                                vp(rec) if ns else None, vp(out.get("temp")), vp(out.get("heat")),
-                                                vp(out.get("ucmd")), vp(out.get("limiter")), vp(out.get("bleed")),
-                                                vp(out.get("zmin")), vp(out.get("vstr")), vp(out.get("istr")),
-                                                vp(out.get("capby")), 0))
-        elif bal:   # a pack context with a balancer
-            for k in th:
-                out[k] = np.empty((nsteps, n))
-            series = getattr(self, "_pack_series", 0)   # 0: no begin, the library refuses the call
-            if "ucmd" in pk:
-                out["ucmd"] = np.empty((nsteps, n))
-            if "limiter" in pk:
-                out["limiter"] = np.empty((nsteps, n // series if series else n), dtype=np.int32)
-            if "bleed" in pk:
-                out["bleed"] = np.empty((nsteps, n))
-            if "zmin" in pk:
-                out["zmin"] = np.empty((nsteps, n // series if series else n))
-            ns = 0 if fields is None else int(slots.size)
-            check(self.L.mpcekf_step_ex_balance(self.h, int(nsteps), tcp, C.byref(tr), iptr(slots) if ns else None, ns,
-                                                vp(rec) if ns else None, vp(out.get("temp")), vp(out.get("heat")),
-                                                vp(out.get("ucmd")), vp(out.get("limiter")), vp(out.get("bleed")),
-                                                vp(out.get("zmin")), 0))
-        elif "cond" in th:   # every row of a coupled context: it has a model and a pack
-            for k in th:
-                out[k] = np.empty((nsteps, n))
-            series = getattr(self, "_pack_series", 0)   # 0: no begin, the library refuses the call
-            if "ucmd" in pk:
-                out["ucmd"] = np.empty((nsteps, n))
-            if "limiter" in pk:
-                out["limiter"] = np.empty((nsteps, n // series if series else n), dtype=np.int32)
-            nreact, mask = getattr(self, "_aging", (0, 0))
-            if "rate" in ag:
-                out["rate"] = np.empty((nsteps, max(bin(mask).count("1") * nreact, 1), n))
-            ns = 0 if fields is None else int(slots.size)
-            check(self.L.mpcekf_step_ex_couple(self.h, int(nsteps), tcp, C.byref(tr), iptr(slots) if ns else None, ns,
-                                               vp(rec) if ns else None, vp(out.get("temp")), vp(out.get("heat")),
-                                               vp(out.get("ucmd")), vp(out.get("limiter")), vp(out.get("rate")),
-                                               vp(out["cond"]), 0))
-        elif aging is not None:
-            for k in th:
-                out[k] = np.empty((nsteps, n))
-            series = getattr(self, "_pack_series", 0)
-            if "ucmd" in pk:
-                out["ucmd"] = np.empty((nsteps, n))
-            if "limiter" in pk:
-                out["limiter"] = np.empty((nsteps, n // series if series else n), dtype=np.int32)
+        # the optional rows the call names, per cell or per string (STEP_ROWS); rate has a shape of its own
+        series = getattr(self, "_pack_series", 0)   # 0: no begin, the library refuses the call
+        for k in th + pk:
+            per_string, dt = self.STEP_ROWS[k]
+            out[k] = np.empty((nsteps, n // series if per_string and series else n), dtype=dt)
+        if "rate" in ag:
             nreact, mask = getattr(self, "_aging", (0, 0))   # (0, 0): no begin, the library refuses the call
-            if "rate" in ag:
-                out["rate"] = np.empty((nsteps, max(bin(mask).count("1") * nreact, 1), n))
-            ns = 0 if fields is None else int(slots.size)
-            check(self.L.mpcekf_step_ex_aging(self.h, int(nsteps), tcp, C.byref(tr), iptr(slots) if ns else None, ns,
-                                              vp(rec) if ns else None, vp(out.get("temp")), vp(out.get("heat")),
-                                              vp(out.get("ucmd")), vp(out.get("limiter")), vp(out.get("rate")), 0))
+            out["rate"] = np.empty((nsteps, max(bin(mask).count("1") * nreact, 1), n))
+        row = lambda *names: tuple(vp(out.get(k)) for k in names)
+        ns = 0 if fields is None else int(slots.size)
+        head, tail = (self.h, int(nsteps)), (C.byref(tr), iptr(slots) if ns else None, ns, vp(rec) if ns else None)
+        call = head + (tcp,) + tail
+        # the entry point, in this order: it decides which refusal of the library a misuse gets
+        if chg:   # a pack context with a charger (and a balancer, for bleed / zmin)
+            check(self.L.mpcekf_step_ex_charger(*call, *row("temp", "heat", "ucmd", "limiter", "bleed", "zmin", "vstr",
+                                                            "istr", "capby"), 0))
+        elif bal:   # a pack context with a balancer
+            check(self.L.mpcekf_step_ex_balance(*call, *row("temp", "heat", "ucmd", "limiter", "bleed", "zmin"), 0))
+        elif "cond" in th:   # every row of a coupled context: it has a model and a pack
+            check(self.L.mpcekf_step_ex_couple(*call, *row("temp", "heat", "ucmd", "limiter", "rate", "cond"), 0))
+        elif aging is not None:
+            check(self.L.mpcekf_step_ex_aging(*call, *row("temp", "heat", "ucmd", "limiter", "rate"), 0))
         elif pack is not None:
-            for k in th:
-                out[k] = np.empty((nsteps, n))
-            series = getattr(self, "_pack_series", 0)   # 0: no begin, the library refuses the call
-            if "ucmd" in pk:
-                out["ucmd"] = np.empty((nsteps, n))
-            if "limiter" in pk:
-                out["limiter"] = np.empty((nsteps, n // series if series else n), dtype=np.int32)
-            ns = 0 if fields is None else int(slots.size)
-            check(self.L.mpcekf_step_ex_pack(self.h, int(nsteps), tcp, C.byref(tr), iptr(slots) if ns else None, ns,
-                                             vp(rec) if ns else None, vp(out.get("temp")), vp(out.get("heat")),
-                                             vp(out.get("ucmd")), vp(out.get("limiter")), 0))
-        elif thermal is not None:
-            for k in th:
-                out[k] = np.empty((nsteps, n))
-            ns = 0 if fields is None else int(slots.size)
-            check(self.L.mpcekf_step_ex_thermal(self.h, int(nsteps), C.byref(tr), iptr(slots) if ns else None, ns,
-                                                vp(rec) if ns else None, vp(out.get("temp")), vp(out.get("heat")), 0))
+            check(self.L.mpcekf_step_ex_pack(*call, *row("temp", "heat", "ucmd", "limiter"), 0))
+        elif thermal is not None:   # the model takes no tc
+            check(self.L.mpcekf_step_ex_thermal(*head, *tail, *row("temp", "heat"), 0))
         elif fields is None:
             check(self.L.mpcekf_step_ex(self.h, int(nsteps), tcp, C.byref(tr), 0))
         elif slots.size:
