@@ -150,7 +150,9 @@ typedef struct {
   mpcekf_electrode neg, pos;
 } mpcekf_rom;
 
-#define MPCEKF_CF_BOUNDS 1 /* also compute boundzk (iterEKF.m:186-205) */
+/* also compute boundzk (iterEKF.m:186-205): on every step of a fused call that asks for a zbk
+ * trajectory, otherwise on the call's last step only (what mpcekf_get_zk returns) */
+#define MPCEKF_CF_BOUNDS 1
 
 /* Controller/estimator configuration (runMPC.m:8-50, initMPC.m). */
 typedef struct {
@@ -255,7 +257,10 @@ int mpcekf_step_ex_obs(mpcekf_ctx *ctx, int32_t nsteps, const double *tc_degC, c
                        const int32_t *slots, int32_t nslots, double *obs, int32_t outputs_on_device);
 
 /* Optional per-step EKF output of the LAST mpcekf_step call: zk and boundzk
- * ([ncells][nz+2], boundzk only with MPCEKF_CF_BOUNDS). */
+ * ([ncells][nz+2], boundzk only with MPCEKF_CF_BOUNDS) of that call's last step.  A fused call
+ * of several steps evaluates boundzk (and stores zk) on every step only when it is given their
+ * trajectory (mpcekf_traj.zbk / .zk); otherwise it evaluates them on its last step alone, the
+ * only one this getter can return.  A call of one step evaluates them as ever. */
 int mpcekf_get_zk(mpcekf_ctx *ctx, double *zk, double *boundzk);
 
 /* eig / svd of one n x n (n <= 8) row-major matrix on the host, as the fused step
@@ -377,7 +382,9 @@ int mpcekf_hildreth_structured(int device, int64_t n, const double *E, const dou
  * counts of [plant, flush, cell, hild, bounds] (arrays of MPCEKF_NKERNELS) since the
  * last call and resets them.  "flush" is the all-model time update (k_flush, every
  * 32 steps and at the end of each call); "bounds" is boundzk (k_bounds, when
- * MPCEKF_CF_BOUNDS is set). */
+ * MPCEKF_CF_BOUNDS is set): its milliseconds and its launch count cover only the steps that
+ * launched k_bounds, which are every step of a call with a zbk trajectory and the last step
+ * of any other call. */
 #define MPCEKF_K_PLANT 0
 #define MPCEKF_K_FLUSH 1
 #define MPCEKF_K_CELL 2

@@ -1487,7 +1487,7 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
   const bool bounds = X->cfg.flags & MPCEKF_CF_BOUNDS;
   if (tr->zbk && !bounds) return fail(MPCEKF_E_ARG, "step_ex: a boundzk trajectory needs MPCEKF_CF_BOUNDS");
   // boundzk from k_cell's / k_ekf4's hand-off record in k_bounds (MB writes boundzk in
-  // k_cell, from its one 6x6 covariance)
+  // k_cell, from its one 6x6 covariance), on the steps that can be read (below)
   // per-cell limits (mpcekf_set_limits): the split route at every batch size, no k_ekf4 mapping
   const double *lim = X->lim();
   const bool quad = X->quad && !lim, split_cell = X->split_cell && !lim;
@@ -1626,6 +1626,11 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
   const int hstart = side ? 7 : 3;  // the event that opens the Hildreth interval
   const int P = X->flush_period;
   std::vector<char> flushed((size_t)nsteps, 0);
+  // boundzk and zk only where they can be read: on every step when the call has
+  // their trajectory, else on the call's last step, whose values mpcekf_get_zk returns.  zk also
+  // on every step of the two-kernel routes, whose k_cell<P_MPC> reads it back (io2.zk_in)
+  const bool zk_readback = !(X->wide || switched) && (split_cell || quad);
+  std::vector<char> bounded((size_t)nsteps, 0);  // the steps that launched k_bounds
   const bool sched = thermal && X->sched;
   const KSched ksch = X->ksched();
   auto run_steps = [&]() -> int {
@@ -1685,10 +1690,13 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
       if (balance && !io.soc) io.soc = X->d_bl_soc;      // k_pack_bal's likewise
       io.nexec = (int *)row(F_NEXEC, k);
       io.x_out = (double *)row(F_X, k);
-      io.zk = f[F_ZK].dev ? (double *)row(F_ZK, k) : X->d_zk;
+      const bool last = k == nsteps - 1;
+      io.zk = f[F_ZK].dev ? (double *)row(F_ZK, k) : last || zk_readback ? X->d_zk : nullptr;
       double *zbk_k = f[F_ZBK].dev ? (double *)row(F_ZBK, k) : X->d_zbk;
-      io.zbk = bounds ? zbk_k : nullptr;
-      io.bnd = bnd_kernel ? X->d_bnd : nullptr;
+      const bool zbk_step = bounds && (f[F_ZBK].dev || last);
+      const bool bnd_step = bnd_kernel && zbk_step;  // k_cell's record and the k_bounds launch that reads it
+      io.zbk = zbk_step ? zbk_k : nullptr;
+      io.bnd = bnd_step ? X->d_bnd : nullptr;
       io.junc_out = (double *)row(F_JUNC, k);
       io.jfin_out = (double *)row(F_JFIN, k);
       io.normdu_out = (double *)row(F_NORMDU, k);
@@ -1756,7 +1764,7 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
         flushed[k] = hi > lo;
       }
       // MB: k_cell writes boundzk itself (one 6x6 covariance per cell)
-      if (bnd_kernel) {
+      if (bnd_step) {
         hipStream_t bs = X->stream;
         if (side) {
           HIPCHK(hipEventRecord(X->ev_bfork, X->stream));
@@ -1766,6 +1774,7 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
         if ((rc = lerr(launch_bounds(X->r, X->s, X->d_bnd, zbk_k, bs), "bounds"))) return rc;
         if (E && side) HIPCHK(hipEventRecord(E[3], bs));
         if (side) HIPCHK(hipEventRecord(X->ev_bjoin, bs));
+        bounded[k] = 1;
       }
       if (E) HIPCHK(hipEventRecord(E[hstart], X->stream));
       if (X->wide) {
@@ -1840,7 +1849,7 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
         }
       }
       // k_bounds done before k_flush or the next step's k_cell rewrites the records it reads
-      if (side) HIPCHK(hipStreamWaitEvent(X->stream, X->ev_bjoin, 0));
+      if (side && bnd_step) HIPCHK(hipStreamWaitEvent(X->stream, X->ev_bjoin, 0));
       if (slice && fork) HIPCHK(hipStreamWaitEvent(X->stream, X->ev_join, 0));
       if (roll ? t == nsteps : (t % P == 0 || t == nsteps)) {
         const bool timed = E && !roll;  // the rolling schedule times its slices only
@@ -1968,7 +1977,7 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
     for (int k = 0; k < nsteps; ++k)
       for (int j = 0; j < 5; ++j) {
         if ((k + 1) % X->timing_every != 0 && k != nsteps - 1) continue;
-        if ((j == 4 && !flushed[k]) || (j == 2 && !bnd_kernel) || (j == 0 && plant_in_cell && !nslots)) continue;
+        if ((j == 4 && !flushed[k]) || (j == 2 && !bounded[k]) || (j == 0 && plant_in_cell && !nslots)) continue;
         float ms = 0;
         const int a = j == 3 ? hstart : e0[j], b = j == 3 ? 4 : e0[j] + 1;
         HIPCHK(hipEventElapsedTime(&ms, X->ev[(size_t)k * NEV + a], X->ev[(size_t)k * NEV + b]));
