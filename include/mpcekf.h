@@ -633,6 +633,103 @@ int mpcekf_thermal_schedule(mpcekf_ctx *ctx, int32_t nfields, const int32_t *fie
  * mpcekf_thermal_end does the same implicitly.  A no-op without a schedule. */
 int mpcekf_thermal_schedule_end(mpcekf_ctx *ctx);
 
+/* ---- the MPC limits mapped over the SOC estimate and the temperature (not part of the reference interface) ----
+ * The charger a fast-charge controller is compared against is a current map over state of charge
+ * and temperature: multi-stage constant current, a C-rate that steps down at 40 / 60 / 80 % SOC,
+ * then constant voltage.  A limit map is sets of 2-D tables of limit fields over (SOC estimate,
+ * cell temperature) on uniform grids, evaluated per cell on the device in every fused step -- on
+ * every fused route: mpcekf_step, every _step_ex_*, mpcekf_step_summary, mpcekf_step_until and
+ * graph replay; with packs, the balancer, the charger, termination, the aging record and the
+ * thermal model with links.  Like the temperature schedule it writes rows of the per-cell limits
+ * record and changes no QP structure.
+ *
+ * fields[nfields]: distinct ids among MPCEKF_LIM_CRATE, _U_MAX, _DU_MIN, _DU_MAX, _V_MAX,
+ * _PHISE_MIN.  tables [nsets][nfields][nt][nz] in mpcekf_config's units: entry [jt][jz] of a table
+ * is the field's value at SOC z_lo + jz (z_hi - z_lo) / (nz - 1) (a fraction, as mpcekf_traj.soc)
+ * and T_lo + jt (T_hi - T_lo) / (nt - 1) degC.  nz >= 1, nt >= 1, not both 1.  nt >= 2 needs a
+ * thermal model (MPCEKF_E_STATE without one); nt == 1 ignores the temperature (T_lo_degC and
+ * T_hi_degC are not read) and works on any context.  interp_z: 0 linear in SOC; 1 hold, the left
+ * node's value, so a staircase is exact without steep ramps (node jz then holds on
+ * [z_jz, z_jz+1), node nz - 2 up to z_hi and beyond: the last column is never the value).  The
+ * temperature axis is always linear.  set_of_cell [ncells]: each cell's table set 0..nsets-1;
+ * NULL: set 0.  z0 [ncells]: the SOC fraction to evaluate at until a fused step has produced an
+ * estimate, finite or NaN; NULL: the record's Z_LAST as it stands when the call replaces an
+ * active map, NaN otherwise -- for a first map and for one set after mpcekf_limit_map_end alike
+ * (no step stores Z_LAST while no map is active, so a caller that resumes passes the soc row it
+ * last read).
+ *
+ * The rule.  For fused step t and each mapped field, the MPC stage of step t reads the table
+ * value at
+ *   z: the soc row (zk(end), mpcekf_traj.soc) of the previous fused step, kept per cell in the
+ *      record's Z_LAST row.  Every fused step stores it (a cell in error stores NaN); neither
+ *      mpcekf_init_cells nor mpcekf_set_state touches it.  The estimate of step t itself is formed
+ *      inside the kernel whose MPC stage reads the limits, so the one-step lag is part of the rule;
+ *   T: the temperature step t uses (temp[t] of mpcekf_step_ex_thermal).
+ * Per cell, every line one or more separately rounded fp64 operations in exactly this order (no
+ * contraction, IEEE division):
+ *   xz = (z - z_lo) / (z_hi - z_lo);  xzc = xz > 0 ? xz : 0;  xzc = xzc < 1 ? xzc : 1   (NaN -> 0)
+ *   sz = xzc * (double)(nz - 1);  jz = min((int)sz, nz - 2);  fz = interp_z ? 0.0 : sz - (double)jz
+ *             (nz == 1: jz = 0, and no second column is read)
+ *   xt, st, jt, ft likewise over T, T_lo, T_hi, nt    (nt == 1: jt = 0, and no second row is read)
+ *   a   = tab[jt][jz]   + fz * (tab[jt][jz+1]   - tab[jt][jz])          (nz == 1: a = tab[jt][0])
+ *   b   = tab[jt+1][jz] + fz * (tab[jt+1][jz+1] - tab[jt+1][jz])        (nt >= 2 only)
+ *   val = a + ft * (b - a)                                              (nt == 1: val = a)
+ * The kernels' slot is formed from val by the expression the scalar configuration goes through
+ * (u_min = -Q * val for CRATE, val itself for the others).  So with nz == 1 the map is
+ * mpcekf_thermal_schedule's lookup bit for bit, and a table constant at the configuration's value
+ * feeds the MPC kernels the scalar's bits.
+ *
+ * A fused call evaluates once before its first step, at Z_LAST and the temperature as they stand,
+ * and at the end of every step that another step of the call follows; the call's last step stores
+ * Z_LAST (and advances the model) but evaluates nothing, so the values in force after a call are
+ * what its last step used.  N one-step calls and one N-step call compute the same.
+ *
+ * The record, per cell, every value a double and the counts exact integers: */
+enum {
+  MPCEKF_LM_Z_LAST = 0, /* the soc row of the last fused step (z0 until there is one) */
+  MPCEKF_LM_NEVAL,      /* evaluations made for fused steps since the map was set: one per step */
+  MPCEKF_LM_NCLAMP_Z,   /* those whose xz fell outside [0, 1] or was NaN */
+  MPCEKF_LM_NCLAMP_T,   /* the same for xt (stays 0 with nt == 1) */
+  MPCEKF_NLM
+};
+/* Setting a map moves the context to the per-cell launch sequence if it is not
+ * there already, restarts the record's counts and evaluates once at Z_LAST and the temperatures as
+ * they stand (this evaluation, and the one a mpcekf_set_limits of another field repeats, are not
+ * counted in the record).  A second call replaces the map (fields of the first that the second
+ * does not name go back to their mpcekf_set_limits / configuration values); captured graphs stay
+ * valid.  The map and a temperature schedule exclude each other: whichever is set second returns
+ * MPCEKF_E_STATE and changes nothing.  While a map is active, mpcekf_get_limits returns for a
+ * mapped field the value in force after the last evaluation; mpcekf_set_limits naming a mapped
+ * field returns MPCEKF_E_ARG and mpcekf_clear_limits returns MPCEKF_E_STATE, both changing
+ * nothing.  mpcekf_thermal_end ends a map that has nt >= 2.  The stage route does not evaluate the
+ * map: it reads the values of the last evaluation.  The map's kernels are not among
+ * mpcekf_set_timing's five slots.
+ * MPCEKF_E_ARG (nothing changed): a NULL ctx, fields or tables; nfields outside 1..6; a repeated
+ * id or one that cannot be mapped; nz < 1, nt < 1 or both 1; z_lo or z_hi not finite, or
+ * z_hi <= z_lo; with nt >= 2, T_lo or T_hi not finite, or T_hi <= T_lo; interp_z outside {0, 1};
+ * nsets < 1; a non-finite table entry; a set_of_cell entry outside 0..nsets-1; an infinite z0
+ * entry (the message names the cell). */
+int mpcekf_limit_map(mpcekf_ctx *ctx, int32_t nfields, const int32_t *fields, int32_t nz, double z_lo, double z_hi,
+                     int32_t nt, double T_lo_degC, double T_hi_degC, int32_t interp_z, int32_t nsets,
+                     const double *tables, const int32_t *set_of_cell, const double *z0);
+/* values [nfields][ncells]: row i = field fields[i] (distinct MPCEKF_LM_* ids).  MPCEKF_E_STATE
+ * without a map; MPCEKF_E_ARG: a NULL pointer, nfields outside 1..MPCEKF_NLM, an unknown or
+ * repeated id. */
+int mpcekf_limit_map_get(mpcekf_ctx *ctx, int32_t nfields, const int32_t *fields, double *values);
+/* Ends the map: its fields go back to what mpcekf_set_limits or the configuration last gave them,
+ * and the launch sequence stays per-cell only if a mpcekf_set_limits is still in force.  The
+ * graphs captured with the map are retired.  A no-op without a map. */
+int mpcekf_limit_map_end(mpcekf_ctx *ctx);
+/* mpcekf_step_ex_charger's arguments (each extension's rows must be NULL without that extension
+ * -- MPCEKF_E_STATE -- and no charger is needed) plus lim [nsteps][nfields][ncells] (host, or
+ * device when outputs_on_device != 0; may be NULL): lim[t][i] is the value of the map's field
+ * fields[i] that the MPC stage of step t read, in mpcekf_config's units.  MPCEKF_E_STATE without
+ * a map. */
+int mpcekf_step_ex_map(mpcekf_ctx *ctx, int32_t nsteps, const double *tc_degC, const mpcekf_traj *traj,
+                       const int32_t *slots, int32_t nslots, double *obs, double *temp, double *heat, double *ucmd,
+                       int32_t *limiter, double *bleed, double *zmin, double *vstr, double *istr, int32_t *capby,
+                       double *lim, int32_t outputs_on_device);
+
 /* ---- series strings: one current per pack string along the fused loop (not part of the reference interface) ----
  * Cells in series carry one current, and a charger can only apply what the weakest cell of the
  * string accepts.  With a pack, the cells' controllers stay their own and the library couples

@@ -31,6 +31,16 @@ function [S, out] = mpcekf_session(op, name, value)
 %   [S, out] = mpcekf_session('stepexcharger', nsteps)
 %     out.u .. out.limiter as 'stepexpack' gives them, out.bal (bleed, zmin; [] without a balancer)
 %     and out.chg (vstr, istr, capby), nstrings x nsteps each.
+%   mpcekf_session('limitmap', map)
+%     MPC limits over each cell's SOC estimate and temperature on the session's context
+%     (mpcekf_limit_map): map is a struct with idx, z_lo, z_hi, tables (nz x nt x numel(idx) x nsets)
+%     and the optional T_lo, T_hi, interp (0 linear, 1 hold), sets, z0, as mpcekf_mex('limitmap') takes them.
+%   [S, out] = mpcekf_session('limitmapget')  out: the record, a struct of ncells x 1 vectors (z_last,
+%     neval, nclamp_z, nclamp_t)
+%   mpcekf_session('limitmapend')
+%   [S, out] = mpcekf_session('stepexmap', nsteps)
+%     out.u .. out.nexec as 'step' gives them and out.lim, ncells x numel(idx) x nsteps: the mapped
+%     fields' values the MPC stage of every step read.
   persistent P
   % zk_last / ekf_tick: the zk the last iterEKF returned and a counter of iterEKF calls, so
   % EKFmatsHandler knows when the library's device copies of zk and Xind are the caller's
@@ -123,6 +133,25 @@ function [S, out] = mpcekf_session(op, name, value)
           mpcekf_mex('chargerend', P.h);
         case 'stepexcharger'
           [o.u, o.v, o.soc, o.phise, o.nexec, o.ucmd, o.limiter, o.bal, o.chg] = mpcekf_mex('stepexcharger', P.h, name);
+          out = o;
+      end
+    case {'limitmap', 'limitmapget', 'limitmapend', 'stepexmap'}
+      if isempty(P.h), error('mpcekf_session: %s before the first OB_step call created the context', op); end
+      switch op
+        case 'limitmap'
+          m = name;
+          opt = {'T_lo', 'T_hi', 'interp', 'sets', 'z0'};
+          for k = 1:numel(opt)
+            if ~isfield(m, opt{k}), m.(opt{k}) = []; end
+          end
+          mpcekf_mex('limitmap', P.h, m.idx, m.z_lo, m.z_hi, m.T_lo, m.T_hi, m.tables, m.interp, m.sets, m.z0);
+        case 'limitmapget'
+          out = mpcekf_mex('limitmapget', P.h);
+        case 'limitmapend'
+          mpcekf_mex('limitmapend', P.h);
+        case 'stepexmap'
+          [o.u, o.v, o.soc, o.phise, o.nexec, lim] = mpcekf_mex('stepexmap', P.h, name);
+          o.lim = reshape(lim, size(lim, 1), size(lim, 2) / max(name, 1), name);   % explicit: [] cannot be inferred when nsteps = 0
           out = o;
       end
     otherwise

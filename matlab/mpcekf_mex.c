@@ -81,6 +81,22 @@
  *                       (j, s) = field idx(j) of derating map s over the grid; sets: [] (map 1) or
  *                       ncells 1-based map numbers.  'getlimits' then returns the values in force
  *                       mpcekf_mex('thermalscheduleend', h)            mpcekf_thermal_schedule_end
+ *                       mpcekf_mex('limitmap', h, idx, z_lo, z_hi, T_lo, T_hi, tables, interp, sets, z0)   mpcekf_limit_map
+ *                       MPC limits that follow each cell's SOC estimate and temperature.  idx: as
+ *                       'thermalschedule'; z_lo < z_hi: the SOC grid's ends (fractions); T_lo < T_hi:
+ *                       the temperature grid's ends (degC; [] without a temperature axis); tables:
+ *                       nz x nt x numel(idx) x nsets (trailing dimensions may be folded), entry
+ *                       (jz, jt, j, s) = field idx(j) of map s at SOC node jz and temperature node
+ *                       jt; nt >= 2 needs 'thermalbegin'; interp: 0 / [] linear in SOC, 1 hold (the
+ *                       left node's value); sets: [] (map 1) or ncells 1-based map numbers; z0: []
+ *                       or ncells SOC fractions to evaluate at before the first fused step
+ *   s                 = mpcekf_mex('limitmapget', h)                   mpcekf_limit_map_get
+ *                       struct of ncells x 1 column vectors: z_last, neval, nclamp_z, nclamp_t (MPCEKF_LM_*)
+ *                       mpcekf_mex('limitmapend', h)                   mpcekf_limit_map_end
+ *   [u,v,soc,phise,nexec,lim] = mpcekf_mex('stepexmap', h, nsteps[, tc])   mpcekf_step_ex_map
+ *                       'step' on a context with a limit map, plus the mapped fields' values the
+ *                       MPC stage of every step read, ncells x (numel(idx)*nsteps),
+ *                       column (j, t) = field idx(j) at step t
  *                       mpcekf_mex('thermalcouple', h, r_link)         mpcekf_thermal_couple
  *                       heat conduction between neighbouring cells of a pack string (needs
  *                       'thermalbegin' and 'packbegin'): r_link, ncells resistances (K/W, Inf: no
@@ -186,6 +202,7 @@ static void chk(int rc) {
 static mpcekf_ctx *g_live[MAXCTX];
 static int32_t g_series[MAXCTX]; /* 'packbegin's series of g_live[i] (0: no pack): sizes 'stepexpack's limiter */
 static int32_t g_agrows[MAXCTX]; /* 'agingbegin's nsrc * nreact of g_live[i] (0: none): sizes 'stepexaging's rate */
+static int32_t g_mapnf[MAXCTX];  /* 'limitmap's numel(idx) of g_live[i] (0: none): sizes 'stepexmap's lim */
 
 static void track(mpcekf_ctx *h, int add) {
   for (int i = 0; i < MAXCTX; ++i)
@@ -193,6 +210,7 @@ static void track(mpcekf_ctx *h, int add) {
       g_live[i] = add ? h : NULL;
       g_series[i] = 0;
       g_agrows[i] = 0;
+      g_mapnf[i] = 0;
       return;
     }
 }
@@ -205,6 +223,7 @@ static void destroy_all(void) {
       g_live[i] = NULL;
       g_series[i] = 0;
       g_agrows[i] = 0;
+      g_mapnf[i] = 0;
     }
 }
 
@@ -217,6 +236,12 @@ static int32_t *series_of(mpcekf_ctx *h) {
 static int32_t *agrows_of(mpcekf_ctx *h) {
   for (int i = 0; i < MAXCTX; ++i)
     if (g_live[i] == h) return &g_agrows[i];
+  return NULL;
+}
+
+static int32_t *mapnf_of(mpcekf_ctx *h) {
+  for (int i = 0; i < MAXCTX; ++i)
+    if (g_live[i] == h) return &g_mapnf[i];
   return NULL;
 }
 
@@ -492,6 +517,7 @@ static void gateway(mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
                                             "clearlimits", "summarybegin", "stepsummary", "getsummary", "summaryend",
                                             "thermalbegin", "thermalget", "thermalend", "stepthermal",
                                             "thermalschedule", "thermalscheduleend",
+                                            "limitmap", "limitmapget", "limitmapend", "stepexmap",
                                             "thermalcouple", "thermalcoupleget", "thermalcoupleend", "stepexcouple",
                                             "packbegin", "packget", "packend", "stepexpack",
                                             "agingbegin", "agingget", "agingend", "stepexaging",
@@ -635,6 +661,70 @@ static void gateway(mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         if (!(sd[j] >= 1 && sd[j] <= (double)schsets) || sd[j] != (double)(int32_t)sd[j])
           mexErrMsgIdAndTxt("mpcekf:arg", "thermalschedule: sets(%zu) = %g is not a map 1..%zu", j + 1, sd[j], schsets);
     }
+  }
+  /* the limit map's commands likewise: output count, field numbers among the mappable ones, each
+     once, grid ends that are real scalars, tables of whole maps, an interp that is 0 or 1, set
+     numbers that are 1-based integers, an nsteps that is no non-negative integer */
+  const int lmset = !strcmp(cmd, "limitmap"), steplm = !strcmp(cmd, "stepexmap");
+  int32_t lmf[MPCEKF_NLIM], lmsteps = 0, lminterp = 0;
+  size_t nlmf = 0, lmnz = 0, lmnt = 0, lmsets = 0;
+  double lm_zlo = 0, lm_zhi = 0, lm_tlo = 0, lm_thi = 1;
+  if ((lmset || !strcmp(cmd, "limitmapend")) && g_nlhs > 0) mexErrMsgIdAndTxt("mpcekf:arg", "%s: no output", cmd);
+  if (!strcmp(cmd, "limitmapget") && g_nlhs > 1) mexErrMsgIdAndTxt("mpcekf:arg", "limitmapget: at most 1 output");
+  if (steplm && g_nlhs > 6) mexErrMsgIdAndTxt("mpcekf:arg", "stepexmap: at most 6 outputs [u, v, soc, phise, nexec, lim]");
+  if (lmset) {
+    need(nrhs, 8, "'limitmap', h, idx, z_lo, z_hi, T_lo, T_hi, tables[, interp[, sets[, z0]]]");
+    nlmf = mxGetNumberOfElements(prhs[2]);
+    if (nlmf < 1 || nlmf > 6) mexErrMsgIdAndTxt("mpcekf:arg", "limitmap: idx: expected 1..6 field numbers");
+    const double *idx = dvec(prhs[2], nlmf, "idx");
+    unsigned seen = 0;
+    for (size_t j = 0; j < nlmf; ++j) {
+      if (!(idx[j] >= MPCEKF_LIM_CRATE + 1 && idx[j] <= MPCEKF_LIM_PHISE_MIN + 1) || idx[j] != (double)(int)idx[j])
+        mexErrMsgIdAndTxt("mpcekf:arg", "limitmap: idx(%zu) = %g is not a field that can be mapped (%d..%d)", j + 1, idx[j],
+                          (int)MPCEKF_LIM_CRATE + 1, (int)MPCEKF_LIM_PHISE_MIN + 1);
+      lmf[j] = (int32_t)idx[j] - 1;
+      if (seen >> lmf[j] & 1) mexErrMsgIdAndTxt("mpcekf:arg", "limitmap: idx(%zu) = %g is given twice", j + 1, idx[j]);
+      seen |= 1u << lmf[j];
+    }
+    lm_zlo = scalar(prhs[3], "limitmap: z_lo");
+    lm_zhi = scalar(prhs[4], "limitmap: z_hi");
+    if (!mxIsDouble(prhs[7]) || mxIsComplex(prhs[7]) || mxIsEmpty(prhs[7]))
+      mexErrMsgIdAndTxt("mpcekf:arg", "limitmap: tables: expected a real double nz x nt x %zu x nsets array", nlmf);
+    lmnz = mxGetM(prhs[7]);
+    lmnt = mxGetNumberOfDimensions(prhs[7]) >= 2 ? mxGetDimensions(prhs[7])[1] : 1;
+    const size_t rest = mxGetNumberOfElements(prhs[7]) / (lmnz * lmnt);
+    if (lmnz > 2147483647.0 || lmnt > 2147483647.0 || (lmnz == 1 && lmnt == 1) || rest % nlmf != 0 ||
+        rest / nlmf > 2147483647.0)
+      mexErrMsgIdAndTxt("mpcekf:arg", "limitmap: tables: %zu x %zu x %zu: expected 2 or more nodes on one axis and %zu "
+                        "tables per map", lmnz, lmnt, rest, nlmf);
+    lmsets = rest / nlmf;
+    if (lmnt > 1 || !mxIsEmpty(prhs[5])) lm_tlo = scalar(prhs[5], "limitmap: T_lo");
+    if (lmnt > 1 || !mxIsEmpty(prhs[6])) lm_thi = scalar(prhs[6], "limitmap: T_hi");
+    if (nrhs > 8 && !mxIsEmpty(prhs[8])) {
+      const double d = scalar(prhs[8], "limitmap: interp");
+      if (d != 0 && d != 1) mexErrMsgIdAndTxt("mpcekf:arg", "limitmap: interp = %g: 0 (linear) or 1 (hold)", d);
+      lminterp = (int32_t)d;
+    }
+    if (nrhs > 9 && !mxIsEmpty(prhs[9])) {
+      if (!mxIsDouble(prhs[9]) || mxIsComplex(prhs[9]))
+        mexErrMsgIdAndTxt("mpcekf:arg", "limitmap: sets: expected [] or ncells real doubles");
+      const size_t k = mxGetNumberOfElements(prhs[9]);
+      const double *sd = mxGetDoubles(prhs[9]);
+      for (size_t j = 0; j < k; ++j)
+        if (!(sd[j] >= 1 && sd[j] <= (double)lmsets) || sd[j] != (double)(int32_t)sd[j])
+          mexErrMsgIdAndTxt("mpcekf:arg", "limitmap: sets(%zu) = %g is not a map 1..%zu", j + 1, sd[j], lmsets);
+    }
+    if (nrhs > 10 && !mxIsEmpty(prhs[10]) && (!mxIsDouble(prhs[10]) || mxIsComplex(prhs[10])))
+      mexErrMsgIdAndTxt("mpcekf:arg", "limitmap: z0: expected [] or ncells real doubles");
+  }
+  if (steplm) {
+    need(nrhs, 3, "'stepexmap', h, nsteps[, tc]");
+    const double nsd = scalar(prhs[2], "nsteps");
+    if (!(nsd >= 0 && nsd <= 2147483647.0) || nsd != (double)(int32_t)nsd)
+      mexErrMsgIdAndTxt("mpcekf:arg", "nsteps: expected a non-negative integer");
+    lmsteps = (int32_t)nsd;
+    if (nrhs > 3 && !mxIsEmpty(prhs[3]) && (!mxIsDouble(prhs[3]) || mxIsComplex(prhs[3])))
+      mexErrMsgIdAndTxt("mpcekf:arg", "stepexmap: tc: expected [] or ncells x nsteps real doubles");
   }
   /* the coupling commands likewise: output count, the links' class, an nsteps that is no
      non-negative integer */
@@ -1001,6 +1091,11 @@ static void gateway(mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
     mxFree(vals);
   } else if (!strcmp(cmd, "thermalend")) {
     chk(mpcekf_thermal_end(h));
+    /* a map with a temperature axis ended with the model: a refused one-field get changes nothing */
+    int32_t id0 = 0;
+    double *probe = (double *)mxMalloc(nc * sizeof(double) + 8);
+    if (mpcekf_limit_map_get(h, 1, &id0, probe) != MPCEKF_OK) *mapnf_of(h) = 0;
+    mxFree(probe);
   } else if (stepth) {
     for (int i = 0; i < 7; ++i) plhs[i] = i == 4 ? imat(nc, (size_t)thsteps) : dmat(nc, (size_t)thsteps);
     mpcekf_traj tr;
@@ -1022,6 +1117,49 @@ static void gateway(mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
     chk(rc);
   } else if (!strcmp(cmd, "thermalscheduleend")) {
     chk(mpcekf_thermal_schedule_end(h));
+  } else if (lmset) {
+    /* nz x nt x numel(idx) x nsets column-major is the library's [nsets][nfields][nt][nz] as it stands */
+    int32_t *set = NULL;
+    if (nrhs > 9 && !mxIsEmpty(prhs[9])) {
+      const double *sd = dvec(prhs[9], nc, "limitmap: sets (ncells)");
+      set = (int32_t *)mxMalloc(nc * sizeof(int32_t) + 8);
+      for (size_t c = 0; c < nc; ++c) set[c] = (int32_t)sd[c] - 1;
+    }
+    const double *z0 = nrhs > 10 ? opt_vec(prhs[10], nc, "limitmap: z0 (ncells)") : NULL;
+    const int rc = mpcekf_limit_map(h, (int32_t)nlmf, lmf, (int32_t)lmnz, lm_zlo, lm_zhi, (int32_t)lmnt, lm_tlo, lm_thi,
+                                    lminterp, (int32_t)lmsets, mxGetDoubles(prhs[7]), set, z0);
+    if (set) mxFree(set);
+    chk(rc);
+    *mapnf_of(h) = (int32_t)nlmf;
+  } else if (!strcmp(cmd, "limitmapget")) {
+    static const char *const lm_names[MPCEKF_NLM] = {"z_last", "neval", "nclamp_z", "nclamp_t"};
+    int32_t ids[MPCEKF_NLM];
+    double *vals = (double *)mxMalloc((size_t)MPCEKF_NLM * nc * sizeof(double) + 8);
+    for (int f = 0; f < MPCEKF_NLM; ++f) ids[f] = f;
+    chk(mpcekf_limit_map_get(h, MPCEKF_NLM, ids, vals));
+    plhs[0] = mxCreateStructMatrix(1, 1, MPCEKF_NLM, (const char **)lm_names);
+    for (int f = 0; f < MPCEKF_NLM; ++f) {
+      mxArray *a = dmat(nc, 1);
+      if (nc) memcpy(mxGetDoubles(a), vals + (size_t)f * nc, nc * sizeof(double));
+      mxSetField(plhs[0], 0, lm_names[f], a);
+    }
+    mxFree(vals);
+  } else if (!strcmp(cmd, "limitmapend")) {
+    chk(mpcekf_limit_map_end(h));
+    *mapnf_of(h) = 0;
+  } else if (steplm) {
+    /* without a 'limitmap' the library refuses the call before it touches a row; lim is
+       ncells x (numel(idx) * nsteps): column (j, t) = field idx(j) at step t */
+    const size_t nf = (size_t)*mapnf_of(h);
+    const double *tc = nrhs > 3 ? opt_vec(prhs[3], nc * (size_t)lmsteps, "stepexmap: tc (ncells x nsteps)") : NULL;
+    for (int i = 0; i < 5; ++i) plhs[i] = i == 4 ? imat(nc, (size_t)lmsteps) : dmat(nc, (size_t)lmsteps);
+    plhs[5] = dmat(nc, (nf ? nf : 1) * (size_t)lmsteps);
+    mpcekf_traj tr;
+    memset(&tr, 0, sizeof tr);
+    tr.u = mxGetDoubles(plhs[0]); tr.v = mxGetDoubles(plhs[1]); tr.soc = mxGetDoubles(plhs[2]);
+    tr.phise = mxGetDoubles(plhs[3]); tr.nexec = (int32_t *)mxGetData(plhs[4]);
+    chk(mpcekf_step_ex_map(h, lmsteps, tc, &tr, NULL, 0, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL,
+                           mxGetDoubles(plhs[5]), 0));
   } else if (tcset) {
     chk(mpcekf_thermal_couple(h, dvec(prhs[2], nc, "thermalcouple: r_link (ncells)")));
   } else if (!strcmp(cmd, "thermalcoupleget")) {

@@ -12,7 +12,7 @@ __all__ = ["ROM", "make_synth_rom", "mpcekf"]
 
 def __getattr__(name):
     # the ctypes layer loads libmpcekf.so lazily so that `import` works before build()
-    if name in ("mpcekf", "Context", "runMPC", "run_summary", "thermal_ocv", "predMat", "hildreth", "constraintsMPC", "make_config"):
+    if name in ("mpcekf", "Context", "runMPC", "run_summary", "thermal_ocv", "mscc_map", "predMat", "hildreth", "constraintsMPC", "make_config"):
         from . import mpcekf as _m
         return _m if name == "mpcekf" else getattr(_m, name)
     raise AttributeError(name)

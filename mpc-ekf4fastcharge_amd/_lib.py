@@ -34,6 +34,8 @@ SUM_WIN = 64     # MPCEKF_SUM_WIN
 THERMAL_PARAMS = ("Cth", "Rth", "Tamb")
 # the limit fields mpcekf_thermal_schedule takes (the ones whose kernel slot is one number)
 SCHEDULE_FIELDS = ("Crate", "u_max", "du_min", "du_max", "v_max", "phise_min")
+# MPCEKF_LM_*: the limit map's per-cell record (mpcekf_limit_map_get)
+LIMIT_MAP_FIELDS = ("z_last", "neval", "nclamp_z", "nclamp_t")
 THERMAL_FIELDS = ("T", "T_max", "T_max_step", "T_min", "heat_sum", "steps", "nheld")
 # MPCEKF_PK_*: the series strings' per-cell record (mpcekf_pack_begin / _get)
 PACK_FIELDS = ("nlim", "steps", "headroom")
@@ -119,6 +121,7 @@ EXPORTS = [
     "mpcekf_pack_begin", "mpcekf_pack_get", "mpcekf_pack_end", "mpcekf_step_ex_pack",
     "mpcekf_aging_begin", "mpcekf_aging_get", "mpcekf_aging_end", "mpcekf_step_ex_aging",
     "mpcekf_thermal_schedule", "mpcekf_thermal_schedule_end",
+    "mpcekf_limit_map", "mpcekf_limit_map_get", "mpcekf_limit_map_end", "mpcekf_step_ex_map",
     "mpcekf_term_begin", "mpcekf_term_get", "mpcekf_term_open", "mpcekf_term_end", "mpcekf_step_until",
     "mpcekf_balance_begin", "mpcekf_balance_get", "mpcekf_balance_end", "mpcekf_step_ex_balance",
     "mpcekf_charger_begin", "mpcekf_charger_get", "mpcekf_charger_end", "mpcekf_step_ex_charger",
@@ -201,6 +204,12 @@ def load():
     L.mpcekf_thermal_end.argtypes = [vp]
     L.mpcekf_thermal_schedule.argtypes = [vp, C.c_int32, _ip, C.c_int32, C.c_double, C.c_double, C.c_int32, _dp, _ip]
     L.mpcekf_thermal_schedule_end.argtypes = [vp]
+    L.mpcekf_limit_map.argtypes = [vp, C.c_int32, _ip, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_double,
+                                   C.c_double, C.c_int32, C.c_int32, _dp, _ip, _dp]
+    L.mpcekf_limit_map_get.argtypes = [vp, C.c_int32, _ip, _dp]
+    L.mpcekf_limit_map_end.argtypes = [vp]
+    L.mpcekf_step_ex_map.argtypes = [vp, C.c_int32, vp, C.POINTER(Traj), _ip, C.c_int32, vp, vp, vp, vp, vp, vp, vp,
+                                     vp, vp, vp, vp, C.c_int32]
     L.mpcekf_step_ex_thermal.argtypes = [vp, C.c_int32, C.POINTER(Traj), _ip, C.c_int32, vp, vp, vp, C.c_int32]
     L.mpcekf_pack_begin.argtypes = [vp, C.c_int32]
     L.mpcekf_pack_get.argtypes = [vp, C.c_int32, _ip, _dp]

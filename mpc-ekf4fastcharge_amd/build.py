@@ -23,11 +23,11 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 CFLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", f"--offload-arch={ARCH}",
           "-Wno-unused-result", "-mllvm", "-pragma-unroll-threshold=200000"]
 SOURCES = ["mpcekf_kernels.hip", "mpcekf_switch.hip", "mpcekf_wide.hip", "mpcekf_io.hip", "mpcekf_summary.hip",
-           "mpcekf_thermal.hip", "mpcekf_thermal_sched.hip", "mpcekf_thermal_couple.hip", "mpcekf_pack.hip",
+           "mpcekf_thermal.hip", "mpcekf_thermal_sched.hip", "mpcekf_limit_map.hip", "mpcekf_thermal_couple.hip", "mpcekf_pack.hip",
            "mpcekf_aging.hip", "mpcekf_term.hip", "mpcekf_balance.hip", "mpcekf_charger.hip",
            "mpcekf_host.cpp"]
 DEPS = ["mpcekf_kernels.hpp", "mpcekf_mpc.hpp", "mpcekf_hild.hpp", "mpcekf_eig.hpp", "mpcekf_summary.hpp",
-        "mpcekf_thermal.hpp", "mpcekf_thermal_sched.hpp", "mpcekf_thermal_couple.hpp", "mpcekf_pack.hpp", "mpcekf_aging.hpp", "mpcekf_term.hpp", "mpcekf_balance.hpp", "mpcekf_charger.hpp", "mpcekf_dexp.hpp", "mpcekf_mpc_sw.inc", "mpcekf_mpc_wide.inc", "mpcekf_cl_diag.inc",
+        "mpcekf_thermal.hpp", "mpcekf_thermal_sched.hpp", "mpcekf_limit_map.hpp", "mpcekf_thermal_couple.hpp", "mpcekf_pack.hpp", "mpcekf_aging.hpp", "mpcekf_term.hpp", "mpcekf_balance.hpp", "mpcekf_charger.hpp", "mpcekf_dexp.hpp", "mpcekf_mpc_sw.inc", "mpcekf_mpc_wide.inc", "mpcekf_cl_diag.inc",
         os.path.join("..", "..", "include", "mpcekf.h")]
 
 

@@ -34,6 +34,7 @@
 #include "mpcekf_summary.hpp"
 #include "mpcekf_thermal.hpp"
 #include "mpcekf_thermal_sched.hpp"
+#include "mpcekf_limit_map.hpp"
 #include "mpcekf_thermal_couple.hpp"
 
 using namespace mk;
@@ -196,6 +197,7 @@ enum {
   F_COND,                                  // k_thermal_couple's
   F_BLEED, F_ZMIN,                         // k_pack_bal's
   F_VSTR, F_ISTR, F_CAPBY,                 // k_charger's
+  F_LIM,                                   // the limit map's kernels'
   NF
 };
 
@@ -222,6 +224,7 @@ struct GraphParts {
   struct { W rec, par, on, comp, soc; } balance;
   struct { W rec, par; } charger;
   struct { W hdr, tab; } sched;                // mpcekf_thermal_schedule may regrow the tables
+  struct { W rec, tab, soc, nf; } map;         // mpcekf_limit_map may regrow the tables; nf: the lim rows' length
   struct { W ocv, nocv, rec; } thermal;
   struct { W reach, rec; } summary;
 };
@@ -291,7 +294,8 @@ struct mpcekf_ctx {
   // kernels' record, allocated by the first set and kept to the end (a captured graph may name
   // it).  percell: the MPC stages launch the per-cell kernel variants
   // lim_set: a mpcekf_set_limits is in force; a temperature schedule (sched, below) keeps the
-  // context on the per-cell sequence too: percell = lim_set || sched
+  // context on the per-cell sequence too, and so does a limit map (lmap): percell = lim_set ||
+  // sched || lmap
   std::vector<double> h_lim;
   double *d_lim = nullptr;
   bool percell = false, lim_set = false;
@@ -333,6 +337,35 @@ struct mpcekf_ctx {
     g.Tc = s.Tc;
     g.lim = d_lim;
     g.val = d_sch_val;
+    g.n = n;
+    return g;
+  }
+  // mpcekf_limit_map .. _map_end: the header, each cell's table set [n], the values in force
+  // [MAP_MAXF][n], the record [NLMR][n] and the soc row the map's kernels read when the call has
+  // none of its own (and no other extension's stands in) are allocated once; the tables
+  // [nsets][nf][nt][nz] grow on demand (lm_cap doubles).  lmap: every fused call evaluates the map
+  // (h_lm: the header's host copy, row i of d_lm_val = field h_lm_field[i])
+  MapHdr *d_lm_hdr = nullptr;
+  double *d_lm_tab = nullptr, *d_lm_val = nullptr, *d_lm = nullptr, *d_lm_soc = nullptr;
+  int *d_lm_set = nullptr;
+  size_t lm_cap = 0;
+  bool lmap = false;
+  MapHdr h_lm{};
+  int32_t h_lm_field[MAP_MAXF] = {};
+  int map_row(int field) const {  // the row of a mapped field, -1: not mapped
+    for (int i = 0; lmap && i < h_lm.nf; ++i)
+      if (h_lm_field[i] == field) return i;
+    return -1;
+  }
+  KMap kmap() const {
+    KMap g{};
+    g.hdr = d_lm_hdr;
+    g.tab = d_lm_tab;
+    g.set = d_lm_set;
+    g.Tc = s.Tc;
+    g.lim = d_lim;
+    g.val = d_lm_val;
+    g.rec = d_lm;
     g.n = n;
     return g;
   }
@@ -1299,7 +1332,7 @@ int mpcekf_ctx_destroy(mpcekf_ctx *X) {
                   X->d_zbk,       X->d_tmp,        X->s.bigx, X->s.ekf,   X->s.lam,   X->d_ts, X->d_hist, X->d_stamps, X->d_bnd, X->d_xm, X->d_xg,
                   X->w.prob, X->w.X, X->w.R, X->w.K, X->w.hii, X->w.it, X->w.smin, X->d_lin, X->d_zsoc, X->d_mb, X->d_uk1p,
                   X->w.q, X->w.list, X->w.hist, X->d_poly, X->d_szk, X->d_sxg, X->d_sxm, X->d_slin, X->d_sv, X->d_zslot,
-                  X->d_obs_blob, X->d_obs, X->d_obs_plan, X->d_lim, X->d_sch_hdr, X->d_sch_tab, X->d_sch_val, X->d_sch_set, X->d_sum, X->d_sum_reach, X->d_sum_obs,
+                  X->d_obs_blob, X->d_obs, X->d_obs_plan, X->d_lim, X->d_sch_hdr, X->d_sch_tab, X->d_sch_val, X->d_sch_set, X->d_lm_hdr, X->d_lm_tab, X->d_lm_val, X->d_lm_set, X->d_lm, X->d_lm_soc, X->d_sum, X->d_sum_reach, X->d_sum_obs,
                   X->d_sum_ring, X->d_pk, X->d_tc, X->d_tc_link, X->d_tc_snap, X->d_ag, X->d_ag_par, X->d_ag_phi, X->d_ag_obs, X->d_ag_plan, X->d_tm, X->d_tm_par, X->d_tm_soc, X->d_tm_int, X->d_bl, X->d_bl_par, X->d_bl_soc, X->d_bl_on, X->d_ch, X->d_ch_par, X->d_th, X->d_th_par, X->d_th_i, X->d_th_ocv, X->d_hot, X->d_hot_i, X->d_hotp, X->d_hotp_i};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
@@ -1412,6 +1445,7 @@ struct StepOut {
   int32_t *limiter = nullptr;
   double *rate = nullptr, *cond = nullptr, *bleed = nullptr, *zmin = nullptr, *vstr = nullptr, *istr = nullptr;
   int32_t *capby = nullptr;
+  double *lim = nullptr;  // [nsteps][nf][ncells] of the map in force
 };
 
 // runMPC.m:84-111, nsteps times: OB_step -> (all-model advance + EKF time
@@ -1452,6 +1486,11 @@ struct StepOut {
 // and k_thermal_couple(_sched) in k_thermal(_sched)'s place reads each cell's neighbours from
 // the snapshot of the step's parity; cond [nsteps][ncells] (mpcekf_step_ex_couple) is one more
 // output field, written by that kernel.
+// A mapped context (mpcekf_limit_map): k_map once before the call's first step; every step ends
+// with k_thermal_map in k_thermal's place (a model), k_map_step after k_thermal_couple (links) or
+// k_map_step alone (no model), which reads the step's soc row (the context's own when the call has
+// none); lim [nsteps][nf][ncells] (mpcekf_step_ex_map) is one more output field: step k's block is
+// written by the launch that evaluated the values step k reads.
 static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const mpcekf_traj *tr,
                      const int32_t *slots, int32_t nslots, double *obs, int32_t outputs_on_device,
                      const StepOut &o = StepOut()) {
@@ -1522,7 +1561,8 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
            // a charger context's only
            {o.vstr, 8, 1, nullptr, nstr},
            {o.istr, 8, 1, nullptr, nstr},
-           {o.capby, 4, 1, nullptr, nstr}};
+           {o.capby, 4, 1, nullptr, nstr},
+           {o.lim, 8, X->lmap ? (size_t)X->h_lm.nf : 0, nullptr}};  // a mapped context's only
   static_assert(sizeof(f) / sizeof(F) == NF, "f[] has one entry per F_* name, in that order");
   auto step_bytes = [&](const F &e) -> size_t { return (e.rows ? e.rows : n) * e.width * e.esz; };  // one step's block
   const double *dtc = tc_degC;  // [nsteps][n] device copy of the per-step temperatures
@@ -1633,10 +1673,21 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
   std::vector<char> bounded((size_t)nsteps, 0);  // the steps that launched k_bounds
   const bool sched = thermal && X->sched;
   const KSched ksch = X->ksched();
+  const bool lmap = X->lmap;
+  auto kmap_of = [&](int k_for, const double *soc, bool eval) {  // the evaluation whose values step k_for reads
+    KMap g = X->kmap();
+    g.soc = soc;
+    g.eval = eval;
+    g.count = 1;
+    g.out = eval && k_for < nsteps ? (double *)row(F_LIM, k_for) : nullptr;
+    return g;
+  };
   auto run_steps = [&]() -> int {
     // the schedule at the temperature the call's first step finds (mpcekf_thermal_sched.hip);
     // before the first timing event, so no slot of mpcekf_set_timing counts it
     if (sched && nsteps > 0 && (rc = lerr(launch_sched(ksch, X->stream), "sched"))) return rc;
+    // the map at Z_LAST and the temperature the call's first step finds (mpcekf_limit_map.hip)
+    if (lmap && nsteps > 0 && (rc = lerr(launch_map(kmap_of(0, nullptr, true), X->stream), "map"))) return rc;
     // the temperatures the call's first step finds, for its neighbours (mpcekf_thermal_couple.hip)
     if (coupled && nsteps > 0 && (rc = lerr(launch_couple_seed(X->s.Tc, X->d_tc_snap, X->n, X->stream), "couple_seed")))
       return rc;
@@ -1688,6 +1739,7 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
       if (ag_est && !io.phise) io.phise = X->d_ag_phi;  // k_aging's input when the call asks for no phise row
       if (term && !io.soc) io.soc = X->d_tm_soc;         // k_term's input when the call asks for no soc row
       if (balance && !io.soc) io.soc = X->d_bl_soc;      // k_pack_bal's likewise
+      if (lmap && !io.soc) io.soc = X->d_lm_soc;         // the map's kernels' likewise
       io.nexec = (int *)row(F_NEXEC, k);
       io.x_out = (double *)row(F_X, k);
       const bool last = k == nsteps - 1;
@@ -1919,11 +1971,19 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
           rc = sched && k + 1 < nsteps ? lerr(launch_thermal_couple_sched(q, h, ksch, X->stream), "thermal_couple_sched")
                                        : lerr(launch_thermal_couple(q, h, X->stream), "thermal_couple");
           if (rc) return rc;
+          // a map: Z_LAST, and the next step's limits at the temperature the launch above left
+          if (lmap && (rc = lerr(launch_map_step(kmap_of(k + 1, io.soc, k + 1 < nsteps), X->stream), "map_step")))
+            return rc;
+        } else if (lmap) {  // the model's step, Z_LAST, and the next step's limits in one launch
+          if ((rc = lerr(launch_thermal_map(q, kmap_of(k + 1, io.soc, k + 1 < nsteps), X->stream), "thermal_map")))
+            return rc;
         } else if (sched && k + 1 < nsteps) {
           if ((rc = lerr(launch_thermal_sched(q, ksch, X->stream), "thermal_sched"))) return rc;
         } else if ((rc = lerr(launch_thermal(q, X->stream), "thermal"))) {
           return rc;
         }
+      } else if (lmap) {  // no model: Z_LAST and the next step's limits, the step's last launch
+        if ((rc = lerr(launch_map_step(kmap_of(k + 1, io.soc, k + 1 < nsteps), X->stream), "map_step"))) return rc;
       }
     }
     return MPCEKF_OK;
@@ -1954,6 +2014,8 @@ static int step_impl(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const
     if (balance) p.balance = {(W)X->d_bl, (W)X->d_bl_par, (W)X->d_bl_on, (W)X->bl_comp, (W)X->d_bl_soc};
     if (charger) p.charger = {(W)X->d_ch, (W)X->d_ch_par};
     if (sched) p.sched = {(W)X->d_sch_hdr, (W)X->d_sch_tab};  // the schedule's launches are part of the graph
+    // and so are the map's; the launches hold the lim rows' stride, nf blocks of ncells per step
+    if (lmap) p.map = {(W)X->d_lm, (W)X->d_lm_tab, (W)X->d_lm_soc, (W)X->h_lm.nf};
     p.thermal = {(W)X->d_th_ocv, (W)X->th_nocv, (W)X->d_th};
     if (sum) p.summary = {(W)X->d_sum_reach, (W)X->d_sum};  // the fold's launches are part of the graph
     if ((rc = X->graph_launch(key, run_steps))) return rc;
@@ -2097,6 +2159,8 @@ static int limits_upload(mpcekf_ctx *X) {
   // on the context's stream, after every launch already queued; the wait makes rec's lifetime safe
   if (n) HIPCHK(hipMemcpyAsync(X->d_lim, rec.data(), rec.size() * 8, hipMemcpyHostToDevice, X->stream));
   if (X->sched && (rc = lerr(launch_sched(X->ksched(), X->stream), "sched"))) return rc;
+  // a map likewise, at Z_LAST and the temperature as they stand; not an evaluation of a fused step
+  if (X->lmap && (rc = lerr(launch_map(X->kmap(), X->stream), "map"))) return rc;
   HIPCHK(hipStreamSynchronize(X->stream));
   return MPCEKF_OK;
 }
@@ -2109,6 +2173,10 @@ int mpcekf_set_limits(mpcekf_ctx *X, int32_t nfields, const int32_t *fields, con
   for (int i = 0; i < nfields; ++i)
     if (X->sched_row(fields[i]) >= 0)
       return fail(MPCEKF_E_ARG, "set_limits: fields[%d] = %d is scheduled over temperature (mpcekf_thermal_schedule)", i,
+                  fields[i]);
+  for (int i = 0; i < nfields; ++i)
+    if (X->map_row(fields[i]) >= 0)
+      return fail(MPCEKF_E_ARG, "set_limits: fields[%d] = %d is mapped over SOC and temperature (mpcekf_limit_map)", i,
                   fields[i]);
   // check_cfg puts no condition on the scalar form of any of these fields, so none is put on
   // an element either (a negative du_max is a legitimate configuration)
@@ -2129,10 +2197,11 @@ int mpcekf_get_limits(mpcekf_ctx *X, int32_t nfields, const int32_t *fields, dou
   const size_t n = (size_t)X->n;
   bool wait = false;
   for (int i = 0; i < nfields; ++i) {
-    const int row = X->sched_row(fields[i]);
-    if (row >= 0) {  // a scheduled field: the value of the last evaluation, kept on the device
+    const int row = X->sched_row(fields[i]), mrow = X->map_row(fields[i]);
+    if (row >= 0 || mrow >= 0) {  // a scheduled or mapped field: the value of the last evaluation, kept on the device
+      const double *src = row >= 0 ? X->d_sch_val + (size_t)row * n : X->d_lm_val + (size_t)mrow * n;
       if (!wait) HIPCHK(hipSetDevice(X->device));
-      if (n) HIPCHK(hipMemcpyAsync(values + (size_t)i * n, X->d_sch_val + (size_t)row * n, n * 8, hipMemcpyDeviceToHost, X->stream));
+      if (n) HIPCHK(hipMemcpyAsync(values + (size_t)i * n, src, n * 8, hipMemcpyDeviceToHost, X->stream));
       wait = true;
     } else if (X->percell) {
       std::copy_n(X->h_lim.begin() + (size_t)fields[i] * n, n, values + (size_t)i * n);
@@ -2148,6 +2217,7 @@ int mpcekf_clear_limits(mpcekf_ctx *X) {
   if (!X) return fail(MPCEKF_E_ARG, "clear_limits: null ctx");
   if (X->sched)
     return fail(MPCEKF_E_STATE, "clear_limits: a temperature schedule is active (mpcekf_thermal_schedule_end first)");
+  if (X->lmap) return fail(MPCEKF_E_STATE, "clear_limits: a limit map is active (mpcekf_limit_map_end first)");
   X->percell = X->lim_set = false;  // the buffers stay: a graph captured per-cell names d_lim until the context goes
   X->h_lim.clear();
   return MPCEKF_OK;
@@ -2333,6 +2403,7 @@ int mpcekf_thermal_end(mpcekf_ctx *X) {
   if (!X->d_th) return MPCEKF_OK;
   int rc = mpcekf_thermal_schedule_end(X);  // the scheduled fields back to set_limits' / the configuration's values
   if (rc) return rc;
+  if (X->lmap && X->h_lm.nt > 1 && (rc = mpcekf_limit_map_end(X))) return rc;  // a temperature axis needs a model
   if ((rc = mpcekf_thermal_couple_end(X))) return rc;  // links need a model
   HIPCHK(hipSetDevice(X->device));
   HIPCHK(hipStreamSynchronize(X->stream));
@@ -2387,6 +2458,7 @@ int mpcekf_thermal_schedule(mpcekf_ctx *X, int32_t nfields, const int32_t *field
     if (set_of_cell[c] < 0 || set_of_cell[c] >= nsets)
       return fail(MPCEKF_E_ARG, "thermal_schedule: set_of_cell[%zu] = %d outside 0..%d", c, set_of_cell[c], nsets - 1);
   if (!X->d_th) return fail(MPCEKF_E_STATE, "thermal_schedule: call mpcekf_thermal_begin first");
+  if (X->lmap) return fail(MPCEKF_E_STATE, "thermal_schedule: a limit map is active (mpcekf_limit_map_end first)");
   int rc;
   HIPCHK(hipSetDevice(X->device));
   const size_t n = std::max<size_t>(nc, 1);
@@ -2435,6 +2507,160 @@ int mpcekf_thermal_schedule_end(mpcekf_ctx *X) {
   X->percell = false;
   X->h_lim.clear();
   return MPCEKF_OK;
+}
+
+// ---- the MPC limits mapped over the SOC estimate and the temperature (mpcekf_limit_map.hip) ----
+static_assert(NLMR == MPCEKF_NLM && LM_Z_LAST == MPCEKF_LM_Z_LAST && LM_NEVAL == MPCEKF_LM_NEVAL &&
+                  LM_NCLAMP_Z == MPCEKF_LM_NCLAMP_Z && LM_NCLAMP_T == MPCEKF_LM_NCLAMP_T,
+              "mpcekf_limit_map.hpp's rows are include/mpcekf.h's MPCEKF_LM_*");
+
+int mpcekf_limit_map(mpcekf_ctx *X, int32_t nfields, const int32_t *fields, int32_t nz, double z_lo, double z_hi,
+                     int32_t nt, double T_lo_degC, double T_hi_degC, int32_t interp_z, int32_t nsets,
+                     const double *tables, const int32_t *set_of_cell, const double *z0) {
+  if (!X) return fail(MPCEKF_E_ARG, "limit_map: null ctx");
+  if (nfields < 1 || nfields > MAP_MAXF)
+    return fail(MPCEKF_E_ARG, "limit_map: nfields = %d outside 1..%d", nfields, (int)MAP_MAXF);
+  if (!fields) return fail(MPCEKF_E_ARG, "limit_map: null fields");
+  if (!tables) return fail(MPCEKF_E_ARG, "limit_map: null tables");
+  MapHdr h{};
+  unsigned seen = 0;
+  for (int i = 0; i < nfields; ++i) {
+    int slot;
+    switch (fields[i]) {
+      case MPCEKF_LIM_CRATE: slot = LK_U_MIN; break;
+      case MPCEKF_LIM_U_MAX: slot = LK_U_MAX; break;
+      case MPCEKF_LIM_DU_MIN: slot = LK_DU_MIN; break;
+      case MPCEKF_LIM_DU_MAX: slot = LK_DU_MAX; break;
+      case MPCEKF_LIM_V_MAX: slot = LK_V_MAX; break;
+      case MPCEKF_LIM_PHISE_MIN: slot = LK_PHISE_MIN; break;
+      default:
+        return fail(MPCEKF_E_ARG, "limit_map: fields[%d] = %d cannot be mapped (CRATE, U_MAX, DU_MIN, DU_MAX, V_MAX, "
+                    "PHISE_MIN can)", i, fields[i]);
+    }
+    if (seen >> fields[i] & 1) return fail(MPCEKF_E_ARG, "limit_map: fields: id %d given twice", fields[i]);
+    seen |= 1u << fields[i];
+    h.slot[i] = slot;
+    h.crate[i] = fields[i] == MPCEKF_LIM_CRATE;
+  }
+  if (nz < 1 || nt < 1 || (nz == 1 && nt == 1))
+    return fail(MPCEKF_E_ARG, "limit_map: nz = %d, nt = %d: 1 or more each, and 2 or more on one axis", nz, nt);
+  if (!std::isfinite(z_lo) || !std::isfinite(z_hi) || !(z_hi > z_lo))
+    return fail(MPCEKF_E_ARG, "limit_map: SOC grid [%g, %g]: finite ends with z_hi > z_lo", z_lo, z_hi);
+  if (nt > 1 && (!std::isfinite(T_lo_degC) || !std::isfinite(T_hi_degC) || !(T_hi_degC > T_lo_degC)))
+    return fail(MPCEKF_E_ARG, "limit_map: temperature grid [%g, %g] degC: finite ends with T_hi > T_lo", T_lo_degC,
+                T_hi_degC);
+  if (interp_z != 0 && interp_z != 1)
+    return fail(MPCEKF_E_ARG, "limit_map: interp_z = %d: 0 (linear) or 1 (hold)", interp_z);
+  if (nsets < 1) return fail(MPCEKF_E_ARG, "limit_map: nsets = %d: 1 or more", nsets);
+  const size_t plane = (size_t)nt * (size_t)nz, ntabs = (size_t)nsets * (size_t)nfields * plane;
+  for (size_t i = 0; i < ntabs; ++i)
+    if (!std::isfinite(tables[i]))
+      return fail(MPCEKF_E_ARG, "limit_map: tables[%zu] = %g is not finite (set %zu, field %zu, T node %zu, SOC node %zu)",
+                  i, tables[i], i / ((size_t)nfields * plane), i / plane % nfields, i / nz % nt, i % nz);
+  const size_t nc = (size_t)X->n;
+  for (size_t c = 0; set_of_cell && c < nc; ++c)
+    if (set_of_cell[c] < 0 || set_of_cell[c] >= nsets)
+      return fail(MPCEKF_E_ARG, "limit_map: set_of_cell[%zu] = %d outside 0..%d", c, set_of_cell[c], nsets - 1);
+  for (size_t c = 0; z0 && c < nc; ++c)
+    if (std::isinf(z0[c])) return fail(MPCEKF_E_ARG, "limit_map: z0[%zu] = %g: finite, or NaN for no estimate", c, z0[c]);
+  if (X->sched)
+    return fail(MPCEKF_E_STATE, "limit_map: a temperature schedule is active (mpcekf_thermal_schedule_end first)");
+  if (nt > 1 && !X->d_th) return fail(MPCEKF_E_STATE, "limit_map: nt = %d: call mpcekf_thermal_begin first", nt);
+  int rc;
+  HIPCHK(hipSetDevice(X->device));
+  const size_t n = std::max<size_t>(nc, 1);
+  // every buffer before anything is stored: a failed allocation leaves the map as it was
+  if (!X->d_lm_hdr && (rc = dalloc(&X->d_lm_hdr, 1))) return rc;
+  if (!X->d_lm_set && (rc = dalloc(&X->d_lm_set, n))) return rc;
+  if (!X->d_lm_val && (rc = dalloc(&X->d_lm_val, n * MAP_MAXF))) return rc;
+  if (!X->d_lm_soc && (rc = dalloc(&X->d_lm_soc, n))) return rc;
+  if (!X->d_lm && (rc = dalloc(&X->d_lm, n * NLMR))) return rc;
+  if (X->lm_cap < ntabs) {
+    double *t = nullptr;
+    if ((rc = dalloc(&t, ntabs))) return rc;
+    if (X->d_lm_tab) {  // no launch in flight reads the old tables, and no graph names them any more
+      HIPCHK(hipStreamSynchronize(X->stream));
+      X->retire_graphs([](const GraphParts &k) { return k.map.rec != 0; });
+      (void)hipFree(X->d_lm_tab);
+    }
+    X->d_lm_tab = t;
+    X->lm_cap = ntabs;
+  }
+  if ((rc = limits_bufs(X))) return rc;
+  h.z_lo = z_lo;
+  h.z_hi = z_hi;
+  h.T_lo = nt > 1 ? T_lo_degC : 0.0;
+  h.T_hi = nt > 1 ? T_hi_degC : 1.0;
+  h.Q = X->r.Q;
+  h.nz = nz;
+  h.nt = nt;
+  h.interp_z = interp_z;
+  h.nf = nfields;
+  h.nsets = nsets;
+  X->h_lm = h;
+  std::copy_n(fields, nfields, X->h_lm_field);
+  HIPCHK(hipMemcpyAsync(X->d_lm_hdr, &X->h_lm, sizeof(MapHdr), hipMemcpyHostToDevice, X->stream));
+  HIPCHK(hipMemcpyAsync(X->d_lm_tab, tables, ntabs * 8, hipMemcpyHostToDevice, X->stream));
+  if (nc && set_of_cell) HIPCHK(hipMemcpyAsync(X->d_lm_set, set_of_cell, nc * 4, hipMemcpyHostToDevice, X->stream));
+  if (nc && !set_of_cell) HIPCHK(hipMemsetAsync(X->d_lm_set, 0, nc * 4, X->stream));
+  // the record restarts; Z_LAST from z0, or NaN, or -- replacing an active map without a z0 -- kept
+  if (nc && z0) HIPCHK(hipMemcpyAsync(X->d_lm + (size_t)LM_Z_LAST * nc, z0, nc * 8, hipMemcpyHostToDevice, X->stream));
+  if ((rc = lerr(launch_map_reset(X->d_lm, z0 || X->lmap, X->n, X->stream), "map_reset"))) return rc;
+  // the limits record from the values set_limits or the configuration gave (a replaced map's fields
+  // go back to them), then the new map's fields at Z_LAST and the temperatures as they stand
+  X->lmap = true;
+  X->percell = true;
+  return limits_upload(X);
+}
+
+int mpcekf_limit_map_get(mpcekf_ctx *X, int32_t nfields, const int32_t *fields, double *values) {
+  int rc = check_rows(X, "limit_map_get", "LM", MPCEKF_NLM, nfields, fields, values);
+  if (rc) return rc;
+  if (!X->lmap) return fail(MPCEKF_E_STATE, "limit_map_get: call mpcekf_limit_map first");
+  return get_rows(X, X->d_lm, (size_t)X->n, nfields, fields, values);
+}
+
+int mpcekf_limit_map_end(mpcekf_ctx *X) {
+  if (!X) return fail(MPCEKF_E_ARG, "limit_map_end: null ctx");
+  if (!X->lmap) return MPCEKF_OK;
+  HIPCHK(hipSetDevice(X->device));
+  HIPCHK(hipStreamSynchronize(X->stream));
+  // the graphs captured with the map launch its kernels: none is replayed on a context without one
+  X->retire_graphs([](const GraphParts &k) { return k.map.rec != 0; });
+  X->lmap = false;  // the buffers stay to the context's end
+  X->h_lm.nf = 0;
+  if (X->lim_set) return limits_upload(X);  // the mapped fields back to what set_limits gave them
+  X->percell = false;
+  X->h_lim.clear();
+  return MPCEKF_OK;
+}
+
+int mpcekf_step_ex_map(mpcekf_ctx *X, int32_t nsteps, const double *tc_degC, const mpcekf_traj *tr, const int32_t *slots,
+                       int32_t nslots, double *obs, double *temp, double *heat, double *ucmd, int32_t *limiter,
+                       double *bleed, double *zmin, double *vstr, double *istr, int32_t *capby, double *lim,
+                       int32_t outputs_on_device) {
+  if (!X) return fail(MPCEKF_E_ARG, "step_ex_map: null ctx");
+  if (!X->lmap) return fail(MPCEKF_E_STATE, "step_ex_map: call mpcekf_limit_map first");
+  if ((temp || heat) && !X->d_th)
+    return fail(MPCEKF_E_STATE, "step_ex_map: temp / heat rows: call mpcekf_thermal_begin first");
+  if ((ucmd || limiter) && !X->d_pk)
+    return fail(MPCEKF_E_STATE, "step_ex_map: ucmd / limiter rows: call mpcekf_pack_begin first");
+  if ((bleed || zmin) && !(X->d_pk && X->d_bl))
+    return fail(MPCEKF_E_STATE, "step_ex_map: bleed / zmin rows: call mpcekf_balance_begin first");
+  if ((vstr || istr || capby) && !(X->d_pk && X->d_ch))
+    return fail(MPCEKF_E_STATE, "step_ex_map: vstr / istr / capby rows: call mpcekf_charger_begin first");
+  StepOut o;
+  o.temp = temp;
+  o.heat = heat;
+  o.ucmd = ucmd;
+  o.limiter = limiter;
+  o.bleed = bleed;
+  o.zmin = zmin;
+  o.vstr = vstr;
+  o.istr = istr;
+  o.capby = capby;
+  o.lim = lim;
+  return step_impl(X, nsteps, tc_degC, tr, slots, nslots, obs, outputs_on_device, o);
 }
 
 int mpcekf_step_ex_thermal(mpcekf_ctx *X, int32_t nsteps, const mpcekf_traj *tr, const int32_t *slots, int32_t nslots,

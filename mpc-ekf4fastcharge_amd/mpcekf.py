@@ -266,6 +266,7 @@ class Context:
         s = self._vec(soc0_pct)
         t = self._vec(tc_degC)
         check(self.L.mpcekf_init_cells(self.h, dptr(s), dptr(t)))
+        self._soc0 = s / 100.0   # limit_map's default z0 (the unit of step()'s soc) until a fused step has run
 
     # -- fused loop (runMPC.m:83-112) ------------------------------------
     # runMPC.m stores per step: name -> (dtype, trailing shape); see mpcekf_traj
@@ -282,7 +283,7 @@ class Context:
                      capby=(True, np.int32))
 
     def step(self, nsteps, outputs=("u", "v", "soc", "phise", "nexec"), tc=None, obs=None, thermal=None, pack=None,
-             aging=None):
+             aging=None, limit_map=None):
         """nsteps fused closed-loop steps (runMPC.m:83-112).  ``outputs`` names the per-step
         stores to return as [nsteps, ncells(, k)] arrays: u, v, soc, phise, nexec, and the
         diagnostics x (x_store), zk / zbk (zkEst / zkBound), J_unc, J_fin, norm_du, nviol
@@ -315,8 +316,20 @@ class Context:
         ``aging``: on an aging context (aging_begin), ("rate",) returns out["rate"]
         [nsteps, nsrc * nreact, ncells], every step's side-reaction currents (A): the enabled
         sources in the order est, plant, the reactions inside; mpcekf_step_ex_aging.  None: the
-        call as it was (an aging context accumulates its record all the same)."""
+        call as it was (an aging context accumulates its record all the same).
+        ``limit_map``: on a context with a limit map (limit_map), ("lim",) returns out["lim"]
+        [nsteps, nfields, ncells], the mapped fields' values the MPC stage of every step read, in
+        the order the map named them; mpcekf_step_ex_map, which takes every thermal and pack row
+        above but has no "cond" or "rate" row.  None: the call as it was (the map is evaluated all
+        the same)."""
         n = self.n
+        lm = () if limit_map is None else (limit_map,) if isinstance(limit_map, str) else tuple(limit_map)
+        for k in lm:
+            if k != "lim":
+                raise KeyError(f"step: unknown limit_map row {k!r} (one of ('lim',))")
+        if limit_map is not None and (aging is not None or (thermal is not None and "cond" in
+                                                            ((thermal,) if isinstance(thermal, str) else tuple(thermal)))):
+            raise ValueError("step: the map's row (lim) comes from mpcekf_step_ex_map, which has no cond or rate row")
         fields, slots = self._obs_select(obs, "step")   # KeyError before any library call
         th = () if thermal is None else (thermal,) if isinstance(thermal, str) else tuple(thermal)
         for k in th:
@@ -362,12 +375,17 @@ class Context:
         if "rate" in ag:
             nreact, mask = getattr(self, "_aging", (0, 0))   # (0, 0): no begin, the library refuses the call
             out["rate"] = np.empty((nsteps, max(bin(mask).count("1") * nreact, 1), n))
+        if "lim" in lm:
+            out["lim"] = np.empty((nsteps, max(getattr(self, "_map_nf", 0), 1), n))   # 0: no map, the library refuses
         row = lambda *names: tuple(vp(out.get(k)) for k in names)
         ns = 0 if fields is None else int(slots.size)
         head, tail = (self.h, int(nsteps)), (C.byref(tr), iptr(slots) if ns else None, ns, vp(rec) if ns else None)
         call = head + (tcp,) + tail
         # the entry point, in this order: it decides which refusal of the library a misuse gets
-        if chg:   # a pack context with a charger (and a balancer, for bleed / zmin)
+        if limit_map is not None:   # a mapped context, whatever else it carries
+            check(self.L.mpcekf_step_ex_map(*call, *row("temp", "heat", "ucmd", "limiter", "bleed", "zmin", "vstr",
+                                                        "istr", "capby", "lim"), 0))
+        elif chg:   # a pack context with a charger (and a balancer, for bleed / zmin)
             check(self.L.mpcekf_step_ex_charger(*call, *row("temp", "heat", "ucmd", "limiter", "bleed", "zmin", "vstr",
                                                             "istr", "capby"), 0))
         elif bal:   # a pack context with a balancer
@@ -387,6 +405,7 @@ class Context:
                                             rec.ctypes.data_as(C.c_void_p), 0))
         else:
             check(self.L.mpcekf_step_ex(self.h, int(nsteps), tcp, C.byref(tr), 0))
+        self._stepped(nsteps)
         if fields is not None:
             lay, pos, out["obs"] = self.rom.obs_layout(), 0, {}
             for k in fields:   # slot-major rows per step -> [nsteps, n] / [nsteps, n, len]
@@ -396,6 +415,12 @@ class Context:
         if "poles" in out:
             out["poles"] = _complex(out["poles"])
         return out
+
+    def _stepped(self, nsteps):
+        """After a fused call: once a step has run, the SOC given to init_cells is no longer the
+        estimate, so limit_map's default z0 is mpcekf_limit_map's own (NaN for a first map)."""
+        if nsteps:
+            self._soc0 = None
 
     def _obs_select(self, obs, who):
         """obs=None / True / name / names -> (fields, int32 slots of the record), (None, None)
@@ -420,6 +445,7 @@ class Context:
         sl = np.ascontiguousarray(obs_slots, dtype=np.int32).ravel()
         if not obs and not sl.size:
             check(self.L.mpcekf_step(self.h, int(nsteps), None, *p, 1))
+            self._stepped(nsteps)
             return
         tr = _lib.Traj()
         for k, x in zip(("u", "v", "soc", "phise", "nexec"), p):
@@ -427,6 +453,7 @@ class Context:
         op = C.c_void_p(obs.ptr if isinstance(obs, DeviceBuffer) else obs) if obs else None
         check(self.L.mpcekf_step_ex_obs(self.h, int(nsteps), None, C.byref(tr), iptr(sl) if sl.size else None,
                                         int(sl.size), op, 1))
+        self._stepped(nsteps)
 
     def sync(self):
         """Wait for every launch on the context's device and complete the asynchronous stage
@@ -527,6 +554,7 @@ class Context:
         trajectory is returned and none is kept (mpcekf_step_summary)."""
         tcs = None if tc is None else tc_grid(tc, nsteps, self.n)
         check(self.L.mpcekf_step_summary(self.h, int(nsteps), tcs.ctypes.data_as(C.c_void_p) if tcs is not None else None))
+        self._stepped(nsteps)
 
     def get_summary(self, fields=None):
         """{name: [ncells] float64} of the summary record (mpcekf_get_summary): ``fields`` names
@@ -589,6 +617,8 @@ class Context:
         """Drop the thermal model (mpcekf_thermal_end): the cells keep their temperature; a
         schedule over it ends too."""
         check(self.L.mpcekf_thermal_end(self.h))
+        if getattr(self, "_map_nt", 1) > 1:   # a map with a temperature axis ended with the model
+            self._map_nf, self._map_nt = 0, 1
 
     SCHEDULE_FIELDS = _lib.SCHEDULE_FIELDS
 
@@ -649,6 +679,98 @@ class Context:
         """End the schedule (mpcekf_thermal_schedule_end): its fields go back to what set_limits
         or the configuration gave them."""
         check(self.L.mpcekf_thermal_schedule_end(self.h))
+
+    # -- MPC limits mapped over the SOC estimate and the temperature ---------
+    LIMIT_MAP_FIELDS = _lib.LIMIT_MAP_FIELDS
+
+    @classmethod
+    def _map_arrays(cls, n, sets, interp_z, z0, tables):
+        """limit_map's arguments -> (int32 ids [nf], float64 tables [nsets][nf][nt][nz], int32
+        set_of_cell [n] or None, interp_z 0 / 1, float64 z0 [n] or None).  A table is [nz] (no
+        temperature axis), [nt][nz] or [nsets][nt][nz].  ValueError for an unknown, repeated or
+        unmappable field, no field at all, tables of different shapes, a bad ``sets``, ``interp_z``
+        or ``z0`` shape: before any library call.  The values themselves are the library's to
+        check."""
+        if not tables:
+            raise ValueError(f"limit_map: no field given (one of {cls.SCHEDULE_FIELDS})")
+        if interp_z not in ("linear", "hold", 0, 1):
+            raise ValueError(f"limit_map: interp_z = {interp_z!r}: 'linear' or 'hold'")
+        ids, tabs = [], []
+        for k, v in tables.items():
+            if k not in cls.SCHEDULE_FIELDS:
+                raise ValueError(f"limit_map: field {k!r} cannot be mapped (one of {cls.SCHEDULE_FIELDS})")
+            a = np.asarray(v, dtype=np.float64)
+            if a.ndim not in (1, 2, 3):
+                raise ValueError(f"limit_map: {k} must be a [nz], [nt][nz] or [nsets][nt][nz] table, got shape {a.shape}")
+            ids.append(cls.LIMIT_FIELDS.index(k))
+            tabs.append(a)
+        three = [a for a in tabs if a.ndim == 3]
+        two = [a for a in tabs if a.ndim >= 2]
+        nsets = three[0].shape[0] if three else 1
+        nt = two[0].shape[-2] if two else 1
+        nz = tabs[0].shape[-1]
+        for k, a in zip(tables, tabs):
+            if a.shape[-1] != nz or (a.ndim >= 2 and a.shape[-2] != nt) or (a.ndim == 3 and a.shape[0] != nsets):
+                raise ValueError(f"limit_map: {k} has shape {a.shape}: every table is [{nz}], [{nt}][{nz}] or "
+                                 f"[{nsets}][{nt}][{nz}] here")
+        if nsets < 1 or nt < 1 or nz < 1:
+            raise ValueError(f"limit_map: empty tables ({nsets} sets of {nt} x {nz} entries)")
+        # [nf][nsets][nt][nz] -> [nsets][nf][nt][nz]; a smaller table serves every set / temperature
+        tab = np.stack([np.broadcast_to(a, (nsets, nt, nz)) for a in tabs]).transpose(1, 0, 2, 3)
+        soc = None
+        if sets is not None:
+            soc = np.asarray(sets)
+            if soc.shape != (n,) or not np.issubdtype(soc.dtype, np.integer):
+                raise ValueError(f"limit_map: sets must be a length-{n} integer array, got shape {soc.shape} of {soc.dtype}")
+            soc = np.ascontiguousarray(soc, dtype=np.int32)
+        z = None if z0 is None else np.ascontiguousarray(cls._per_cell(n, "z0", z0, "limit_map"))
+        return (np.asarray(ids, dtype=np.int32), np.ascontiguousarray(tab, dtype=np.float64), soc,
+                int(interp_z in ("hold", 1)), z)
+
+    def limit_map(self, z_lo, z_hi, T_lo=None, T_hi=None, sets=None, interp_z="linear", z0=None, **tables):
+        """Map MPC limits over (SOC estimate, cell temperature) (mpcekf_limit_map): each keyword is
+        a limit field's name as in set_limits (Crate, u_max, du_min, du_max, v_max, phise_min;
+        make_config's units) with a table on the uniform grids ``z_lo`` .. ``z_hi`` (SOC fraction,
+        the unit of step()'s ``soc``) and ``T_lo`` .. ``T_hi`` (degC): [nz] (no temperature axis:
+        any context), [nt][nz] (needs thermal_begin) or, for several maps in one batch,
+        [nsets][nt][nz] with ``sets`` [ncells] naming each cell's map (None: map 0).
+        ``interp_z``: "linear", or "hold" for the left node's value (see :func:`mscc_map`); the
+        temperature axis is linear.  From then on the MPC stage of every fused step reads, per
+        cell, the table value at the previous step's ``soc`` and the temperature the step uses,
+        clamped to the grids' ends.  ``z0`` (scalar or [ncells]): the SOC to evaluate at until a
+        fused step has run.  None: when the call replaces an active map, the record's z_last as it
+        stands; else the SOC given to init_cells if no fused step has run since; else NaN, the
+        first column, as mpcekf_limit_map's NULL (a map set on a context that has stepped without
+        one, after limit_map_end for instance: pass the last ``soc`` row as z0 to start from it).
+        get_limits returns the values in force; a second call replaces the map."""
+        ids, tab, soc, hold, z = self._map_arrays(self.n, sets, interp_z, z0, tables)   # ValueError before any library call
+        nt = tab.shape[2]
+        if nt > 1 and (T_lo is None or T_hi is None):
+            raise ValueError("limit_map: tables with a temperature axis need T_lo and T_hi")
+        if z is None and not getattr(self, "_map_nf", 0) and getattr(self, "_soc0", None) is not None:
+            z = np.ascontiguousarray(self._soc0)
+        check(self.L.mpcekf_limit_map(self.h, int(ids.size), iptr(ids), int(tab.shape[3]), float(z_lo), float(z_hi),
+                                      int(nt), float(0.0 if T_lo is None else T_lo), float(1.0 if T_hi is None else T_hi),
+                                      hold, int(tab.shape[0]), dptr(tab), iptr(soc), dptr(z)))
+        self._map_nf, self._map_nt = int(ids.size), int(nt)
+
+    def limit_map_get(self, fields=None):
+        """{name: [ncells] float64} of the map's record (mpcekf_limit_map_get): ``fields`` names of
+        LIMIT_MAP_FIELDS (default all).  Counts are exact integers."""
+        names = self.LIMIT_MAP_FIELDS if fields is None else (fields,) if isinstance(fields, str) else tuple(fields)
+        for k in names:
+            if k not in self.LIMIT_MAP_FIELDS:
+                raise KeyError(f"limit_map_get: unknown field {k!r} (one of {self.LIMIT_MAP_FIELDS})")
+        ids = np.asarray([self.LIMIT_MAP_FIELDS.index(k) for k in names], dtype=np.int32)
+        vals = np.empty((ids.size, self.n))
+        check(self.L.mpcekf_limit_map_get(self.h, int(ids.size), iptr(ids), dptr(vals)))
+        return {k: vals[i] for i, k in enumerate(names)}
+
+    def limit_map_end(self):
+        """End the map (mpcekf_limit_map_end): its fields go back to what set_limits or the
+        configuration gave them."""
+        check(self.L.mpcekf_limit_map_end(self.h))
+        self._map_nf = 0
 
     # -- heat conduction between neighbouring cells of a pack string --------
     COUPLE_FIELDS = ("NB_SUM", "DT_MAX", "DT_MAX_STEP")   # include/mpcekf.h MPCEKF_TCR_*
@@ -893,6 +1015,7 @@ class Context:
         t = None if tc is None else np.ascontiguousarray(self._per_cell(self.n, "tc", tc, who="step_until"))
         run, left = C.c_int32(), C.c_int64()
         check(self.L.mpcekf_step_until(self.h, int(max_steps), int(chunk), dptr(t), C.byref(run), C.byref(left)))
+        self._stepped(run.value)
         return run.value, left.value
 
     # -- side-reaction losses per cell (plating, SEI) -----------------------
@@ -1317,6 +1440,35 @@ def thermal_ocv(rom, n=101, T_degC=25.0):
                      for z in np.linspace(0.0, 1.0, int(n)).tolist()], dtype=np.float64)
 
 
+def mscc_map(soc_breaks, crates, nz):
+    """A multi-stage constant-current staircase as a hold-interpolated table: (z_lo, z_hi, table
+    [nz]) for Context.limit_map(z_lo, z_hi, interp_z="hold", Crate=table).  ``crates`` [m]: the
+    C-rate of each stage; ``soc_breaks`` [m + 1] ascending SOC fractions: stage i holds on
+    [soc_breaks[i], soc_breaks[i + 1]), the first stage also below soc_breaks[0] and the last at
+    and above soc_breaks[-1].  The grid is uniform with ``nz`` nodes over soc_breaks[0] ..
+    soc_breaks[-1], and node j carries the stage its SOC lies in, so a break that is not a node
+    takes effect at the next node above it: choose nz so that (nz - 1) * (break - z_lo) /
+    (z_hi - z_lo) is an integer for an exact staircase.  Host numpy only."""
+    b = np.asarray(soc_breaks, dtype=np.float64)
+    c = np.asarray(crates, dtype=np.float64)
+    if b.ndim != 1 or c.ndim != 1 or b.size != c.size + 1 or c.size < 1:
+        raise ValueError(f"mscc_map: {c.size} stages need {c.size + 1} soc_breaks, got {b.size}")
+    if not np.all(np.diff(b) > 0):
+        raise ValueError("mscc_map: soc_breaks must ascend")
+    if int(nz) != nz or int(nz) < 2:
+        raise ValueError(f"mscc_map: nz = {nz!r}: 2 nodes or more")
+    z = b[0] + (b[-1] - b[0]) * (np.arange(int(nz)) / (int(nz) - 1))
+    # a node within rounding of a break belongs to the stage the break opens
+    stage = np.searchsorted(b[1:-1], z + 1e-12 * (b[-1] - b[0]), side="right")
+    return float(b[0]), float(b[-1]), c[stage]
+
+
+def _limit_map(ctx, limit_map):
+    """runMPC's / run_summary's limit_map dict: Context.limit_map's arguments."""
+    if limit_map:
+        ctx.limit_map(**limit_map)
+
+
 def _thermal_begin(ctx, thermal):
     """runMPC's / run_summary's thermal dict: thermal_begin's keywords, plus an optional
     "schedule": a dict of thermal_schedule's (T_lo, T_hi, sets and the tables), and an optional
@@ -1394,8 +1546,13 @@ def _stop_args(n, stop, who, chunk=False):
 
 
 def runMPC(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=None, obs=None, limits=None,
-           thermal=None, pack=None, aging=None, stop=None):
+           thermal=None, pack=None, aging=None, stop=None, limit_map=None):
     """runMPC.m:72-112 for a batch of cells; returns trajectories [nsteps, ncells].
+    limit_map: a dict of Context.limit_map's arguments (z_lo, z_hi, T_lo, T_hi, sets, interp_z, z0,
+    the tables): limits that follow each cell's SOC estimate and temperature, set after the
+    extensions below; adds out["limits"], the values in force at the last step, out["limit_map"],
+    the map's record, and (not with aging or thermal["couple"], whose calls have no such row)
+    out["lim"], the values every step read.
     tc_traj [nsteps, ncells] (degC): a temperature profile (TC is the initial one).
     obs: the plant's observables of every step as out["obs"] (Context.step's obs=).
     limits: per-cell targets and limits, a dict of Context.set_limits' keywords (a protocol
@@ -1444,12 +1601,18 @@ def runMPC(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=None,
             ctx.aging_begin(**aging)
         if term:
             check(ctx.L.mpcekf_term_begin(ctx.h, dptr(term[0]), term[1]))
+        _limit_map(ctx, limit_map)
+        lm_rows = bool(limit_map) and not aging and links is None
         th_rows = ("temp", "heat", "cond") if links is not None else ("temp", "heat")
         pk_rows = ("ucmd", "limiter", "bleed", "zmin") if bal and not aging and links is None else ("ucmd", "limiter")
         if chg is not None and not aging and links is None:
             pk_rows += ("vstr", "istr", "capby")
         out = ctx.step(nsteps, tc=tc_traj, obs=obs, thermal=th_rows if thermal else None,
-                       pack=pk_rows if pack else None, aging=("rate",) if aging else None)
+                       pack=pk_rows if pack else None, aging=("rate",) if aging else None,
+                       limit_map=("lim",) if lm_rows else None)
+        if limit_map:
+            out["limits"] = ctx.get_limits()
+            out["limit_map"] = ctx.limit_map_get()
         if aging:
             out["aging"] = ctx.aging_record()
         if term:
@@ -1471,7 +1634,7 @@ def runMPC(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=None,
 
 
 def run_summary(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=None, limits=None, reach=None,
-                obs=None, chunk=None, thermal=None, pack=None, aging=None, stop=None):
+                obs=None, chunk=None, thermal=None, pack=None, aging=None, stop=None, limit_map=None):
     """runMPC.m:72-112 for a batch of cells, read out as the per-cell charge summary instead of
     trajectories: {field: [ncells]} of Context.get_summary plus "status".  limits: as runMPC's
     (a protocol sweep); reach, obs: Context.summary_begin's; tc_traj [nsteps, ncells] (degC): a
@@ -1485,7 +1648,8 @@ def run_summary(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=
     thermal["couple"] with a pack: as runMPC's; adds "couple", the coupling's record.
     stop: a dict of Context.term_begin's keywords plus chunk (default 64): the loop runs through
     Context.step_until with nsteps as the cap and ends when every cell is done (no tc_traj: TC
-    holds); adds "steps_run", the steps run, and "term", the rule's record."""
+    holds); adds "steps_run", the steps run, and "term", the rule's record.
+    limit_map: as runMPC's; adds "limit_map", the map's record."""
     SOC0 = np.atleast_1d(np.asarray(SOC0, dtype=np.float64))
     n = ncells or SOC0.shape[0]
     nsteps = int(nsteps)
@@ -1515,6 +1679,7 @@ def run_summary(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=
             ctx.thermal_couple(links)
         if aging:
             ctx.aging_begin(**aging)
+        _limit_map(ctx, limit_map)
         ctx.summary_begin(reach=reach, obs=obs)
         if term:
             check(ctx.L.mpcekf_term_begin(ctx.h, dptr(term[0]), term[1]))
@@ -1524,6 +1689,8 @@ def run_summary(rom, SOC0, TC, nsteps, cfg=None, device=0, ncells=None, tc_traj=
                 m = min(chunk, nsteps - k)
                 ctx.step_summary(m, tc=None if tcs is None else tcs[k:k + m])
         out = ctx.get_summary()
+        if limit_map:
+            out["limit_map"] = ctx.limit_map_get()
         if term:
             out["steps_run"] = steps_run
             out["term"] = ctx.term_get()
